@@ -14,7 +14,14 @@ The timed steps rotate over ``--batches`` (8) distinct seeded candidate batches,
 bounds-checked once before the timed region (what ``pipeline.score_edges`` does for a whole split);
 ``value_validate_per_batch`` is the same loop with the per-batch check (one host sync per batch) left on.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (``metric``, ``value``, ``unit``,
+``ms_per_step``, ...).  Everything else it can measure or check — stage timers and roofline objects, repeats of the
+timed loop, the one-stream / per-batch-validation / trained-innerprod legs, the CPU baseline and its parity check, the
+encoder timing — runs only with ``--full``.  ``--dump-outputs DIR`` writes the scores of the last timed step as
+``DIR/scores.npy`` (float32; the inputs are seeded, so two builds can be compared output for output).
+
     python bench.py --gpus 1 --steps 128 --warmup 8
+    python bench.py --full                      # the headline line plus every other figure and check
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config citation2          # other BASELINE configs: citation2 | ppa | ddi | cora
@@ -164,14 +171,16 @@ def build_workload(args, dev, rank, world):
     pred = make_predictor(cfg, dev)
     if getattr(args, "innerprod", 0.0):
         pred.innerprod.fill_(args.innerprod)           # a trained checkpoint's buffer (order-exact S2 path of cn5)
+    t_enc = None
     with torch.no_grad():
         h = enc(x, adj)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        for _ in range(3):
-            h = enc(x, adj)
-        torch.cuda.synchronize()
-        t_enc = (time.time() - t0) / 3
+        if getattr(args, "full", True):                   # (the encoder's time is a --full figure)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(3):
+                h = enc(x, adj)
+            torch.cuda.synchronize()
+            t_enc = (time.time() - t0) / 3
     adj2, t_a2 = None, 0.0
     if cfg["route"] != "walk":
         t0 = time.time()
@@ -331,6 +340,23 @@ def pmc_traffic(dataset, kernel_substr):
     return best
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, scores):
+    """--dump-outputs: the scores the last timed step returned, as <path>/scores.npy in float32 — or, above 64 MB, the rows of a
+    fixed seeded sample of them in ascending order, with their row ids as <path>/scores_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    s = scores.detach().float().cpu()
+    if s.numel() * 4 > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (8 + 4 * s[0].numel())            # a float64 row id + the row's float32 scores
+        rows = torch.randperm(s.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        s = s[rows]
+        np.save(os.path.join(path, "scores_rows.npy"), rows.double().numpy())
+    np.save(os.path.join(path, "scores.npy"), s.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,6 +392,12 @@ def main():
     ap.add_argument("--rehearse-collectives", action="store_true",
                     help="one rank, but with the N > 1 code path: RCCL process group, histogram all-reduce and score "
                          "all-gather executed (a one-GPU box can then time what the collectives add); not a bench line")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: stage timers and roofline objects, --repeats, the one-stream, per-batch "
+                         "validation and trained-innerprod legs, the CPU baseline with its parity check, the encoder timing "
+                         "(the --no-* switches above act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step as DIR/scores.npy (float32)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -561,9 +593,15 @@ def main():
             dt = tmax.item()
         return dt, t_launch, out
 
+    if not args.full:
+        args.no_stage_timers = True                # (a plain run: the headline loop only, no stage events in it)
     timer = None if args.no_stage_timers else StageTimer(pool=48 * (args.steps // max(args.timer_every or max(1, args.steps // 8), 1) + 2), lean=not args.all_stages)
     dt, t_launch, out = timed_loop(args.steps, timer)
     pattern_main = pattern[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if not args.full:
+        args.repeats, args.no_validate_leg, args.no_cpu_baseline = 1, True, True
     # the same timed loop again (no stage events): the spread of the step time from run to run, reported beside `value`
     runs = [dt / args.steps] + [timed_loop(args.steps, None)[0] / args.steps for _ in range(max(args.repeats, 1) - 1)]
     pattern[0] = pattern_main
@@ -612,96 +650,6 @@ def main():
         step(0)
 
     if rank == 0:
-        per = [batch_bytes(wl, m, H) for m in mines]
-        ab = {k: sum(p[k] for p in per) / NB for k in per[0]}
-        stages = {k: dict(ms=v[0], launches=v[1], ms_per_step=v[2]) for k, v in (timer.totals() if timer else {}).items()}
-        sampled = max(timer.sampled_steps, 1) if timer else 1
-        roof, roof_hbm, roofs = None, None, {}
-        if stages:
-            kname = {"cn_flags": "cn_walk_kernel" if cfg["route"] == "walk" else "cn_flags_kernel",
-                     "cn_gather": "cn_gather_wave_kernel" if (H <= 64 and mines[0].shape[1] * (H // 4) < 262144) else "cn_gather_kernel"}
-            for k, comp, form in (("cn_flags", "flags_compulsory", "flags_formula"), ("cn_gather", "gather_compulsory", "gather_formula")):
-                if k not in stages:
-                    continue
-                t = stages[k]["ms"] * 1e-3
-                tr = pmc(kname[k])
-                roofs[k] = dict(bound="hbm", kernel=kname[k], achieved=ab[comp] / t / 1e9, peak=HBM_PEAK / 1e9, unit="GB/s",
-                                frac=ab[comp] / t / HBM_PEAK, traffic=tr,
-                                traffic_frac=None if tr is None else tr / t / HBM_PEAK,
-                                algorithmic_bytes_per_launch=ab[comp], survey_formula_bytes_per_launch=ab[form],
-                                survey_formula_GBps=ab[form] / t / 1e9, avg_launch_ms=stages[k]["ms"],
-                                note="achieved = compulsory bytes of the batch (distinct embedding / weight rows once, "
-                                     "CSR rows walked, outputs) / launch time; the SURVEY §8d formula (one row per CN "
-                                     "entry, whole A² row) is printed beside it and may exceed the HBM peak because "
-                                     "shared rows are served by L2; traffic = PMC 2*FETCH_SIZE + WRITE_SIZE of the "
-                                     "committed profile")
-                stages[k]["compulsory_GBps"] = roofs[k]["achieved"]
-            stages1 = {k: dict(ms=v[0], launches=v[1], ms_per_step=v[2]) for k, v in (timer1.totals() if timer1 else {}).items()}
-            # the dominant kernel: the stage with the most time per STEP inside the timed region (same-stream event pairs)
-            dom = max((k for k in ("cn_flags", "cn_gather", "linear") if k in stages), key=lambda k: stages[k]["ms_per_step"])
-            roof_hbm = roofs.get("cn_gather")
-            if "linear" in stages:
-                # MFMA work of the MLP heads per launch.  The fused kernel (ocn_heads_fused, H >= 128) multiplies a row by
-                # 8 H x H panels (the reference's 9 Linear(H,H): the last layer of each branch is folded into lin's Linear
-                # offline, model._fused_pack), skips, per 128-row tile of the class-major order, the pooled branches whose
-                # input is all zero, and evaluates every f32 product as THREE f16 MFMAs (hi/lo splits of both operands).
-                # The grouped Linear launches (narrower heads) issue six bf16 MFMAs per product.  frac is the fraction of
-                # the pipe the kernel runs on: issued f16 / bf16 MFMA FLOPs over the dense 16-bit MFMA peak.
-                launches_per_step = stages["linear"]["launches"] / sampled
-                Bm = mines[0].shape[1]
-                t = stages["linear"]["ms"] * 1e-3
-                fused = bool(ops.fused_heads and H >= ops.fused_heads_min_width and getattr(pred, "_fused_plan", lambda H: None)(H) is not None)
-                ref_fl = timer.flops.get("linear", 0.0) / stages["linear"]["launches"]
-                skip = getattr(pred, "_skip_state", None)
-                skipping = bool(ops.skip_zero_rows and skip is not None and skip["off"] == 0 and Bm >= ops.skip_zero_min_batch)
-                n_cn1, n_any = ab["n_cn1"], ab["n_any"]
-                n_b = n_any if pred._xcn2_on_union else ab["n_cn2"]
-                if fused:
-                    rows_a, rows_b = (n_cn1, n_b) if skipping else (Bm, Bm)
-                    f32_fl = 2.0 * H * H * (3 * rows_a + 3 * rows_b + 2 * Bm) / launches_per_step
-                    kern, terms, pipe = "heads_fused_kernel", 3, "f16"
-                else:
-                    f32_fl = ref_fl
-                    if skipping and pred._heads_plan(H) is not None:
-                        sx_layers = len(pred._heads_plan(H)[2])
-                        lin_layers = sum(1 for m in pred.lin if isinstance(m, torch.nn.Linear) and m.out_features == H)
-                        f32_fl = (2.0 * H * H * (2 * n_cn1 + 2 * n_b + sx_layers * Bm + lin_layers * Bm)
-                                  + 2.0 * (2 * H) * H * n_any) / launches_per_step
-                    kern, terms, pipe = "linear_bf16x6_kernel", 6, "bf16"
-                issued = terms * f32_fl
-                roofs["heads"] = dict(bound="mfma", kernel=kern, achieved=issued / t / 1e12, peak=BF16_MFMA_PEAK / 1e12,
-                                      unit="TFLOP/s", frac=issued / t / BF16_MFMA_PEAK, traffic=pmc(kern),
-                                      algorithmic_flops_per_launch=issued, avg_launch_ms=stages["linear"]["ms"],
-                                      launches_per_step=launches_per_step, mfma_per_f32_product=terms, mfma_dtype=pipe,
-                                      f32_equivalent_tflops=f32_fl / t / 1e12, f32_equivalent_flops_per_launch=f32_fl,
-                                      f32_equivalent_frac_of_f32_mfma_peak=f32_fl / t / F32_MFMA_PEAK,
-                                      reference_head_f32_flops_per_step=2.0 * H * H * 9 * Bm + 2.0 * H * Bm,
-                                      skipped_zero_rows=skipping,
-                                      note=f"achieved / peak / frac = the {pipe} MFMA FLOPs the launch issues ({terms} MFMAs per f32 "
-                                           "product; 2*H*H per row and panel, rows of skipped all-zero branches excluded, the 9 "
-                                           "Linear(H,H) of the reference folded to 8 panels) against the dense 16-bit MFMA peak; "
-                                           "f32_equivalent_* = the same work counted once per f32 product.  MFMA-busy counters: "
-                                           "profiles/r03_heads_pmc.json.  Head: " + head_layout(pred))
-            for k, rk in (("cn_flags", "cn_flags"), ("cn_gather", "cn_gather"), ("linear", "heads")):
-                if rk in roofs and k in stages1:
-                    t1 = stages1[k]["ms"]
-                    roofs[rk]["avg_launch_ms_one_stream"] = t1
-                    roofs[rk]["frac_one_stream"] = roofs[rk]["frac"] * roofs[rk]["avg_launch_ms"] / t1
-                    stages[k]["ms_one_stream"] = t1
-                    roofs[rk]["note"] += ("  avg_launch_ms / achieved / frac are measured inside the timed region, where the intersection pass "
-                                          "of the next batch runs on a second stream beside this kernel; *_one_stream = the same launch "
-                                          "with the streams serialised.")
-            roof = roofs["heads"] if dom == "linear" else roofs[dom]
-        cpu, err, ref_scale = None, None, None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu, b, ref = cpu_baseline(wl, args, mines[0])
-            ops.validate_indices = False
-            sub = mines[0][:, :b].contiguous()
-            with torch.no_grad():
-                c1, c2 = cn_handles(wl, sub)
-                got = pred(h, adj, c1, c2, sub, wl["args"]).cpu()
-            err = (got - ref).abs().max().item()
-            ref_scale = ref.abs().max().item()
         idx = {"cora": 0, "collab": 1, "ppa": 2, "citation2": 3, "ddi": 4}[args.dataset]
         line = {
             "metric": f"candidate-edges/sec (CN predictor fwd), ogbl-{args.dataset} shape",
@@ -713,10 +661,6 @@ def main():
                              + ("f16x3-split, f32 accumulate (each f32 product = three f16 MFMAs on hi/lo splits of both operands; the "
                                 "dropped lo*lo term is below 2^-22 relative)" if H >= ops.fused_heads_min_width and ops.fused_heads
                                 else "bf16x6-split, f32 accumulate (each f32 product = six bf16 MFMAs)")),
-            "value_runs": [B_total / r for r in runs], "value_min": B_total / max(runs),
-            "value_median": B_total / sorted(runs)[len(runs) // 2], "ms_per_step_runs": [r * 1e3 for r in runs],
-            "stage_timer": {"sampled_steps": sampled, "rule": "HIP events on the launch stream, same-stream pairs only, "
-                            ">= 8 sampled steps, never the priming step"},
             "config": {"workload": f"ogbl-{args.dataset}-shaped synthetic graph, {cfg['enc']} {cfg['conv']} x{cfg['layers']} "
                                    f"hiddim={H} predictor={cfg['pred']} built as the reference drivers build it (only cndeg "
                                    f"forwarded: tailact=False, use_xlin=False, beta=1, lnnn={cfg['lnnn']}; head = "
@@ -727,31 +671,129 @@ def main():
                                    f"region (BASELINE.json configs[{idx}])",
                        "nodes": wl["n"], "nnz": wl["nnz"], "nnz_A2": wl["nnz2"], "max_deg": wl["max_deg"],
                        "global_batch": B_total, "parallelism": f"edge-shard x{world}", "graph_scale": args.scale,
-                       "batches_in_rotation": NB, "innerprod": args.innerprod,
-                       "mean_deg_src": ab["mean_di"], "mean_deg_dst": ab["mean_dj"],
-                       "mean_second_operand_len": ab["mean_second"],
-                       "mean_cn1": ab["mean_c1"], "mean_cn2": ab["mean_c2"],
-                       "distinct_h_rows_per_batch": ab["distinct_h_rows"],
-                       "frac_rows_with_cn1": ab["frac_rows_cn1"], "frac_rows_with_any_cn": ab["frac_rows_any"]},
-            "roofline": roof, "roofline_hbm_kernel": roof_hbm, "rooflines": roofs, "cpu_baseline": cpu,
-            "value_trained_innerprod": None if dt_tr is None else B_total / dt_tr,
-            "ms_per_step_trained_innerprod": None if dt_tr is None else dt_tr * 1e3,
-            "value_one_stream": None if dt1 is None else B_total / dt1,
-            "ms_per_step_one_stream": None if dt1 is None else dt1 * 1e3,
-            "value_validate_per_batch": None if dt_val is None else B_total / dt_val,
-            "ms_per_step_validate_per_batch": None if dt_val is None else dt_val * 1e3,
-            "stages": stages,
-            "once_per_graph": {"encoder_ms": wl["enc_s"] * 1e3, "adj2_build_ms": wl["a2_s"] * 1e3,
-                               "graph_build_s": wl["graph_s"]},
-            "algorithmic_bytes_per_step": ab["flags_compulsory"] + ab["gather_compulsory"],
-            "survey_formula_bytes_per_step": ab["flags_formula"] + ab["gather_formula"],
+                       "batches_in_rotation": NB, "innerprod": args.innerprod},
             "host_enqueue_ms_per_step": t_launch / args.steps * 1e3,
             "communication_pattern": pattern[0],
-            "parity_on_cpu_sample_max_abs_err": err,
-            "parity_on_cpu_sample_max_abs_ref": ref_scale,         # the scores' scale: raw walk-count pools (citation2) reach 1e4
-            "parity_on_cpu_sample_rel_err": None if not ref_scale else err / ref_scale,
             "score_checksum": float(out.double().sum().item()),
         }
+        if args.full:
+            per = [batch_bytes(wl, m, H) for m in mines]
+            ab = {k: sum(p[k] for p in per) / NB for k in per[0]}
+            stages = {k: dict(ms=v[0], launches=v[1], ms_per_step=v[2]) for k, v in (timer.totals() if timer else {}).items()}
+            sampled = max(timer.sampled_steps, 1) if timer else 1
+            roof, roof_hbm, roofs = None, None, {}
+            if stages:
+                kname = {"cn_flags": "cn_walk_kernel" if cfg["route"] == "walk" else "cn_flags_kernel",
+                         "cn_gather": "cn_gather_wave_kernel" if (H <= 64 and mines[0].shape[1] * (H // 4) < 262144) else "cn_gather_kernel"}
+                for k, comp, form in (("cn_flags", "flags_compulsory", "flags_formula"), ("cn_gather", "gather_compulsory", "gather_formula")):
+                    if k not in stages:
+                        continue
+                    t = stages[k]["ms"] * 1e-3
+                    tr = pmc(kname[k])
+                    roofs[k] = dict(bound="hbm", kernel=kname[k], achieved=ab[comp] / t / 1e9, peak=HBM_PEAK / 1e9, unit="GB/s",
+                                    frac=ab[comp] / t / HBM_PEAK, traffic=tr,
+                                    traffic_frac=None if tr is None else tr / t / HBM_PEAK,
+                                    algorithmic_bytes_per_launch=ab[comp], survey_formula_bytes_per_launch=ab[form],
+                                    survey_formula_GBps=ab[form] / t / 1e9, avg_launch_ms=stages[k]["ms"],
+                                    note="achieved = compulsory bytes of the batch (distinct embedding / weight rows once, "
+                                         "CSR rows walked, outputs) / launch time; the SURVEY §8d formula (one row per CN "
+                                         "entry, whole A² row) is printed beside it and may exceed the HBM peak because "
+                                         "shared rows are served by L2; traffic = PMC 2*FETCH_SIZE + WRITE_SIZE of the "
+                                         "committed profile")
+                    stages[k]["compulsory_GBps"] = roofs[k]["achieved"]
+                stages1 = {k: dict(ms=v[0], launches=v[1], ms_per_step=v[2]) for k, v in (timer1.totals() if timer1 else {}).items()}
+                # the dominant kernel: the stage with the most time per STEP inside the timed region (same-stream event pairs)
+                dom = max((k for k in ("cn_flags", "cn_gather", "linear") if k in stages), key=lambda k: stages[k]["ms_per_step"])
+                roof_hbm = roofs.get("cn_gather")
+                if "linear" in stages:
+                    # MFMA work of the MLP heads per launch.  The fused kernel (ocn_heads_fused, H >= 128) multiplies a row by
+                    # 8 H x H panels (the reference's 9 Linear(H,H): the last layer of each branch is folded into lin's Linear
+                    # offline, model._fused_pack), skips, per 128-row tile of the class-major order, the pooled branches whose
+                    # input is all zero, and evaluates every f32 product as THREE f16 MFMAs (hi/lo splits of both operands).
+                    # The grouped Linear launches (narrower heads) issue six bf16 MFMAs per product.  frac is the fraction of
+                    # the pipe the kernel runs on: issued f16 / bf16 MFMA FLOPs over the dense 16-bit MFMA peak.
+                    launches_per_step = stages["linear"]["launches"] / sampled
+                    Bm = mines[0].shape[1]
+                    t = stages["linear"]["ms"] * 1e-3
+                    fused = bool(ops.fused_heads and H >= ops.fused_heads_min_width and getattr(pred, "_fused_plan", lambda H: None)(H) is not None)
+                    ref_fl = timer.flops.get("linear", 0.0) / stages["linear"]["launches"]
+                    skip = getattr(pred, "_skip_state", None)
+                    skipping = bool(ops.skip_zero_rows and skip is not None and skip["off"] == 0 and Bm >= ops.skip_zero_min_batch)
+                    n_cn1, n_any = ab["n_cn1"], ab["n_any"]
+                    n_b = n_any if pred._xcn2_on_union else ab["n_cn2"]
+                    if fused:
+                        rows_a, rows_b = (n_cn1, n_b) if skipping else (Bm, Bm)
+                        f32_fl = 2.0 * H * H * (3 * rows_a + 3 * rows_b + 2 * Bm) / launches_per_step
+                        kern, terms, pipe = "heads_fused_kernel", 3, "f16"
+                    else:
+                        f32_fl = ref_fl
+                        if skipping and pred._heads_plan(H) is not None:
+                            sx_layers = len(pred._heads_plan(H)[2])
+                            lin_layers = sum(1 for m in pred.lin if isinstance(m, torch.nn.Linear) and m.out_features == H)
+                            f32_fl = (2.0 * H * H * (2 * n_cn1 + 2 * n_b + sx_layers * Bm + lin_layers * Bm)
+                                      + 2.0 * (2 * H) * H * n_any) / launches_per_step
+                        kern, terms, pipe = "linear_bf16x6_kernel", 6, "bf16"
+                    issued = terms * f32_fl
+                    roofs["heads"] = dict(bound="mfma", kernel=kern, achieved=issued / t / 1e12, peak=BF16_MFMA_PEAK / 1e12,
+                                          unit="TFLOP/s", frac=issued / t / BF16_MFMA_PEAK, traffic=pmc(kern),
+                                          algorithmic_flops_per_launch=issued, avg_launch_ms=stages["linear"]["ms"],
+                                          launches_per_step=launches_per_step, mfma_per_f32_product=terms, mfma_dtype=pipe,
+                                          f32_equivalent_tflops=f32_fl / t / 1e12, f32_equivalent_flops_per_launch=f32_fl,
+                                          f32_equivalent_frac_of_f32_mfma_peak=f32_fl / t / F32_MFMA_PEAK,
+                                          reference_head_f32_flops_per_step=2.0 * H * H * 9 * Bm + 2.0 * H * Bm,
+                                          skipped_zero_rows=skipping,
+                                          note=f"achieved / peak / frac = the {pipe} MFMA FLOPs the launch issues ({terms} MFMAs per f32 "
+                                               "product; 2*H*H per row and panel, rows of skipped all-zero branches excluded, the 9 "
+                                               "Linear(H,H) of the reference folded to 8 panels) against the dense 16-bit MFMA peak; "
+                                               "f32_equivalent_* = the same work counted once per f32 product.  MFMA-busy counters: "
+                                               "profiles/r03_heads_pmc.json.  Head: " + head_layout(pred))
+                for k, rk in (("cn_flags", "cn_flags"), ("cn_gather", "cn_gather"), ("linear", "heads")):
+                    if rk in roofs and k in stages1:
+                        t1 = stages1[k]["ms"]
+                        roofs[rk]["avg_launch_ms_one_stream"] = t1
+                        roofs[rk]["frac_one_stream"] = roofs[rk]["frac"] * roofs[rk]["avg_launch_ms"] / t1
+                        stages[k]["ms_one_stream"] = t1
+                        roofs[rk]["note"] += ("  avg_launch_ms / achieved / frac are measured inside the timed region, where the intersection pass "
+                                              "of the next batch runs on a second stream beside this kernel; *_one_stream = the same launch "
+                                              "with the streams serialised.")
+                roof = roofs["heads"] if dom == "linear" else roofs[dom]
+            cpu, err, ref_scale = None, None, None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu, b, ref = cpu_baseline(wl, args, mines[0])
+                ops.validate_indices = False
+                sub = mines[0][:, :b].contiguous()
+                with torch.no_grad():
+                    c1, c2 = cn_handles(wl, sub)
+                    got = pred(h, adj, c1, c2, sub, wl["args"]).cpu()
+                err = (got - ref).abs().max().item()
+                ref_scale = ref.abs().max().item()
+            line["config"].update({
+                "mean_deg_src": ab["mean_di"], "mean_deg_dst": ab["mean_dj"],
+                "mean_second_operand_len": ab["mean_second"],
+                "mean_cn1": ab["mean_c1"], "mean_cn2": ab["mean_c2"],
+                "distinct_h_rows_per_batch": ab["distinct_h_rows"],
+                "frac_rows_with_cn1": ab["frac_rows_cn1"], "frac_rows_with_any_cn": ab["frac_rows_any"]})
+            line.update({
+                "value_runs": [B_total / r for r in runs], "value_min": B_total / max(runs),
+                "value_median": B_total / sorted(runs)[len(runs) // 2], "ms_per_step_runs": [r * 1e3 for r in runs],
+                "stage_timer": {"sampled_steps": sampled, "rule": "HIP events on the launch stream, same-stream pairs only, "
+                                ">= 8 sampled steps, never the priming step"},
+                "roofline": roof, "roofline_hbm_kernel": roof_hbm, "rooflines": roofs, "cpu_baseline": cpu,
+                "value_trained_innerprod": None if dt_tr is None else B_total / dt_tr,
+                "ms_per_step_trained_innerprod": None if dt_tr is None else dt_tr * 1e3,
+                "value_one_stream": None if dt1 is None else B_total / dt1,
+                "ms_per_step_one_stream": None if dt1 is None else dt1 * 1e3,
+                "value_validate_per_batch": None if dt_val is None else B_total / dt_val,
+                "ms_per_step_validate_per_batch": None if dt_val is None else dt_val * 1e3,
+                "stages": stages,
+                "once_per_graph": {"encoder_ms": wl["enc_s"] * 1e3, "adj2_build_ms": wl["a2_s"] * 1e3,
+                                   "graph_build_s": wl["graph_s"]},
+                "algorithmic_bytes_per_step": ab["flags_compulsory"] + ab["gather_compulsory"],
+                "survey_formula_bytes_per_step": ab["flags_formula"] + ab["gather_formula"],
+                "parity_on_cpu_sample_max_abs_err": err,
+                "parity_on_cpu_sample_max_abs_ref": ref_scale,         # the scores' scale: raw walk-count pools (citation2) reach 1e4
+                "parity_on_cpu_sample_rel_err": None if not ref_scale else err / ref_scale,
+            })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,5 +1,5 @@
 """The bench line contract, checked on the committed round profile (profiles/r*_bench_collab.json is the
-stdout of `python bench.py` on an MI355X): every key the driver and the judge read, with sane values."""
+stdout of `python bench.py --full` on an MI355X): every key its readers use, with sane values."""
 import glob
 import json
 import os
@@ -42,3 +42,33 @@ def test_profiles_hold_the_rocprof_summaries():
     stats = open(sorted(glob.glob(os.path.join(ROOT, "profiles", "*_bench_kernel_stats.csv")))[-1]).read()
     for kernel in ("heads_fused_kernel", "cn_gather_kernel", "cn_flags_kernel"):
         assert kernel in stats
+
+
+def test_dump_outputs_writes_float32_scores_and_a_fixed_sample_above_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the scores as float32; above the byte cap, a seeded sample of rows (the same one every run) with
+    their row ids beside them, both files together within the cap."""
+    import sys
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    s = torch.randn(1000, 1, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), s)
+    got = np.load(tmp_path / "whole" / "scores.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, s.float().numpy())
+    assert not (tmp_path / "whole" / "scores_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1200)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), s)
+    rows, got = np.load(tmp_path / "a" / "scores_rows.npy"), np.load(tmp_path / "a" / "scores.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and rows.nbytes + got.nbytes <= 1200 and len(rows) == 100
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, s.float().numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "scores_rows.npy"))
+
+
+def test_full_and_dump_outputs_are_options():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
