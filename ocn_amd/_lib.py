@@ -126,32 +126,32 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
-def build_flags(extra_flags=()):
+def build_flags():
     """The compile flags of the product build (tests/test_host.py asserts that no experiment macro is among them)."""
     return ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17",
             # the reference's CPU kernels round the product and the sum separately; HIP's __fmul_rn /
             # __fadd_rn are plain * and + and would be contracted into FMAs under the default mode
             "-ffp-contract=off",
-            # every unit's compile command is recorded in the library (.GCC.command.line): a build with an experiment macro
-            # (-DOCN_X_*: timing ablations, several of which compute wrong results) can be told from the product build
+            # every unit's compile command is recorded in the library (.GCC.command.line): the flags a library was
+            # built with can be read back from it
             "-frecord-command-line",
-            f"-I{INCLUDE}", f"-I{CSRC}", *extra_flags]
+            f"-I{INCLUDE}", f"-I{CSRC}"]
 
 
-def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None, jobs: int = None) -> str:
+def build(force: bool = False, verbose: bool = False, jobs: int = None) -> str:
     """Compile csrc/*.hip -> ocn_amd/libocn_hip.so for gfx950 (hipcc cross-compiles without a GPU): one object per
     translation unit under csrc/_build/<flag hash>/ (rebuilt only when the unit, a header or the flags changed), compiled in
     parallel, then one link."""
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
-    out = out or LIB_PATH
+    out = LIB_PATH
     hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "ocn_hip.h")]
     deps = sources() + hdrs + [os.path.abspath(__file__)]
-    if not force and not extra_flags and os.path.exists(out) and \
+    if not force and os.path.exists(out) and \
             os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = build_flags(extra_flags)
+    flags = build_flags()
     tag = hashlib.sha1(" ".join(flags).encode()).hexdigest()[:10]
     bdir = os.path.join(CSRC, "_build", tag)
     os.makedirs(bdir, exist_ok=True)

@@ -42,24 +42,17 @@ __device__ __forceinline__ bool sampled_has(const int32_t* samp, const int32_t* 
 #define T1_CAP 1024
 #define REC_LEN_SHIFT 40                     /* slot record word 2: row start (nnz < 2^40) | row length << 40 */
 #define REC_FULL2_BIT 61     /* record word 3: every position of the source row is a cn2 entry (cnt2 == row length) */
-#ifndef OCN_X_G
-#define OCN_X_G 64     /* lanes per candidate edge; tools/kbench.py overrides it for timing experiments */
-#endif
+constexpr int FLAGS_G = 64;    /* lanes per candidate edge of the intersection pass (cn_flags_kernel's G) */
 // a group's cost: the largest entry count among its four candidates (a wave walks one candidate), in buckets of 32 —
-// measured at the collab shape (tools/_ab notes in DESIGN.md): sum / max and 4 .. 256-entry buckets all land within
+// measured at the collab shape (pooling): sum / max and 4 .. 256-entry buckets all land within
 // 0.184 - 0.200 ms against 0.206 unscheduled; coarse buckets keep more of the source order's L2 locality
 #define SCHED_COST(t, c) ((t) > (c) ? (t) : (c))
-#ifndef OCN_X_SCHED_SHIFT
-#define OCN_X_SCHED_SHIFT 5
-#endif
-#ifndef OCN_X_POOL_LPE
-#define OCN_X_POOL_LPE 64    /* lanes per candidate of the H = 256 pooling (64: one candidate per wave) */
-#endif
-#define POOL_FOLD (OCN_WAVE / OCN_X_POOL_LPE)      /* 4-slot cost groups of the intersection pass per pooling workgroup */
-#define SCHED_GROUP (OCN_BLOCK / OCN_X_G)    /* slots per scheduling group: a workgroup of the intersection pass == one of the H = 256 pooling */
+constexpr int SCHED_SHIFT = 5;
+constexpr int POOL_LPE = 64;    /* lanes per candidate of the H = 256 pooling (64: one candidate per wave) */
+#define SCHED_GROUP (OCN_BLOCK / FLAGS_G)    /* slots per scheduling group: a workgroup of the intersection pass == one of the H = 256 pooling */
 
 // G lanes cooperate on one candidate edge (64/G edges per wave).  Measured on the collab-shaped
-// batch (tools/kbench.py): G = 64 / 32 / 16 / 8 -> 208 / 242 / 327 / 494 us.  The kernel is bound by
+// batch: G = 64 / 32 / 16 / 8 -> 208 / 242 / 327 / 494 us.  The kernel is bound by
 // the number of distinct cache lines its scattered probes touch per wave instruction, not by the
 // latency of the chains: lanes that search the SAME rows share the top-of-tree lines, lanes of
 // different edges do not, so one edge per wave wins although most source rows are < 64 long.
@@ -129,37 +122,19 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     int c1 = 0, c2 = 0;
     for (i64 p = gl; p < da; p += G) {
       const int32_t k = colA[a0 + p];
-#ifdef OCN_X_NOT1   /* OCN_X_*: timing experiments of tools/kbench.py, never defined in the product build */
-      const bool f1 = (k & 7) == 0;
-#else
       const bool f1 = bmT1 ? (bool)((bm1_row[k >> 5] >> (k & 31)) & 1u)
                            : (t1_lds ? sorted_has(&s_t1[g][0], db, k) : sorted_has(colT1 + b0, db, k));
-#endif
       bool f2 = false;
-#ifdef OCN_X_NOT2
-      f2 = (k & 1) == 0;
-#else
       if (HAS_T2) {
         if (t2_full) f2 = true;
         else if (bmT2) f2 = (bm_row[k >> 5] >> (k & 31)) & 1u;    // one probe
         else f2 = dc > OCN_WAVE ? sampled_has(&s_t2[g][0], colT2 + c0, dc, k) : sorted_has(&s_t2[g][0], dc, k);
       }
-#endif
-#ifndef OCN_X_NOFLAGS
       if (fits) flags[base + p] = (uint8_t)((f1 ? OCN_F_CN1 : 0u) | (f2 ? OCN_F_CN2 : 0u));
-#endif
-#ifndef OCN_X_NOATOMIC
       if (f1 | f2) {
         const u64 inc = (u64)f1 | ((u64)f2 << HF_BITS) | (1ull << (2 * HF_BITS));
-#ifdef OCN_X_ATOMIC_SPREAD   /* timing experiment: the same number of atomics on uniformly spread addresses (no hot column) */
-        if (LH) atomicAdd(s_hist + k, inc); else atomicAdd(hist + 2 * (i64)((((u64)k * 2654435761ull) ^ ((u64)(base + p) * 40503ull)) % (u64)n_cols), inc);
-#elif defined(OCN_X_ATOMIC_WG)  /* timing experiment: the atomics resolved in the issuing XCD's L2 (results wrong across XCDs) */
-        if (LH) atomicAdd(s_hist + k, inc); else __hip_atomic_fetch_add(hist + 2 * (i64)k, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
         if (LH) atomicAdd(s_hist + k, inc); else atomicAdd(hist + 2 * (i64)k, inc);
-#endif
       }
-#endif
       c1 += f1;
       c2 += f2;
     }
@@ -212,24 +187,15 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
 // true hits (~1 % of the swept elements) plus the false positives — are queued in LDS and resolved in
 // bulk, one per thread, by binary search in the sorted CSR row; done inline that search would run with
 // a handful of live lanes on nearly every wave iteration.
-#ifndef OCN_X_WALK_BM_BITS
-#define OCN_X_WALK_BM_BITS 17
-#endif
-#define WALK_BM_BITS OCN_X_WALK_BM_BITS
+constexpr int WALK_BM_BITS = 17;
 #define WALK_BM_WORDS (1 << (WALK_BM_BITS - 5))
-#ifndef OCN_X_WALK_Q
-#define OCN_X_WALK_Q 1024
-#endif
-#define WALK_Q OCN_X_WALK_Q     /* queue entries; flushed when half full, overflow resolves in place */
+constexpr int WALK_Q = 1024;      /* queue entries; flushed when half full, overflow resolves in place */
 // The probed row itself is kept in LDS beside its bitmap (it passes through the workgroup's hands anyway when the bitmap
 // is built): resolving a queued element, and the cn1 test of the finalise step, are then binary searches in LDS —
 // ~10 dependent LDS reads instead of ~10 dependent trips to L2, which were two thirds of an item's chain of dependent
 // loads.  Rows longer than WALK_SET (hubs) keep the search in memory.  The room comes from halving the bitmap
 // (128 Kbit: twice the false positives, each now one cheap LDS search).
-#ifndef OCN_X_WALK_SET
-#define OCN_X_WALK_SET 4096
-#endif
-#define WALK_SET OCN_X_WALK_SET
+constexpr int WALK_SET = 4096;
 
 __device__ __forceinline__ unsigned walk_bit(int32_t v) { return ((unsigned)v * 2654435761u) >> (32 - WALK_BM_BITS); }
 __device__ __forceinline__ void walk_bm_add(unsigned* bm, int32_t v) {
@@ -253,7 +219,6 @@ __device__ __forceinline__ i64 sorted_find(const int32_t* __restrict__ a, i64 n,
 
 // position of key in the probed row (LDS copy when it fits, else the CSR row in memory), or -1
 __device__ __forceinline__ i64 walk_set_find(const int32_t* s_set, const int32_t* __restrict__ set_g, i64 ds, int32_t key) {
-#if WALK_SET > 0
   if (ds <= WALK_SET) {
     int lo = 0, hi = (int)ds;
     while (lo < hi) {
@@ -262,7 +227,6 @@ __device__ __forceinline__ i64 walk_set_find(const int32_t* s_set, const int32_t
     }
     return (lo < (int)ds && s_set[lo] == key) ? lo : -1;
   }
-#endif
   return sorted_find(set_g, ds, key);
 }
 
@@ -282,10 +246,7 @@ __device__ __forceinline__ i64 walk_item_slot(const i64* __restrict__ item_off, 
   return lo;
 }
 
-#ifndef OCN_X_WALK_THREADS
-#define OCN_X_WALK_THREADS 512
-#endif
-#define WALK_THREADS OCN_X_WALK_THREADS   /* threads per walk work item */
+constexpr int WALK_THREADS = 512;   /* threads per walk work item */
 #define WALK_WAVES (WALK_THREADS / OCN_WAVE)
 #define WALK_ROWS (WALK_WAVES * WALK_CHUNK)   /* rows a forward item can take: one 64-row chunk per wave */
 
@@ -326,10 +287,7 @@ template <typename Hit>
 __device__ __forceinline__ void walk_sweep(const int32_t* __restrict__ colA, const unsigned* s_bm, const int* s_pre,
                                            const i64* s_r0, int total, const int32_t* s_set, const int32_t* __restrict__ set_g, i64 ds,
                                            int32_t* s_qk, uint16_t* s_qr, int* s_nq, Hit hit) {
-#ifndef OCN_X_WALK_WU
-#define OCN_X_WALK_WU 8
-#endif
-  constexpr int WU = OCN_X_WALK_WU;          // independent element loads in flight per thread
+  constexpr int WU = 8;                      // independent element loads in flight per thread
   int lo = 0;                                // a thread's elements come in increasing x: the row pointer only moves forward
   for (int x0 = 0; x0 < total; x0 += WU * WALK_THREADS) {              // workgroup-uniform trip count
     int row[WU];
@@ -373,7 +331,7 @@ __device__ __forceinline__ void walk_sweep(const int32_t* __restrict__ colA, con
 
 #define WALK_SHARED                                     \
   __shared__ unsigned s_bm[WALK_BM_WORDS];              \
-  __shared__ int32_t s_set[WALK_SET > 0 ? WALK_SET : 1]; \
+  __shared__ int32_t s_set[WALK_SET];                   \
   __shared__ int s_pre[WALK_ROWS + 1];                  \
   __shared__ i64 s_r0[WALK_ROWS];                       \
   __shared__ int32_t s_r[WALK_ROWS];                    \
@@ -384,8 +342,7 @@ __device__ __forceinline__ void walk_sweep(const int32_t* __restrict__ colA, con
   __shared__ i64 s_slot, s_item
 
 // draw the next work item (ticket counter) and find its batch slot, while the other waves clear the bitmap
-#define WALK_NEXT_ITEM(TICKET, ITEM_OFF) WALK_NEXT_ITEM_X(TICKET, ITEM_OFF, (void)0)
-#define WALK_NEXT_ITEM_X(TICKET, ITEM_OFF, ONEXIT)                                                   \
+#define WALK_NEXT_ITEM(TICKET, ITEM_OFF)                                                             \
   if (w == 0) {                                                                                      \
     i64 t = 0;                                                                                       \
     if (lane == 0) t = atomicAdd((TICKET), 1);                                                       \
@@ -397,7 +354,7 @@ __device__ __forceinline__ void walk_sweep(const int32_t* __restrict__ colA, con
   }                                                                                                  \
   __syncthreads();                                                                                   \
   const i64 item = s_item;                                                                           \
-  if (item >= n_items) { ONEXIT; break; }                                                            \
+  if (item >= n_items) break;                                                                        \
   const i64 slot = s_slot;                                                                           \
   const i64 e = order ? order[slot] : slot;                                                          \
   const i64 i = src[e], j = dst[e];                                                                  \
@@ -429,9 +386,6 @@ __global__ __launch_bounds__(WALK_THREADS) void cn_walk_rev_kernel(
       if (q < WALK_SET) s_set[q] = v;
     }
     int total = walk_item_rows(rowptrA, colA, b0 + p_lo, nm, s_pre, s_r0, s_r, s_ctot);
-#ifdef OCN_X_WALK_NOSWEEP   /* timing experiment: per-item overhead only */
-    total = 0;
-#endif
     if (base + da > cap) total = 0;
     int32_t* wrow = wc + base;
     walk_sweep(colA, s_bm, s_pre, s_r0, total, s_set, ni_g, da, s_qk, s_qr, &s_nq,
@@ -440,13 +394,6 @@ __global__ __launch_bounds__(WALK_THREADS) void cn_walk_rev_kernel(
   }
 }
 
-#ifdef OCN_X_WALK_STAMPS
-__device__ unsigned long long g_walk_stamps[256 * 8];
-extern "C" int ocn_debug_walk_stamps(unsigned long long* out, int reset) {
-  if (reset) { static unsigned long long z[256 * 8]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_walk_stamps), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_stamps), 256 * 8 * sizeof(unsigned long long));
-}
-#endif
 // Forward sweep.  Work item = (batch row, group of <= WALK_WAVES consecutive 64-row chunks of N(i));
 // items are enumerated through the exclusive scan chunk_off[] so that a hub source node is spread
 // over many workgroups instead of serialising one, while a light row is a single item (one round of
@@ -470,27 +417,15 @@ __global__ __launch_bounds__(WALK_THREADS) void cn_walk_kernel(
     if (chunk_off[B] < 0) status_raise(status, chunk_off[B], cap);
   }
   const i64 n_items = chunk_off[B];
-#ifdef OCN_X_WALK_STAMPS   /* diagnostic build: where an item's time goes (tools/walkstamps.py) */
-  unsigned long long tph[6] = {0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
-#define WSTAMP(k) do { __builtin_amdgcn_s_waitcnt(0); const unsigned long long tn = __builtin_amdgcn_s_memtime(); tph[k] += tn - tprev; tprev = tn; } while (0)
-#define WSTAMP_OUT() do { if (threadIdx.x == 0 && blockIdx.x < 256) for (int q = 0; q < 6; ++q) g_walk_stamps[blockIdx.x * 8 + q] += tph[q]; } while (0)
-#else
-#define WSTAMP(k) do {} while (0)
-#define WSTAMP_OUT() do {} while (0)
-#endif
   for (;;) {
-    if (w == 0) { WSTAMP(5); }
-    WALK_NEXT_ITEM_X(status + 1, chunk_off, WSTAMP_OUT());
-    WSTAMP(0);
+    WALK_NEXT_ITEM(status + 1, chunk_off);
     const bool rev = walk_reverse(nds, i, j, da, db);      // workgroup-uniform
     const int32_t* nj_g = colA + b0;
-#ifndef OCN_X_WALK_NOBM
     for (i64 q = threadIdx.x; q < db; q += WALK_THREADS) {
       const int32_t v = nj_g[q];
       walk_bm_add(s_bm, v);
       if (q < WALK_SET) s_set[q] = v;
     }
-#endif
     const i64 n_chunks = (da + WALK_CHUNK - 1) / WALK_CHUNK;
     const i64 cg = walk_group(nds, i, da);
     const i64 p_lo = (item - chunk_off[slot]) * cg * WALK_CHUNK;
@@ -499,22 +434,12 @@ __global__ __launch_bounds__(WALK_THREADS) void cn_walk_kernel(
     const int nk = (int)(p_hi - p_lo);
     const bool in_cap = base + da <= cap;
     s_walks[threadIdx.x] = 0;
-#ifdef OCN_X_WALK_NOROWS
-    int total = 0; __syncthreads();
-#else
     int total = walk_item_rows(rowptrA, colA, a0 + p_lo, nk, s_pre, s_r0, s_r, s_ctot);
-#endif
-#ifdef OCN_X_WALK_NOSWEEP
-    total = 0;
-#endif
     if (rev) total = 0;
-    WSTAMP(1);
     int* walks_of = s_walks;
     walk_sweep(colA, s_bm, s_pre, s_r0, total, s_set, nj_g, db, s_qk, s_qr, &s_nq,
                [walks_of](int32_t, int row, i64) { atomicAdd(walks_of + row, 1); });
     __syncthreads();
-    WSTAMP(2);
-#ifndef OCN_X_WALK_NOFIN
     {                                          // finalise: one row per thread
       const int t = threadIdx.x;
       bool f1 = false, f2 = false;
@@ -538,15 +463,7 @@ __global__ __launch_bounds__(WALK_THREADS) void cn_walk_kernel(
         if (c2) atomicAdd(cnt2 + e, c2);
       }
     }
-#endif
-    WSTAMP(3);
     __syncthreads();
-    WSTAMP(4);
-    if (threadIdx.x == 0) {
-#ifdef OCN_X_WALK_STAMPS
-      if (blockIdx.x < 256) g_walk_stamps[blockIdx.x * 8 + 6] += 1;
-#endif
-    }
   }
 }
 
@@ -716,12 +633,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn7_column_weights(u64* __restrict_
 // Pool the flagged neighbours at positions [p_begin, p_end) of the source row into acc1 / acc2, in
 // ascending position (= column) order.  LPE lanes cooperate; each lane owns NV float4 of the
 // H = LPE*NV*4 features; four embedding rows are in flight per group.
-#ifndef OCN_X_GATHER_UNR
-#define OCN_X_GATHER_UNR 4
-#endif
+constexpr int GATHER_UNR = 4;
 // (eight for the one-wave-per-candidate layout of H >= 256 — one candidate's gathers are all a wave has in flight:
 // 0.214 -> 0.206 ms at the collab shape; four where several candidates share a wave)
-template <int LPE, int NV, int UNR = (LPE >= 64 ? 2 * OCN_X_GATHER_UNR : OCN_X_GATHER_UNR)>
+template <int LPE, int NV, int UNR = (LPE >= 64 ? 2 * GATHER_UNR : GATHER_UNR)>
 __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 base, int gl, int gbase,
                                            const int32_t* __restrict__ colA, const uint8_t* __restrict__ flags,
                                            const int32_t* __restrict__ wc, const float4* __restrict__ weights,
@@ -778,18 +693,8 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
           kk[u] = __shfl(k[t], sl, OCN_WAVE);
           wwa[u] = __shfl(wa[t], sl, OCN_WAVE);
           wwb[u] = __shfl(wb[t], sl, OCN_WAVE);
-#ifdef OCN_X_ROWSKIP   /* timing experiment (results wrong): only every OCN_X_ROWSKIP-th entry fetches its row, the others reuse it — what perfect in-register row sharing would leave of the launch */
-          if (bsel[u] >= 0 && (u % OCN_X_ROWSKIP) != 0) {
-#pragma unroll
-            for (int v = 0; v < NV; ++v) x[u][v] = x[u - (u % OCN_X_ROWSKIP)][v];
-          } else
-#endif
           if (bsel[u] >= 0) {
-#ifdef OCN_X_ROWMASK   /* timing experiment (results wrong): every row fetch folded onto a table of OCN_X_ROWMASK + 1 rows — what the kernel costs when its rows are cache-resident */
-            const float4* row = h4 + (i64)(kk[u] & OCN_X_ROWMASK) * rowq + gl;
-#else
             const float4* row = h4 + (i64)kk[u] * rowq + gl;
-#endif
 #pragma unroll
             for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
           }
@@ -841,23 +746,9 @@ __device__ __forceinline__ void pool_store(i64 e, i64 i, i64 j, int gl, const fl
 // groups take contiguous segments of the row and the partial sums are added in segment order.
 // Rows up to LONG_ROW keep the strictly sequential ascending-column sum of the reference's spmm.
 #define LONG_ROW 1024
-#ifndef GATHER_SLICE_MIN_BATCH
-#define GATHER_SLICE_MIN_BATCH 16384     /* candidates from which the pooling of H >= 256 runs one feature slice per XCD */
-#endif
 
-#ifdef OCN_X_POOL_STAMPS   /* diagnostic build (tools/poolstamps.py): per processing slot {start, end, row length, xcc | hw id} of its pooling wave */
-__device__ unsigned long long g_pool_stamps[4 << 17];
-extern "C" int ocn_debug_pool_stamps(unsigned long long* out, long long n_slots) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pool_stamps), (size_t)n_slots * 4 * sizeof(unsigned long long));
-}
-#endif
 // LPE lanes cooperate on one edge (64/LPE edges per wave).
-// SLICED: the H features are cut into 8 slices of LPE*NV*4 and workgroup b pools slice b % 8 of its candidates.
-// Workgroups are dealt round-robin over the 8 XCDs, so XCD x only ever reads feature slice x of the embedding
-// table: every row slice has ONE home L2 (a row shared by candidates on different XCDs is no longer fetched up to
-// eight times) and that L2 holds 8x as many rows.  Every feature is still summed on its own in ascending column
-// order, so the result does not change by a bit.
-template <int LPE, int NV, bool SLICED = false>
+template <int LPE, int NV>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
     const i64* __restrict__ src, const i64* __restrict__ dst, const i64* __restrict__ order, i64 B,
@@ -876,26 +767,17 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
   // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  The batch rows are
   // visited in source-node order, so give every XCD one contiguous eighth of that order: rows
   // with neighbouring sources then share an L2 instead of being spread over all eight.
+  // (One feature slice per XCD instead — every row slice with one home L2 — was bit-identical but 0.76 ms against 0.22 ms
+  // at the collab shape: eight candidates share a wave and run in lockstep to the longest of them)
   i64 bid = blockIdx.x;
-  int slice = 0;
-  if (SLICED) {
-    slice = (int)(bid & 7);
-    bid >>= 3;
-  } else {
-#ifndef OCN_X_NOXCD
-    if ((gridDim.x & 7) == 0) {
-      bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-      // ... and inside its eighth an XCD takes the groups in the order of the schedule: the longest jobs first (groups of
-      // one source have one cost and stay neighbours: the L2 locality of the source order is kept)
-      if (perm) bid = perm[bid];
-    }
-#endif
+  if ((gridDim.x & 7) == 0) {
+    bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    // ... and inside its eighth an XCD takes the groups in the order of the schedule: the longest jobs first (groups of
+    // one source have one cost and stay neighbours: the L2 locality of the source order is kept)
+    if (perm) bid = perm[bid];
   }
   const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
   if (slot >= B) return;                    // whole group leaves together
-#ifdef OCN_X_POOL_STAMPS
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-#endif
   // One dependent load instead of three (order -> src / dst / off / counts -> rowptr) in front of the first gather:
   // the intersection pass left everything about this slot in a 32-byte record.
   i64 e, i, j, a0, da, base;
@@ -918,32 +800,19 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
     full2 = rowsum && cnt2 && da > 0 && (i64)cnt2[e] == da;
   }
   if (da > LONG_ROW && !full2) return;      // cn_gather_long_kernel's (a hub row whose cn2 is the whole row only has its cn1 entries left)
-  const float4* h4 = reinterpret_cast<const float4*>(h) + slice * (LPE * NV);
+  const float4* h4 = reinterpret_cast<const float4*>(h);
   const i64 rowq = H >> 2;                  // float4 per row
-  if (SLICED) { xcn1 += slice * (LPE * NV * 4); xcn2 += slice * (LPE * NV * 4); xij += slice * (LPE * NV * 4); }
   float4 acc1[NV], acc2[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) acc1[v] = acc2[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (has1 | (has2 & !full2)) pool_range<LPE, NV>(0, da, a0, base, gl, gbase, colA, flags, wc, weights, h4, rowq, acc1, acc2, full2);
   if (full2) {
-    const float4* rs = reinterpret_cast<const float4*>(rowsum) + slice * (LPE * NV) + i * rowq + gl;
+    const float4* rs = reinterpret_cast<const float4*>(rowsum) + i * rowq + gl;
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc2[v] = rs[v * LPE];
   }
   pool_store<LPE, NV>(out_row ? out_row[e] : e, i, j, gl, h4, rowq, acc1, acc2, xcn1, xcn2, xij,
                       !out_row || has1, !out_row || has1 || has2);
-#ifdef OCN_X_POOL_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);
-  if (gl == 0 && slot < (1 << 17)) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_pool_stamps[4 * slot + 0] = t_start;
-    g_pool_stamps[4 * slot + 1] = __builtin_amdgcn_s_memtime();
-    g_pool_stamps[4 * slot + 2] = (unsigned long long)da;
-    g_pool_stamps[4 * slot + 3] = ((unsigned long long)(xcc & 0xf) << 32) | hwid;
-  }
-#endif
 }
 
 // The sequential sum of ranks [0, nr) of a compacted round: acc += w[r] * x[r], one multiply and one add per entry and
@@ -1002,23 +871,11 @@ __device__ __forceinline__ void chain_rows(const float2* __restrict__ w, const f
 // LONG: the same kernel over the batch rows whose source row is LONGER than LONG_ROW only (large batches of narrow
 // embeddings on a dense graph — ogbl-ddi: a third of the candidates have such a source; a lane group of the packed
 // kernel would walk 2 000 positions four gathers at a time).
-#ifdef OCN_X_WAVE_CHECK
-__device__ unsigned g_wave_chk_n;
-__device__ float g_wave_chk[4096 * 6];
-extern "C" int ocn_debug_wave_check(float* out, unsigned* n) {
-  const int e = (int)hipMemcpyFromSymbol(n, HIP_SYMBOL(g_wave_chk_n), sizeof(unsigned));
-  return e ? e : (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_chk), sizeof(float) * 4096 * 6);
-}
-#endif
-// (waves per workgroup: the slabs of four waves at H = 64 are 70 KiB of static LDS — above the 64 KiB a workgroup gets without an
-// opt-in, and measured to go wrong exactly then: with workgroups of ANOTHER kernel on the same CU (a scoring loop's heads beside
-// this pooling on a second stream) about one batch in a hundred came back with 64 bytes of one xcn1 row wrong; two waves there)
+// (waves per workgroup: the slabs of four waves at H = 64 would be 70 KiB of static LDS, above the 64 KiB a workgroup gets without
+// an opt-in; two waves there.  The wrong H = 64 sums beside another stream's kernels were not the slab — halving it left their rate
+// unchanged — but the packed multiply-add form that axpy_pair_lds replaces: DESIGN.md section 6)
 template <int LPE, int NV, bool LONG>
-#ifdef OCN_X_WAVE_WPB   /* diagnostic build only (tools/dbg_two_stream.py) */
-constexpr int gather_wave_wpb() { return LONG ? 1 : OCN_X_WAVE_WPB; }
-#else
 constexpr int gather_wave_wpb() { return LONG ? 1 : ((size_t)OCN_WPB * OCN_WAVE * (LPE * NV * 16 + 24) > 65536 ? 2 : OCN_WPB); }
-#endif
 
 template <int LPE, int NV, bool LONG = false, int WPB = gather_wave_wpb<LPE, NV, LONG>()>
 __global__ __launch_bounds__(WPB * OCN_WAVE) void cn_gather_wave_kernel(
@@ -1118,30 +975,6 @@ __global__ __launch_bounds__(WPB * OCN_WAVE) void cn_gather_wave_kernel(
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     n = n_next;
   }
-#ifdef OCN_X_WAVE_CHECK   /* diagnostic build only (tools/dbg_two_stream.py): the same sums once more, straight from memory */
-  if (!LONG && lane < HF) {
-    float c1 = 0.f, c2 = 0.f;
-    for (i64 p = 0; p < da; ++p) {
-      const unsigned f = flags[base + p] & fmask;
-      if (!f) continue;
-      const int32_t k = colA[a0 + p];
-      float wa = 0.f, wb = 0.f;
-      entry_weights(f, weights[k], wc ? (float)wc[base + p] : 1.f, wa, wb);
-      if (wa == 0.f && wb == 0.f) continue;
-      const float xv = h[(i64)k * H + lane];
-      c1 = __fadd_rn(c1, __fmul_rn(wa, xv));
-      c2 = __fadd_rn(c2, __fmul_rn(wb, xv));
-    }
-    const bool bad1 = __float_as_uint(c1) != __float_as_uint(acc1[0]), bad2 = !full2 && __float_as_uint(c2) != __float_as_uint(acc2[0]);
-    if (bad1 || bad2) {
-      const unsigned q = atomicAdd(&g_wave_chk_n, 1u);
-      if (q < 4096) {
-        g_wave_chk[q * 6 + 0] = (float)e; g_wave_chk[q * 6 + 1] = (float)lane; g_wave_chk[q * 6 + 2] = acc1[0];
-        g_wave_chk[q * 6 + 3] = c1; g_wave_chk[q * 6 + 4] = acc2[0]; g_wave_chk[q * 6 + 5] = c2;
-      }
-    }
-  }
-#endif
   if (lane < HF) {
     const i64 o = (out_row ? out_row[e] : e) * H + lane;
     xcn1[o] = acc1[0];
@@ -1192,20 +1025,8 @@ __device__ __forceinline__ void long_store(const f32x4 (&x)[RPG][NV], float4* __
 // entry and accumulator, not a float4's worth of them on a quarter of the lanes.
 // LONG_THREADS: 1024 for small batches (few hub rows, each as parallel as a workgroup gets), 256 for large ones (one
 // workgroup is launched per batch row and all but the hub rows' leave at once).
-#ifndef LONG_SMALL_THREADS
-#define LONG_SMALL_THREADS 1024             /* hub-row workgroup of a small batch (B <= 4096); 512 (two per CU) measured 5 % slower */
-#endif
+constexpr int LONG_SMALL_THREADS = 1024;   /* hub-row workgroup of a small batch (B <= 4096); 512 (two per CU) measured 5 % slower */
 #define LONG_SLAB_BYTES(threads) ((threads) >= 512 ? 32768 : 16384)   /* per half; dynamic LDS = two halves */
-#ifdef OCN_X_LONG_STAMPS   /* diagnostic build: where a hub row's time goes (wave 0 of every hub-row workgroup; tools/longstamps.py) */
-__device__ unsigned long long g_long_stamps[8];
-extern "C" int ocn_debug_long_stamps(unsigned long long* out, int reset) {
-  if (reset) { static unsigned long long z[8]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_long_stamps), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_long_stamps), sizeof(unsigned long long) * 8);
-}
-#define LSTAMP(k) do { if (threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); const unsigned long long tn = __builtin_amdgcn_s_memtime(); lt[k] += tn - lprev; lprev = tn; } } while (0)
-#else
-#define LSTAMP(k) do {} while (0)
-#endif
 template <int LPE, int NV, int LONG_THREADS>
 __global__ __launch_bounds__(LONG_THREADS) void cn_gather_long_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
@@ -1241,18 +1062,13 @@ __global__ __launch_bounds__(LONG_THREADS) void cn_gather_long_kernel(
   float acc1[FPL], acc2[FPL];
 #pragma unroll
   for (int q = 0; q < FPL; ++q) acc1[q] = acc2[q] = 0.f;
-#ifdef OCN_X_LONG_STAMPS
-  unsigned long long lt[6] = {0, 0, 0, 0, 0, 0}, lprev = __builtin_amdgcn_s_memtime();
-#endif
   for (i64 p0 = 0; p0 < da; p0 += LONG_THREADS) {
     const i64 p = p0 + threadIdx.x;
     int32_t k = 0, cv = 1;
     unsigned f = 0;
     if (p < da) { k = colA[a0 + p]; f = flags[base + p]; if (wc) cv = wc[base + p]; }
-    LSTAMP(0);                                                   // ids / flags / cn2 values
     float wa = 0.f, wb = 0.f;
     if (f) entry_weights(f, weights[k], (float)cv, wa, wb);
-    LSTAMP(1);                                                   // column weights
     const bool need = (wa != 0.f) | (wb != 0.f);
     const unsigned long long m = __ballot(need);
     if (lane == 0) s_wcnt[wv] = __popcll(m);
@@ -1271,7 +1087,6 @@ __global__ __launch_bounds__(LONG_THREADS) void cn_gather_long_kernel(
     }
     __syncthreads();
     const int nsr = (n + SLAB - 1) / SLAB;
-    LSTAMP(2);                                                   // compaction (two barriers)
     // Sub-round u lives in register set u & 1 of the fetching waves from its request until it is stored two steps
     // later.  Step t: waves 1.. store sub-round t + 1 and request t + 3 into the set it leaves; wave 0 sums sub-round t
     // from the slab half t & 1; barrier.
@@ -1303,18 +1118,7 @@ __global__ __launch_bounds__(LONG_THREADS) void cn_gather_long_kernel(
         __syncthreads();
       }
     }
-    LSTAMP(3);                                                   // the round's sub-rounds: fetch / store / sum, a barrier each
-#ifdef OCN_X_LONG_STAMPS
-    if (threadIdx.x == 0) { lt[4] += (unsigned long long)n; lt[5] += 1; }
-#endif
   }
-#ifdef OCN_X_LONG_STAMPS
-  if (threadIdx.x == 0) {
-    for (int q = 0; q < 6; ++q) atomicAdd(&g_long_stamps[q], lt[q]);
-    atomicAdd(&g_long_stamps[6], 1ull);
-    atomicMax(&g_long_stamps[7], lt[0] + lt[1] + lt[2] + lt[3]);
-  }
-#endif
   if (wv == 0 && lane < AL) {
     const i64 o = (out_row ? out_row[e] : e) * H + lane * FPL;
 #pragma unroll
@@ -1611,7 +1415,7 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
                           const int32_t* cnt2, const uint64_t* rec, const int32_t* perm, const float* rowsum, hipStream_t st) {
   const i64 epb = (i64)OCN_WPB * (OCN_WAVE / LPE);
   // the schedule's groups are the workgroups of the intersection pass: usable where the pooling's workgroups are the same
-  const bool sched = perm && rec && epb == SCHED_GROUP * POOL_FOLD && ((B + epb - 1) / epb) % 8 == 0;
+  const bool sched = perm && rec && epb == SCHED_GROUP && ((B + epb - 1) / epb) % 8 == 0;
   bool packed = true;
   if constexpr (LPE <= 16) {
     if (B * LPE < 262144) {                  // the packed form would not fill the SIMDs
@@ -1626,25 +1430,9 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
 #define PACKED_ARGS (const i64*)rowptrA, colA, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B, \
                     (const i64*)off, flags, wc, (const float4*)weights, h, (int)H, xcn1, xcn2, xij,           \
                     (const i64*)out_row, cnt1, cnt2, (const u64*)rec
-  if (packed) {
-    bool sliced = false;
-#ifdef OCN_X_SLICE
-    // EXPERIMENT, off in the product (pooling): one feature slice per XCD.  Bit-identical scores, but 8
-    // candidates share a wave and run in lockstep to the longest of them: 0.76 ms against 0.22 ms at the collab shape.
-    if constexpr (LPE * NV >= 64 && (LPE * NV) % 8 == 0) {
-      constexpr int SL = LPE * NV / 8;                           // float4 per slice
-      const i64 spb = (i64)OCN_WPB * (OCN_WAVE / SL);
-      if (B >= GATHER_SLICE_MIN_BATCH) {
-        hipLaunchKernelGGL((cn_gather_kernel<SL, 1, true>), dim3((unsigned)(8 * ((B + spb - 1) / spb))), dim3(OCN_BLOCK),
-                           0, st, PACKED_ARGS, (const int32_t*)nullptr, rowsum);
-        sliced = true;
-      }
-    }
-#endif
-    if (!sliced)
-      hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,
-                         PACKED_ARGS, sched ? perm : (const int32_t*)nullptr, rowsum);
-  }
+  if (packed)
+    hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,
+                       PACKED_ARGS, sched ? perm : (const int32_t*)nullptr, rowsum);
 #undef PACKED_ARGS
 #define LONG_ARGS (const i64*)rowptrA, colA, (const i64*)src, (const i64*)dst, (i64)B, (const i64*)off, flags, wc, \
                   (const float4*)weights, h, (int)H, xcn1, xcn2, xij, (const i64*)out_row, cnt2, rowsum
@@ -1693,7 +1481,7 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* row
   if (!rowptrA || (!rowptrT1 && !bitmapT1) || !src || !dst || !off || !hist || !cnt1 || !status) return OCN_EINVAL;
   if ((bitmapT1 && bm1_stride_words * 32 < n_cols) || (bitmapT2 && bm_stride_words * 32 < n_cols)) return OCN_EINVAL;
   // col pointers may legitimately be NULL for an adjacency with no entries
-  constexpr int GPB = OCN_BLOCK / OCN_X_G;
+  constexpr int GPB = OCN_BLOCK / FLAGS_G;
   hipStream_t st = (hipStream_t)stream;
   const bool lh = n_cols > 0 && n_cols <= LH_MAX_COLS;
   const size_t lds = lh ? (size_t)n_cols * sizeof(u64) : 0;
@@ -1705,10 +1493,10 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* row
     if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OCN_EINVAL;
     bool& raised = raised_dev[devid];
     if (!raised) {
-      hipError_t e1 = hipFuncSetAttribute((const void*)cn_flags_kernel<OCN_X_G, true, true>,
+      hipError_t e1 = hipFuncSetAttribute((const void*)cn_flags_kernel<FLAGS_G, true, true>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize,
                                           LH_MAX_COLS * (int)sizeof(u64));
-      hipError_t e2 = hipFuncSetAttribute((const void*)cn_flags_kernel<OCN_X_G, false, true>,
+      hipError_t e2 = hipFuncSetAttribute((const void*)cn_flags_kernel<FLAGS_G, false, true>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize,
                                           LH_MAX_COLS * (int)sizeof(u64));
       if (e1 != hipSuccess) return (int)e1;
@@ -1723,14 +1511,14 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* row
       (u64*)hist, cnt1, cnt2, status, (u64*)rec, gcost
   if (!rowptrT2 && bitmapT2 && lh) return OCN_EINVAL;      // (small graphs read T2's row lengths beside its bit rows)
   if (rowptrT2 || bitmapT2) {                              // T2 by its bit rows alone: a product whose rows are built on demand
-    if (lh) hipLaunchKernelGGL((cn_flags_kernel<OCN_X_G, true, true>), dim3(grid), dim3(OCN_BLOCK), lds, st,
+    if (lh) hipLaunchKernelGGL((cn_flags_kernel<FLAGS_G, true, true>), dim3(grid), dim3(OCN_BLOCK), lds, st,
                                CN_FLAGS_ARGS(rowptrT2, colT2));
-    else hipLaunchKernelGGL((cn_flags_kernel<OCN_X_G, true, false>), dim3(grid), dim3(OCN_BLOCK), 0, st,
+    else hipLaunchKernelGGL((cn_flags_kernel<FLAGS_G, true, false>), dim3(grid), dim3(OCN_BLOCK), 0, st,
                             CN_FLAGS_ARGS(rowptrT2, colT2));
   } else {
-    if (lh) hipLaunchKernelGGL((cn_flags_kernel<OCN_X_G, false, true>), dim3(grid), dim3(OCN_BLOCK), lds, st,
+    if (lh) hipLaunchKernelGGL((cn_flags_kernel<FLAGS_G, false, true>), dim3(grid), dim3(OCN_BLOCK), lds, st,
                                CN_FLAGS_ARGS(nullptr, (const int32_t*)nullptr));
-    else hipLaunchKernelGGL((cn_flags_kernel<OCN_X_G, false, false>), dim3(grid), dim3(OCN_BLOCK), 0, st,
+    else hipLaunchKernelGGL((cn_flags_kernel<FLAGS_G, false, false>), dim3(grid), dim3(OCN_BLOCK), 0, st,
                             CN_FLAGS_ARGS(nullptr, (const int32_t*)nullptr));
   }
   return launch_status();
@@ -1836,10 +1624,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void gather_schedule_kernel(const int32_
   const i64 ipt = (per + OCN_BLOCK - 1) / OCN_BLOCK;                          // groups per thread, contiguous
   for (int b = 0; b < SCHED_BUCKETS; ++b) tc[b * OCN_BLOCK + t] = 0;
   auto bucket = [&](i64 q) -> int {
-    int c = 0;
-#pragma unroll
-    for (int f = 0; f < POOL_FOLD; ++f) c = SCHED_COST(c, gcost[(lo + q) * POOL_FOLD + f]);
-    c >>= OCN_X_SCHED_SHIFT;
+    const int c = max(gcost[lo + q], 0) >> SCHED_SHIFT;
     return SCHED_BUCKETS - 1 - (c < SCHED_BUCKETS - 1 ? c : SCHED_BUCKETS - 1);
   };
   for (i64 k = 0; k < ipt; ++k) {
@@ -1871,8 +1656,6 @@ int ocn_gather_schedule(const int32_t* gcost, int64_t n_groups, int64_t segment,
   if (n_groups < 0 || (n_groups & 7) || (n_groups >> 3) > 65535 || segment < 0) return OCN_EINVAL;      // eighths; ranks are 16-bit
   if (n_groups == 0) return 0;
   if (!gcost || !perm) return OCN_EINVAL;
-  if (n_groups % (8 * POOL_FOLD)) return OCN_EINVAL;
-  n_groups /= POOL_FOLD;
   i64 per = n_groups >> 3;
   if (segment > 0 && segment < per && per % segment == 0) per = segment;      // (a segment that does not divide the eighth: whole eighths)
   hipLaunchKernelGGL(gather_schedule_kernel, dim3((unsigned)(n_groups / per)), dim3(OCN_BLOCK), 0, (hipStream_t)stream, gcost, per, perm);
@@ -1895,7 +1678,7 @@ int ocn_cn_gather(const int64_t* rowptrA, const int32_t* colA, const int64_t* sr
     case 32:  LAUNCH_GATHER(8, 1); break;
     case 64:  LAUNCH_GATHER(16, 1); break;
     case 128: LAUNCH_GATHER(32, 1); break;
-    case 256: LAUNCH_GATHER(OCN_X_POOL_LPE, (64 / OCN_X_POOL_LPE)); break;
+    case 256: LAUNCH_GATHER(POOL_LPE, (64 / POOL_LPE)); break;
     case 512: LAUNCH_GATHER(64, 2); break;
     default:   /* generic widths: every row by one wave, no long-row split */
       hipLaunchKernelGGL(cn_gather_generic, dim3((unsigned)((B + OCN_WPB - 1) / OCN_WPB)),

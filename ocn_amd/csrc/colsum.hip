@@ -12,9 +12,7 @@
 #include "common.h"
 
 #define CS_WAVE_MAX 64          /* columns with at most this many entries: one wave each */
-#ifndef OCN_X_CS_LDS
-#define OCN_X_CS_LDS 4096       /* longer columns up to this many entries are sorted in LDS, beyond in place in memory */
-#endif
+constexpr int CS_LDS = 4096;    /* longer columns up to this many entries are sorted in LDS, beyond in place in memory */
 #define CS_CHUNK 2048           /* values staged in LDS per accumulation round of a long column */
 #define CS_BINS 256             /* long columns: one bucket pass by position range, then every thread sorts one small bucket */
 #define CS_BIN_MAX 48           /* ... unless a bucket is longer than this (clustered positions): then the bitonic network */
@@ -307,8 +305,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void colsum_long_kernel(
     ColCtx cx, const float* __restrict__ innerprod, const int32_t* __restrict__ scalars,
     float* __restrict__ s2, float* __restrict__ s3, const int32_t* __restrict__ long_list,
     const int32_t* __restrict__ n_long, int32_t* __restrict__ ticket, const float* __restrict__ s2_init, i64 cap) {
-  __shared__ uint32_t s_key[OCN_X_CS_LDS];
-  __shared__ uint32_t s_out[OCN_X_CS_LDS];
+  __shared__ uint32_t s_key[CS_LDS];
+  __shared__ uint32_t s_out[CS_LDS];
   __shared__ int s_cnt[CS_BINS], s_start[CS_BINS];
   __shared__ i64 s_scan[2 * OCN_WPB];
   __shared__ int s_big;
@@ -327,7 +325,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void colsum_long_kernel(
     const i64 b = col_off[c];
     const int n = (int)(col_off[c + 1] - b);
     uint32_t* keys = entries + b;
-    const bool in_lds = n <= OCN_X_CS_LDS;
+    const bool in_lds = n <= CS_LDS;
     const uint32_t* sorted = keys;                         // where the sorted positions end up
     if (in_lds) {
       // A column's entries come from all over the batch, so their flag positions spread over [0, cap): CS_BINS position

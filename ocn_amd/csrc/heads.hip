@@ -88,11 +88,7 @@ __device__ __forceinline__ void hd_unroll(F&& f) { hd_unroll_impl(f, std::make_i
 #define HD_SP1 "v_mul_f32 %[t0], %[x0], %[sc]\n\tv_mul_f32 %[t1], %[x1], %[sc]\n\tv_cvt_pk_f16_f32 %[H], %[t0], %[t1]\n\tv_cvt_f32_f16 %[t2], %[H]\n\t"
 #define HD_SP2 "v_cvt_f32_f16_sdwa %[t3], %[H] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n\t" \
                "v_sub_f32 %[t0], %[t0], %[t2]\n\tv_sub_f32 %[t1], %[t1], %[t3]\n\tv_cvt_pk_f16_f32 %[L], %[t0], %[t1]\n\t"
-#ifndef OCN_X_HD_NOGLDS   /* timing experiment (tools/headsbench.py): no weight traffic */
 #define HD_DMA "s_add_u32 m0, %[ld], %[imm]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[vo], %[gb]\n\t"
-#else
-#define HD_DMA "s_add_u32 m0, %[ld], %[imm]\n\t"
-#endif
 
 // statement 1: (wait until at most N LDS reads are outstanding) acc (+)= wh . xl; the hi fragment of the tile three
 // steps ahead; first half of an operand split: t = x * sc, H = f16x2(t0, t1), t2 = f32(H.lo)
@@ -403,12 +399,6 @@ struct Heads {
 
 #define HD_PARK_BYTES(H) ((int64_t)HD_MAX_GRID * 4 * 2 * (H) * 32 * 4)
 #define HD_MAX_GRID 256               /* one workgroup per CU (LDS and registers admit no second one): a persistent grid */
-#ifdef OCN_X_HD_STAMPS               /* diagnostic build only (tools/headsbench.py): s_memtime at the phase boundaries of workgroup 0's first tile */
-#define HD_STAMP(k) do { if (blockIdx.x == 0 && tile == 0 && threadIdx.x == 0) \
-    reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(a.scratch) + HD_PARK_BYTES(H))[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define HD_STAMP(k) do {} while (0)
-#endif
 
 template <int NT, bool LN>
 __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsArgs a) {
@@ -425,9 +415,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
   const unsigned lds0 = (unsigned)(size_t)(lds_bytes_t)smem;
   for (int q = threadIdx.x; q < HD::VEC_FLOATS; q += OCN_BLOCK) s_vec[q] = a.vec[q];
   const i64 n_tiles = a.dump ? 1 : (a.B + HD_ROWS - 1) / HD_ROWS;
-#ifdef OCN_X_HD_CLOCK                /* diagnostic build only: the clock the chip holds under this kernel (guide, DVFS give-back item 6) */
-  const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
   // class boundaries of the class-major order (both | cn1 only | cn2 only | none), or "every row runs every branch"
   i64 m3 = a.B, m32 = a.B, m321 = a.B;
   if (a.ranges) { m3 = a.ranges[2 * 1 + 1]; m32 = a.ranges[2 * 0 + 1]; m321 = a.ranges[2 * 3 + 1]; }
@@ -501,7 +488,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
     const int wgA = tile_runs(tile, 0), wgB = tile_runs(tile, 1);
     const i64 ntile = tile_at(round + 1) >= 0 ? tile_at(round + 1) : tile;        // (past the end: this tile's rows once more)
     __syncthreads();                  // s_vec is written; nobody reads the previous tile's ring slots any more
-    HD_STAMP(0);
 
     Ring rg;
 #pragma unroll
@@ -518,7 +504,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
         for (int q = 0; q < NPW; ++q) hd_dma(lane16, p0 + (size_t)k * CHB + (size_t)q * 4096, rg.ld[k] + q * 4096);
       hd_sync<NPW>();                                                          // chunk 0 is there, chunk 1 on its way
     }
-    HD_STAMP(1);
 
     // ---- pooled branches a (xcn1lin) and b (xcn2lin): their shares M . act of the last layer's input -------------
 #pragma unroll 1
@@ -532,25 +517,18 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
       const char* pn = uni(a.panel[3 * nbr]) + (size_t)w * 1024;
       float sc, inv;
       hd_row_scale(x_prepare(row_has(slot, br)), s_scal[1 + 3 * br], sc, inv);
-      HD_STAMP(2 + 7 * br);
       HD::template layer<false, false>(rB, rA, sc, rg, p0, p1, lane16, nullptr);
-      HD_STAMP(3 + 7 * br);
       float m = HD::bias_relu(rA, rB, inv, vb, hh);
       HD::pin_in(rA);
       hd_row_scale(m, s_scal[2 + 3 * br], sc, inv);
-      HD_STAMP(4 + 7 * br);
       HD::template layer<false, false>(rB, rA, sc, rg, p1, p2, lane16, nullptr);
-      HD_STAMP(5 + 7 * br);
       if constexpr (LN) m = HD::bias_ln_relu(rA, rB, inv, vb + H, vb + 2 * H, vb + 3 * H, a.eps, hh);
       else m = HD::bias_relu(rA, rB, inv, vb + H, hh);
       HD::pin_in(rA);
       hd_row_scale(m, s_scal[3 + 3 * br], sc, inv);
-      HD_STAMP(6 + 7 * br);
       HD::template layer<false, true>(rB, rA, sc, rg, p2, pn, lane16, x_row(tile, nbr));
-      HD_STAMP(7 + 7 * br);
       // (constants mode: B = 1, every lane holds row 0 — wave 0's share, as parked, IS the constant in the park layout)
       HD::park_share((a.dump && w == 0 ? reinterpret_cast<f32x4*>(a.dump) : park) + (size_t)br * (NT * 4) * 64, rB, inv, lane);
-      HD_STAMP(8 + 7 * br);
     }
     // ---- xijlin, then out = ((share a + share b) + share c) + folded bias ---------------------------------------
     float inv;
@@ -559,17 +537,13 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
       const char* pc = uni(a.panel[P_MC]) + (size_t)w * 1024;
       float sc;
       hd_row_scale(x_prepare(live), s_scal[1 + P_X0], sc, inv);
-      HD_STAMP(16);
       HD::template layer<false, false>(rB, rA, sc, rg, px, pc, lane16, nullptr);
-      HD_STAMP(17);
       float m;
       if constexpr (LN) m = HD::bias_ln_relu(rA, rB, inv, s_vec + V_B0X * H, s_vec + V_GX * H, s_vec + V_EX * H, a.eps, hh);
       else m = HD::bias_relu(rA, rB, inv, s_vec + V_B0X * H, hh);
       HD::pin_in(rA);
       hd_row_scale(m, s_scal[1 + P_MC], sc, inv);
-      HD_STAMP(18);
       HD::template layer<true, true>(rB, rA, sc, rg, pc, pc, lane16, x_row(ntile, first_branch(ntile)));
-      HD_STAMP(19);
     }
     // ---- lin: LayerNorm, ReLU, Linear(H, 1) on the accumulator file (the VGPR set already holds the next rows) -----
     float PS[4];                          // quarter sums of the last layer's input (hd_quad)
@@ -660,14 +634,7 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
     }
     const float d = hd_quad(PD4);
     if (live && hh == 0 && !a.dump) a.y[a.y_row_map ? a.y_row_map[slot] : slot] = d + s_scal[0];
-    HD_STAMP(20);
   }
-#ifdef OCN_X_HD_CLOCK
-  if (threadIdx.x == 0) {            // into the scratch page of the diagnostic builds
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(a.scratch) + HD_PARK_BYTES(H)) + 64 + 2 * blockIdx.x;
-    if (blockIdx.x < 192) { o[0] = __builtin_amdgcn_s_memtime() - clk0; o[1] = __builtin_amdgcn_s_memrealtime() - rt0; }
-  }
-#endif
 }
 
 // ---- small batches: the same head on a tile of 32 candidates per workgroup (latency instead of throughput) -------------
@@ -851,12 +818,6 @@ struct HeadsN {
   }
 };
 
-#ifdef OCN_X_HN_STAMPS               /* diagnostic build only (tools/headslat.py -DOCN_X_HN_STAMPS): s_memtime at the phase boundaries of workgroup 0, wave 0 */
-#define HN_STAMP(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) \
-    reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(a.scratch) + HD_PARK_BYTES(H))[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define HN_STAMP(k) do {} while (0)
-#endif
 
 template <int NT, bool LN>
 __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_nsplit_kernel(const HeadsArgs a) {
@@ -912,9 +873,7 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_nsplit_kernel(const HeadsA
 #pragma unroll
       for (int g = 0; g < 4; ++g) y[u][g] = has ? y[u][g] : (f32x4)(0.f);
   };
-  HN_STAMP(0);
   __syncthreads();                    // s_vec is written
-  HN_STAMP(1);
   // (a + b): the pooled branches' shares of the last layer's input on this wave's tiles; -0 + x == x for every x
   f32x4 sab[TW][4];
 #pragma unroll
@@ -941,42 +900,29 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_nsplit_kernel(const HeadsA
     const char* pn = panel(nbr == 2 ? P_X0 : 3 * nbr);
     zero_unless(xin[br], row_has(br));
     HN::template operand<true>(ob, xin[br], s_scal[1 + 3 * br], inv, red, w, lane);
-    HN_STAMP(2 + 8 * br);
     HN::template layer<false>(acc, ob, fr, vo, p0, p1);
-    HN_STAMP(3 + 8 * br);
     HN::template bias<true>(y, acc, inv, vb, w, hh);
     HN::template operand<false>(ob, y, s_scal[2 + 3 * br], inv, red, w, lane);
-    HN_STAMP(4 + 8 * br);
     HN::template layer<false>(acc, ob, fr, vo, p1, p2);
-    HN_STAMP(5 + 8 * br);
     HN::template bias<!LN>(y, acc, inv, vb + H, w, hh);
     if constexpr (LN) HN::ln_relu(y, vb + 2 * H, vb + 3 * H, a.eps, red, w, hh, lane);
-    HN_STAMP(6 + 8 * br);
     HN::template operand<false>(ob, y, s_scal[3 + 3 * br], inv, red, w, lane);
-    HN_STAMP(7 + 8 * br);
     HN::template layer<false>(acc, ob, fr, vo, p2, pn);
-    HN_STAMP(8 + 8 * br);
 #pragma unroll
     for (int u = 0; u < TW; ++u)
 #pragma unroll
       for (int g = 0; g < 4; ++g) sab[u][g] += HD_GRP(acc[u], g) * (f32x4)(inv);
     HN::drain(fr);                    // (the paths join below)
-    HN_STAMP(9 + 8 * br);
   }
   // ---- xijlin, then ((share a + share b) + share c) + folded bias on this wave's tiles --------------------------------
   const char *px = panel(P_X0), *pc = panel(P_MC);
   zero_unless(xin[2], live);
   HN::template operand<true>(ob, xin[2], s_scal[1 + P_X0], inv, red, w, lane);
-  HN_STAMP(18);
   HN::template layer<false>(acc, ob, fr, vo, px, pc);
-  HN_STAMP(19);
   HN::template bias<!LN>(y, acc, inv, s_vec + V_B0X * H, w, hh);
   if constexpr (LN) HN::ln_relu(y, s_vec + V_GX * H, s_vec + V_EX * H, a.eps, red, w, hh, lane);
-  HN_STAMP(20);
   HN::template operand<false>(ob, y, s_scal[1 + P_MC], inv, red, w, lane);
-  HN_STAMP(21);
   HN::template layer<true>(acc, ob, fr, vo, pc, pc);
-  HN_STAMP(22);
 #pragma unroll
   for (int u = 0; u < TW; ++u)
 #pragma unroll
@@ -1024,7 +970,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_nsplit_kernel(const HeadsA
   HN::cross_put(red + 512, HN::quarter(d4), w, lane);
   __syncthreads();
   if (w == 0 && live && hh == 0) a.y[a.y_row_map ? a.y_row_map[slot] : slot] = HN::cross_sum(red + 512, lane) + s_scal[0];
-  HN_STAMP(23);
 }
 
 // Wp[s][t][hi, lo][lane][8 halves]: k-step s = 2 tt + ss consumes accumulator tile tt, registers 8 ss .. 8 ss + 7, of
@@ -1115,7 +1060,7 @@ int32_t ocn_heads_nscal(void) { return HD_NSCAL; }
 
 int64_t ocn_heads_const_bytes(int32_t H) { return (int64_t)2 * H * 32 * 4; }   /* two shares of one wave, park layout */
 
-int64_t ocn_heads_scratch_bytes(int32_t H) { return HD_PARK_BYTES(H) + 4096; }   /* + a page of diagnostic stamps */
+int64_t ocn_heads_scratch_bytes(int32_t H) { return HD_PARK_BYTES(H) + 4096; }   /* + a spare page (where the diagnostic builds of DESIGN.md section 4 stamped) */
 
 int ocn_heads_fused(const OcnHeadsArgs* h, void* stream) {
   if (!h || h->B < 0 || h->H <= 0) return OCN_EINVAL;

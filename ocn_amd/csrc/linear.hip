@@ -16,9 +16,7 @@
 
 #define LIN_KS 16                    // k per MFMA step
 #define LIN_ROWS 128                 // rows per workgroup
-#ifndef LIN_PF
-#define LIN_PF 4                     // X fragments in flight per lane (k-steps of look-ahead)
-#endif
+constexpr int LIN_PF = 4;            // X fragments in flight per lane (k-steps of look-ahead)
 
 __device__ __forceinline__ void split_frag(const float4& xa, const float4& xb, bf16x8& a1, bf16x8& a2, bf16x8& a3) {
   const float xs[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
@@ -145,7 +143,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
       if (s < nks) {
         const int cur = s & 1;
         bf16x8 stage[(PANEL + OCN_BLOCK - 1) / OCN_BLOCK];
-#ifndef OCN_X_LIN_NOW    /* timing experiments: no weight-panel reload / no X reload */
         if (s + 1 < nks) {
 #pragma unroll
           for (int q = 0; q < (PANEL + OCN_BLOCK - 1) / OCN_BLOCK; ++q) {
@@ -153,13 +150,10 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
             if (f < PANEL) stage[q] = wp8[(i64)(s + 1) * PANEL + f];
           }
         }
-#endif
-#ifndef OCN_X_LIN_NOX
         if (s + LIN_PF < nks) {                            // slot d was consumed when step s was split
           xr[d][0] = xrow[(s + LIN_PF) * (LIN_KS / 4)];
           xr[d][1] = xrow[(s + LIN_PF) * (LIN_KS / 4) + 1];
         }
-#endif
         bf16x8 n1 = a1, n2 = a2, n3 = a3;
         // B fragments are fetched from LDS one column tile ahead of the MFMAs that consume them
         bf16x8 bq[2][3];
@@ -174,11 +168,9 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
           __builtin_amdgcn_sched_barrier(0);               // keep the next tile's LDS reads ahead of these MFMAs
           const bf16x8 b1 = bq[t & 1][0], b2 = bq[t & 1][1], b3 = bq[t & 1][2];
           // smallest cross terms first
-#ifndef OCN_X_LIN_T3    /* timing experiment: three cross terms only (what a 2-way split would issue) */
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[t], 0, 0, 0);
-#endif
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[t], 0, 0, 0);
@@ -188,7 +180,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-#ifndef OCN_X_LIN_NOW
         if (s + 1 < nks) {
 #pragma unroll
           for (int q = 0; q < (PANEL + OCN_BLOCK - 1) / OCN_BLOCK; ++q) {
@@ -196,11 +187,8 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
             if (f < PANEL) wbuf[cur ^ 1][f] = stage[q];
           }
         }
-#endif
         a1 = n1; a2 = n2; a3 = n3;
-#ifndef OCN_X_LIN_NOBAR
         __syncthreads();
-#endif
       }
     }
   }
@@ -280,27 +268,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
     }
     return;
   }
-#ifdef OCN_X_LIN_NOSTORE   /* timing experiment: keep the accumulators live, store one word */
-  { float z = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) z += acc[t][i];
-    if (z == 12345.678f) Y[0] = z;
-    return; }
-#endif
-#ifdef OCN_X_LIN_DIRECTSTORE   /* timing experiment: 4-byte stores straight from the accumulator layout */
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const i64 row = row0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-    if (row < M) {
-      float* yr = Y + row * G.ldY + r;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        yr[32 * t] = acc[t][i] + (G.addend ? G.addend[(G.add_bcast ? 0 : row * G.ldAdd) + 32 * t + r] : 0.f);
-    }
-  }
-#else
   // The accumulator layout gives each lane one column of 16 rows: 128 four-byte stores per lane.
   // Instead each wave transposes 8 rows at a time through its slice of the (now idle) weight
   // buffers and writes them back as whole rows, 16 bytes per lane, 1 KiB per wave-instruction.
@@ -328,7 +295,6 @@ __global__ __launch_bounds__(OCN_BLOCK, 2) void linear_bf16x6_kernel(const LinAr
     }
     __syncthreads();
   }
-#endif
 }
 
 extern "C" {

@@ -288,12 +288,19 @@ def test_overlapped_steps_host_order_without_a_gpu():
 
 
 def test_the_shipped_library_was_built_without_experiment_macros(hiplib):
-    """the kernels carry ~30 `OCN_X_*` timing-experiment switches, several of which give wrong results when
-    defined.  The product build never defines one: `_lib.build_flags()` holds none, the library records the compile command of
-    every translation unit (-frecord-command-line -> .GCC.command.line) and none of them names one, and no `ocn_debug_*` entry
-    (they only exist under those switches) is exported."""
+    """the kernels carried `OCN_X_*` timing-experiment switches, several of which gave wrong results when
+    defined, and `ocn_debug_*` entries with `s_memtime` stamps under them.  They are gone from the sources; and the product build
+    defines none: `_lib.build_flags()` holds none, the library records the compile command of every translation unit
+    (-frecord-command-line -> .GCC.command.line) and none of them names one, and no `ocn_debug_*` entry is exported."""
+    import glob
     import re
     from ocn_amd import _lib
+    files = [f for d in (_lib.CSRC, _lib.INCLUDE) for f in glob.glob(os.path.join(d, "*")) if os.path.isfile(f)]
+    assert len(files) >= 17
+    for f in files:
+        txt = open(f, encoding="utf-8").read()
+        for word in ("OCN_X_", "ocn_debug_", "s_memtime"):
+            assert word not in txt, f"{os.path.relpath(f, ROOT)} names {word}"
     assert not any("OCN_X_" in f for f in _lib.build_flags())
     blob = open(_lib.LIB_PATH, "rb").read()
     cmds = re.findall(rb"[^\x00]*-frecord-command-line[^\x00]*", blob)

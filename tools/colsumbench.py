@@ -1,21 +1,14 @@
 """The order-exact column sums of a trained cn5 (innerprod != 0) at the collab shape, kernel by kernel:
-    python tools/colsumbench.py [-D flags ...]
+    python tools/colsumbench.py
 HIP-event time of ocn_cn_colsum_exact + weights per batch, the number of ordered / long columns, S2 checksum."""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-flags = tuple(f for f in sys.argv[1:] if f.startswith("-D"))
-if flags:
-    os.environ["OCN_LIB_PATH"] = "/tmp/libocn_cs.so"
 import argparse  # noqa: E402
 
 import torch  # noqa: E402
-from ocn_amd import _lib  # noqa: E402
-
-if flags:
-    _lib.build(force=True, extra_flags=flags, out="/tmp/libocn_cs.so")
 import bench  # noqa: E402
 from ocn_amd import ops  # noqa: E402
 from ocn_amd.utils import CNState  # noqa: E402
@@ -45,7 +38,7 @@ def main():
             torch.cuda.synchronize()
             times.append(a.elapsed_time(b))
         times.sort()
-        print(f"{' '.join(flags) or 'product':24s} weights with order-exact sums: median {times[len(times) // 2] * 1e3:.1f} us, best {times[0] * 1e3:.1f} us, "
+        print(f"weights with order-exact sums: median {times[len(times) // 2] * 1e3:.1f} us, best {times[0] * 1e3:.1f} us, "
               f"checksum {float(w.double().sum()):.9f}", flush=True)
 
 

@@ -9,15 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-flags = tuple(f for f in sys.argv[1:] if f.startswith("-D"))
-sys.argv = [v for v in sys.argv if not v.startswith("-D")]
-if flags:
-    os.environ["OCN_LIB_PATH"] = "/tmp/libocn_hl.so"
 import torch  # noqa: E402
-from ocn_amd import _lib  # noqa: E402
-
-if flags:
-    _lib.build(force=True, extra_flags=flags, out="/tmp/libocn_hl.so")
 import ocn_amd.model as M  # noqa: E402
 from ocn_amd import ops  # noqa: E402
 
@@ -47,20 +39,6 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.reps * 1e3, y
 
-    if "-DOCN_X_HN_STAMPS" in flags:      # s_memtime at the phase boundaries of workgroup 0 (heads.hip: HN_STAMP)
-        x1, x2, xij = (torch.randn(1152, H, device=dev) for _ in range(3))
-        ops.heads_small_batch(1 << 40)
-        with torch.no_grad():
-            for _ in range(3):
-                ops.heads_fused(x1, x2, xij, pack, None, None, True, scratch)
-        torch.cuda.synchronize()
-        st = scratch.view(torch.int64)[-512:][:24].cpu().tolist()
-        names = ["vec+sync"] + [f"{b}.{p}" for b in "ab" for p in ("x operand", "L0", "bias+operand", "L3", "bias+LN", "operand", "Lout", "share")]
-        names += ["c.x operand", "c.L0", "c.bias+LN", "c.operand", "c.Lout", "final"]
-        print("  ".join(f"{n} {st[i + 1] - st[i]}" for i, n in enumerate(names)), flush=True)
-        print(f"workgroup cycles (s_memtime, 100 MHz ticks x clock ratio) {st[23] - st[0]}", flush=True)
-        ops.heads_small_batch(prev)
-        return
     try:
         for B in (32, 256, 1152, 2048, 4096, 8192, 16384, 32768, 65536):
             x1, x2, xij = (torch.randn(B, H, device=dev) for _ in range(3))

@@ -1,13 +1,11 @@
-"""Per-kernel timing on the bench workload, optionally for experimental builds of the library.
+"""Per-kernel timing on the bench workload.
 
-    python tools/kbench.py                        # shipped library
-    python tools/kbench.py -DOCN_X_NOATOMIC ...   # each flag set = one variant build in /tmp
+    python tools/kbench.py
 
-Every variant runs in its own subprocess (OCN_LIB_PATH) and prints HIP-event times of the CN-stage
-kernels.  Experiments only — nothing here is part of the product or the tests.
+Prints HIP-event times of the CN-stage kernels.  Experiments only — nothing here is part of the
+product or the tests.
 """
 import os
-import subprocess
 import sys
 import time
 
@@ -15,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child():
+def main():
     import argparse
 
     import torch
@@ -69,18 +67,5 @@ def child():
     print(" ".join(f"{k}={v[0]*1e3:.1f}us" for k, v in tot.items()), f"checksum={chk}", flush=True)
 
 
-def main():
-    variants = [()] + [tuple(a.split(",")) for a in sys.argv[1:]]
-    from ocn_amd import _lib
-    for v in variants:
-        out = _lib.LIB_PATH if not v else f"/tmp/libocn_{abs(hash(v))}.so"
-        if v:
-            _lib.build(force=True, extra_flags=v, out=out)
-        env = dict(os.environ, OCN_LIB_PATH=out, KB_CHILD="1")
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True)
-        line = [l for l in r.stdout.splitlines() if "checksum" in l]
-        print(f"{' '.join(v) or 'shipped':40s} {line[-1] if line else r.stderr[-400:]}", flush=True)
-
-
 if __name__ == "__main__":
-    child() if os.environ.get("KB_CHILD") else main()
+    main()

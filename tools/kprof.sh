@@ -4,10 +4,6 @@ cfg=$1; shift
 O=${OCN_OUT_DIR:-bench_out}
 mkdir -p $O
 export TMPDIR=/tmp
-if [ -n "$KPROF_FLAGS" ]; then   # experimental build:  KPROF_FLAGS="-DOCN_X_WALK_NOSWEEP" tools/kprof.sh citation2
-  python -c "from ocn_amd import _lib; _lib.build(force=True, extra_flags='$KPROF_FLAGS'.split(','), out='/tmp/libocn_kprof.so')"
-  export OCN_LIB_PATH=/tmp/libocn_kprof.so
-fi
 rm -rf $O/kprof_tmp
 rocprofv3 --kernel-trace --stats -d $O/kprof_tmp -o run --output-format csv -- python bench.py --full --config $cfg --steps 32 --warmup 5 --no-cpu-baseline --prewarm 8 "$@" > $O/kprof_$cfg.json 2> /dev/null
 python - <<PY

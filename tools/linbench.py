@@ -1,14 +1,12 @@
-"""Times ocn_linear_bf16x6 against torch's fp32 GEMM on the head shapes; variants via compile flags
-like tools/kbench.py.  Experiments only."""
+"""Times ocn_linear_bf16x6 against torch's fp32 GEMM on the head shapes.  Experiments only."""
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child():
+def main():
     import torch
     from ocn_amd import ops
     dev = torch.device("cuda:0")
@@ -39,17 +37,5 @@ def child():
           f"maxdiff={err:.2e} checksum", flush=True)
 
 
-def main():
-    from ocn_amd import _lib
-    for v in [()] + [tuple(a.split(",")) for a in sys.argv[1:]]:
-        out = _lib.LIB_PATH if not v else f"/tmp/libocn_{abs(hash(v))}.so"
-        if v:
-            _lib.build(force=True, extra_flags=v, out=out)
-        env = dict(os.environ, OCN_LIB_PATH=out, KB_CHILD="1")
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True)
-        line = [l for l in r.stdout.splitlines() if "checksum" in l]
-        print(f"{' '.join(v) or 'shipped':32s} {line[-1] if line else r.stderr[-600:]}", flush=True)
-
-
 if __name__ == "__main__":
-    child() if os.environ.get("KB_CHILD") else main()
+    main()

@@ -1,20 +1,13 @@
 """Stress of the two-stream scoring loop against the one-stream loop: the tool that found the H = 64 pooling kernel's packed-math
 fault (one batch in a hundred with 64 bytes of one xcn1 row wrong, only beside another stream's heads).
-    DBG_H=64 DBG_MODE=real DBG_REPS=250 python tools/loop_race_check.py [-DOCN_X_WAVE_CHECK]
+    DBG_H=64 DBG_MODE=real DBG_REPS=250 python tools/loop_race_check.py
 n = 20 000, twelve ragged batches of DBG_B (8 192) candidates, trained cn5; every repetition runs the depth-2 loop and compares each
 batch's scores with the one-stream loop's.  DBG_MODE: real (the product), noskip (no class-major rows), pool_only / dummy_writes /
-heads_then_pool (what phase B does: nothing, unrelated work, the heads with the pooled rows compared — which buffer is hit).
--DOCN_X_WAVE_CHECK: the wave pooling kernel recomputes every sum straight from memory and counts disagreements in the kernel."""
+heads_then_pool (what phase B does: nothing, unrelated work, the heads with the pooled rows compared — which buffer is hit)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from types import SimpleNamespace
-flags = tuple(f for f in sys.argv[1:] if f.startswith("-D"))
-if flags:
-    os.environ["OCN_LIB_PATH"] = "/tmp/libocn_dbg.so"
 import torch
-if flags:
-    from ocn_amd import _lib
-    _lib.build(force=True, extra_flags=flags, out="/tmp/libocn_dbg.so")
 from ocn_amd.sparse import SparseTensor
 from ocn_amd.synth import chung_lu_graph, sample_edges
 from ocn_amd import ops
@@ -107,11 +100,3 @@ with torch.no_grad():
                     print("   correct", [round(v, 4) for v in ref_pl[pln, row, c0:c0 + 16].tolist()])
                     print("   row before (correct)", [round(v, 4) for v in ref_pl[pln, row, c0 - 4:c0].tolist()], "xcn2 same cols", [round(v, 4) for v in ref_pl[1, row, c0:c0 + 4].tolist()])
     print(mode, "failures", nbad)
-    if "-DOCN_X_WAVE_CHECK" in flags:
-        import ctypes
-        lib = ctypes.CDLL("/tmp/libocn_dbg.so")
-        outb = (ctypes.c_float * (4096 * 6))()
-        nn = ctypes.c_uint(0)
-        print("wave check rc", lib.ocn_debug_wave_check(outb, ctypes.byref(nn)), "in-kernel mismatches (LDS path vs memory path):", nn.value)
-        for q in range(min(nn.value, 24)):
-            print("   e", int(outb[q * 6]), "lane", int(outb[q * 6 + 1]), "acc1", outb[q * 6 + 2], "direct", outb[q * 6 + 3], "acc2", outb[q * 6 + 4], "direct", outb[q * 6 + 5])

@@ -1,23 +1,22 @@
-"""Timing of the walk-count intersection stage (ppa / citation2 route) on the bench workload, for the
-shipped library and for experimental builds (compile flags as in tools/kbench.py).  Experiments only.
+"""Timing of the walk-count intersection stage (ppa / citation2 route) on the bench workload.
+Experiments only.
 
-    python tools/walkbench.py citation2 [-DOCN_X_WALK_NOSWEEP ...]
+    python tools/walkbench.py citation2
 """
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child():
+def main():
     import argparse
     import torch
     import bench
     from ocn_amd import ops
     from ocn_amd.utils import CNState
-    args = argparse.Namespace(dataset=os.environ["KB_DATASET"], scale=1.0, hiddim=None, predictor=None, batch=None, batches=1, innerprod=0.0)
+    args = argparse.Namespace(dataset=sys.argv[1], scale=1.0, hiddim=None, predictor=None, batch=None, batches=1, innerprod=0.0)
     dev = torch.device("cuda:0")
     wl = bench.build_workload(args, dev, 0, 1)
     adj, e = wl["adj"], wl["edges"][0]
@@ -41,18 +40,5 @@ def child():
     print(" | ".join(out), "checksum", flush=True)
 
 
-def main():
-    from ocn_amd import _lib
-    ds = sys.argv[1]
-    for v in [()] + [tuple(a.split(",")) for a in sys.argv[2:]]:
-        out = _lib.LIB_PATH if not v else f"/tmp/libocn_{abs(hash(v))}.so"
-        if v:
-            _lib.build(force=True, extra_flags=v, out=out)
-        env = dict(os.environ, OCN_LIB_PATH=out, KB_CHILD="1", KB_DATASET=ds)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True)
-        line = [l for l in r.stdout.splitlines() if "checksum" in l]
-        print(f"{' '.join(v) or 'shipped':28s} {line[-1] if line else r.stderr[-800:]}", flush=True)
-
-
 if __name__ == "__main__":
-    child() if os.environ.get("KB_CHILD") else main()
+    main()
