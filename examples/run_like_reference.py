@@ -7,6 +7,8 @@ argument parser is the reference's call sequence with the three import lines swa
 
     python examples/run_like_reference.py --dataset cora --predictor cn5 --epochs 5
     python examples/run_like_reference.py --dataset collab --scale 0.05 --hiddim 64 --batch_size 8192
+    python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
+        --gnnedp 0.07 --res --maskinput --batch_size 384
 """
 import argparse
 import os
@@ -114,6 +116,8 @@ def main(argv=None):
     ap.add_argument("--gnnlr", type=float, default=0.0043)
     ap.add_argument("--prelr", type=float, default=0.0024)
     ap.add_argument("--feat", type=int, default=0, help="feature width override for the synthetic x")
+    ap.add_argument("--gnnedp", type=float, default=0.0, help="DropAdj probability of the encoder's adjacency (train only)")
+    ap.add_argument("--res", action="store_true", help="residual connections in the encoder")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
@@ -123,7 +127,7 @@ def main(argv=None):
     data.full_adj_t = data.full_adj_t.to_device(dev) if args.use_valedges_as_input else data.adj_t
     torch.manual_seed(0)
     fin = args.hiddim if data.max_x >= 0 else data.x.shape[1]
-    model = GCN(fin, args.hiddim, args.hiddim, args.mplayers, 0.05, True, False, data.max_x, args.model, True, 0.0,
+    model = GCN(fin, args.hiddim, args.hiddim, args.mplayers, 0.05, True, args.res, data.max_x, args.model, True, args.gnnedp,
                 xdropout=0.3, taildropout=0.1).to(dev)
     predictor = predictor_dict[args.predictor](args.hiddim, args.hiddim, 1, args.nnlayers, 0.05, 0.0, True,
                                                use_xlin=True, tailact=True).to(dev)

@@ -35,7 +35,8 @@ extern "C" {
  *    int32[4] for every intersection entry, word 3 the sticky error word; ocn_cn_weights_cn7 takes the Chebyshev diagonals,
  *    ocn_gather_schedule a segment; + ocn_cn_gather3_backward, ocn_cn_gather_backward_det_lists, ocn_ln_drop_relu_*.
  * 9: + ocn_heads_small_batch (ocn_heads_fused picks its small-batch form by the batch size; same bits), ocn_spgemm_bit_rows
- *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2). */
+ *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
+ *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -354,11 +355,26 @@ int ocn_cn_gather_backward_det_lists(const int64_t* rowptrA, const int32_t* colA
  * edge_scale: 0 -> entry weight is pre[k] applied to x[k] first (PureConv: n*x then A.);
  *             1 -> entry weight is fl(pre[r]*pre[k]) (GCNConv / PureConv2: normalised A).
  * self_mode: 0 none; 1 add the row's own term after the neighbours (PureConv gcn);
- *            2 insert it at its sorted column position (GCNConv fill_diag). */
+ *            2 insert it at its sorted column position (GCNConv fill_diag).
+ * max of a valued adjacency is max_k fl(val_rk * x[k]) (torch_sparse spmm_max); an empty row gives 0.  Max is defined for
+ * pre = post = NULL and self_mode = 0 only: no caller passes them with mode 2, and what it computes with them is unspecified. */
 int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows,
                  const float* x, int32_t F, const float* pre, const float* post,
                  int32_t mode, int32_t edge_scale, int32_t self_mode,
                  float* y, void* stream);
+
+/* Max aggregation under autograd (model.py:42-55 aggr "max", pygho spmm aggr "amax", model.py:101-102).
+ * ocn_spmm_csr_max_arg: y[i,f] = max over row i of fl(val_ik * x[k,f]) (val NULL: x[k,f]) and arg[i,f] = the column id
+ *   k of the winner, the first maximum in the row's (ascending column) order; an empty row gives y = 0, arg = -1.
+ *   y, arg: [n_rows, F] fp32 / int32.  Bit-equal to ocn_spmm_csr mode 2 for inputs without NaN or ±0 ties.
+ * ocn_spmm_max_backward: gx[k,f] = sum over the entries (k, i) of Aᵀ with arg[i,f] == k of valT * g[i,f] (valT NULL: 1),
+ *   added in Aᵀ's row order (no atomics: bit-reproducible); rowptrT / colT / valT = the CSR of Aᵀ with n_rows rows, arg and
+ *   g [rows of A, F], gx [n_rows, F] (every row written).
+ * F in {16, 32, 64, 128, 256, 512}; NULL pointers, n_rows < 0 or another F: OCN_EINVAL before any launch. */
+int ocn_spmm_csr_max_arg(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows,
+                         const float* x, int32_t F, float* y, int32_t* arg, void* stream);
+int ocn_spmm_max_backward(const int64_t* rowptrT, const int32_t* colT, const float* valT, int64_t n_rows,
+                          const int32_t* arg, const float* g, int32_t F, float* gx, void* stream);
 
 /* out[r] = 1/sqrt(add + deg(r)) (0 where the argument is 0): rsqrt_(1+adj.sum(-1)) of
  * model.py:51,106 (add=1) and gcn_norm's deg^-1/2 (add=1 after fill_diag); deg = row length, or the

@@ -24,7 +24,10 @@ enum { SPMM_SUM = 0, SPMM_MEAN = 1, SPMM_MAX = 2 };
 
 template <int MODE>
 __device__ __forceinline__ void red4(float4& acc, float w, bool weighted, const float4& x) {
-  if (MODE == SPMM_MAX) {
+  if (MODE == SPMM_MAX && weighted) {        // valued max (torch_sparse spmm_max): max_k fl(val_ik * x_k)
+    acc.x = fmaxf(acc.x, __fmul_rn(w, x.x)); acc.y = fmaxf(acc.y, __fmul_rn(w, x.y));
+    acc.z = fmaxf(acc.z, __fmul_rn(w, x.z)); acc.w = fmaxf(acc.w, __fmul_rn(w, x.w));
+  } else if (MODE == SPMM_MAX) {
     acc.x = fmaxf(acc.x, x.x); acc.y = fmaxf(acc.y, x.y);
     acc.z = fmaxf(acc.z, x.z); acc.w = fmaxf(acc.w, x.w);
   } else if (weighted) {
@@ -129,6 +132,150 @@ __global__ __launch_bounds__(OCN_BLOCK) void spmm_csr_kernel(
   }
 }
 
+// Max aggregation under autograd.  Forward: y[i,f] = max over row i of fl(v_ik * x[k,f]) (v = 1 unvalued) and
+// arg[i,f] = the COLUMN id k of the winner — the backward walks Aᵀ (SparseTensor.t(): no map back to A's positions), and
+// in a coalesced row (i, k) names one entry.  Ties go to the first maximum in row (ascending column) order: the row's
+// first entry seeds the lane, later entries replace it only when strictly greater.  Empty row: y = 0, arg = -1 (the plain
+// kernel's seen == 0 rule).  Without NaN and ±0 ties y is bit-equal to spmm_csr_kernel<.., SPMM_MAX>.
+template <int LPE, int NV>
+__global__ __launch_bounds__(OCN_BLOCK) void spmm_max_arg_kernel(
+    const i64* __restrict__ rowptr, const int32_t* __restrict__ col, i64 n_rows, const float* __restrict__ val,
+    const float* __restrict__ x, int F, float* __restrict__ y, int32_t* __restrict__ arg) {
+  constexpr int GPW = OCN_WAVE / LPE;
+  constexpr int UNR = 4;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane % LPE;
+  const int gbase = lane - gl;
+  const i64 r = ((i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  if (r >= n_rows) return;
+  const i64 a0 = rowptr[r], da = rowptr[r + 1] - a0;
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const i64 rowq = F >> 2;
+
+  float4 acc[NV];
+  int4 am[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); am[v] = make_int4(-1, -1, -1, -1); }
+
+  for (i64 p0 = 0; p0 < da; p0 += LPE) {
+    const i64 p = p0 + gl;
+    int32_t k = 0;
+    float wk = 1.0f;
+    if (p < da) {
+      k = col[a0 + p];
+      if (val) wk = val[a0 + p];
+    }
+    const int cnt = (int)((da - p0) < LPE ? (da - p0) : LPE);
+    for (int b0 = 0; b0 < cnt; b0 += UNR) {
+      int32_t kk[UNR];
+      float ww[UNR];
+      float4 xv[UNR][NV];
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        const int b = b0 + t;
+        const int sl = gbase + (b < cnt ? b : 0);
+        kk[t] = __shfl(k, sl, OCN_WAVE);
+        ww[t] = __shfl(wk, sl, OCN_WAVE);
+        if (b < cnt) {
+          const float4* row = x4 + (i64)kk[t] * rowq + gl;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) xv[t][v] = row[v * LPE];
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        if (b0 + t < cnt) {
+          const bool first = p0 + b0 + t == 0;          // the row's first entry seeds every feature
+          const int32_t kc = kk[t];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            float4 c = xv[t][v];
+            if (val) { c.x = __fmul_rn(ww[t], c.x); c.y = __fmul_rn(ww[t], c.y); c.z = __fmul_rn(ww[t], c.z); c.w = __fmul_rn(ww[t], c.w); }
+            if (first || c.x > acc[v].x) { acc[v].x = c.x; am[v].x = kc; }
+            if (first || c.y > acc[v].y) { acc[v].y = c.y; am[v].y = kc; }
+            if (first || c.z > acc[v].z) { acc[v].z = c.z; am[v].z = kc; }
+            if (first || c.w > acc[v].w) { acc[v].w = c.w; am[v].w = kc; }
+          }
+        }
+      }
+    }
+  }
+  float4* o = reinterpret_cast<float4*>(y) + r * rowq + gl;
+  int4* oa = reinterpret_cast<int4*>(arg) + r * rowq + gl;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) { o[v * LPE] = acc[v]; oa[v * LPE] = am[v]; }
+}
+
+// Max backward: gx[k,f] = Σ_{i in row k of Aᵀ, arg[i,f] == k} v_ik * g[i,f].  One lane group per row k of Aᵀ, the
+// entries added (__fadd_rn) in Aᵀ's row order: no atomics, two runs are bit-equal.  Every gx row is written (zeros
+// included), so the output needs no memset.
+template <int LPE, int NV>
+__global__ __launch_bounds__(OCN_BLOCK) void spmm_max_backward_kernel(
+    const i64* __restrict__ rowptrT, const int32_t* __restrict__ colT, i64 n_rows, const float* __restrict__ valT,
+    const int32_t* __restrict__ arg, const float* __restrict__ g, int F, float* __restrict__ gx) {
+  constexpr int GPW = OCN_WAVE / LPE;
+  constexpr int UNR = 4;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane % LPE;
+  const int gbase = lane - gl;
+  const i64 r = ((i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  if (r >= n_rows) return;
+  const i64 a0 = rowptrT[r], da = rowptrT[r + 1] - a0;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  const int4* arg4 = reinterpret_cast<const int4*>(arg);
+  const i64 rowq = F >> 2;
+  const int32_t me = (int32_t)r;
+
+  float4 acc[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  for (i64 p0 = 0; p0 < da; p0 += LPE) {
+    const i64 p = p0 + gl;
+    int32_t i = 0;
+    float wi = 1.0f;
+    if (p < da) {
+      i = colT[a0 + p];
+      if (valT) wi = valT[a0 + p];
+    }
+    const int cnt = (int)((da - p0) < LPE ? (da - p0) : LPE);
+    for (int b0 = 0; b0 < cnt; b0 += UNR) {
+      float ww[UNR];
+      float4 gv[UNR][NV];
+      int4 av[UNR][NV];
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        const int b = b0 + t;
+        const int sl = gbase + (b < cnt ? b : 0);
+        const int32_t ii = __shfl(i, sl, OCN_WAVE);
+        ww[t] = __shfl(wi, sl, OCN_WAVE);
+        if (b < cnt) {
+          const i64 off = (i64)ii * rowq + gl;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) { av[t][v] = arg4[off + v * LPE]; gv[t][v] = g4[off + v * LPE]; }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        if (b0 + t < cnt) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            float4 c = gv[t][v];
+            if (valT) { c.x = __fmul_rn(ww[t], c.x); c.y = __fmul_rn(ww[t], c.y); c.z = __fmul_rn(ww[t], c.z); c.w = __fmul_rn(ww[t], c.w); }
+            if (av[t][v].x == me) acc[v].x = __fadd_rn(acc[v].x, c.x);
+            if (av[t][v].y == me) acc[v].y = __fadd_rn(acc[v].y, c.y);
+            if (av[t][v].z == me) acc[v].z = __fadd_rn(acc[v].z, c.z);
+            if (av[t][v].w == me) acc[v].w = __fadd_rn(acc[v].w, c.w);
+          }
+        }
+      }
+    }
+  }
+  float4* o = reinterpret_cast<float4*>(gx) + r * rowq + gl;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) o[v * LPE] = acc[v];
+}
+
 extern "C" {
 
 #define SPMM_ARGS (const i64*)rowptr, col, (i64)n_rows, val, x, (int)F, pre, post, (int)edge_scale, \
@@ -160,6 +307,55 @@ int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, in
   if (mode == SPMM_SUM) DISPATCH_SPMM(SPMM_SUM);
   else if (mode == SPMM_MEAN) DISPATCH_SPMM(SPMM_MEAN);
   else DISPATCH_SPMM(SPMM_MAX);
+  return launch_status();
+}
+
+// F -> (lanes per row, float4 per lane) of the lane-group kernels above: the widths of DISPATCH_SPMM
+#define DISPATCH_F(LAUNCH)                                                                          \
+  do {                                                                                              \
+    if (F == 16) LAUNCH(4, 1);                                                                      \
+    else if (F == 32) LAUNCH(8, 1);                                                                 \
+    else if (F == 64) LAUNCH(16, 1);                                                                \
+    else if (F == 128) LAUNCH(32, 1);                                                               \
+    else if (F == 256) LAUNCH(64, 1);                                                               \
+    else LAUNCH(64, 2);                                                                             \
+  } while (0)
+
+static inline bool spmm_width_ok(int32_t F) {
+  return F == 16 || F == 32 || F == 64 || F == 128 || F == 256 || F == 512;
+}
+
+int ocn_spmm_csr_max_arg(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, const float* x,
+                         int32_t F, float* y, int32_t* arg, void* stream) {
+  if (n_rows < 0 || !spmm_width_ok(F)) return OCN_EINVAL;
+  if (!rowptr || !col || !x || !y || !arg) return OCN_EINVAL;
+  if (n_rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_MAX_ARG(LPE, NV)                                                                           \
+  do {                                                                                                    \
+    const i64 rpb = (i64)OCN_WPB * (OCN_WAVE / (LPE));                                                    \
+    hipLaunchKernelGGL((spmm_max_arg_kernel<LPE, NV>), dim3((unsigned)((n_rows + rpb - 1) / rpb)),        \
+                       dim3(OCN_BLOCK), 0, st, (const i64*)rowptr, col, (i64)n_rows, val, x, (int)F, y, arg); \
+  } while (0)
+  DISPATCH_F(LAUNCH_MAX_ARG);
+#undef LAUNCH_MAX_ARG
+  return launch_status();
+}
+
+int ocn_spmm_max_backward(const int64_t* rowptrT, const int32_t* colT, const float* valT, int64_t n_rows,
+                          const int32_t* arg, const float* g, int32_t F, float* gx, void* stream) {
+  if (n_rows < 0 || !spmm_width_ok(F)) return OCN_EINVAL;
+  if (!rowptrT || !colT || !arg || !g || !gx) return OCN_EINVAL;
+  if (n_rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_MAX_BWD(LPE, NV)                                                                           \
+  do {                                                                                                    \
+    const i64 rpb = (i64)OCN_WPB * (OCN_WAVE / (LPE));                                                    \
+    hipLaunchKernelGGL((spmm_max_backward_kernel<LPE, NV>), dim3((unsigned)((n_rows + rpb - 1) / rpb)),   \
+                       dim3(OCN_BLOCK), 0, st, (const i64*)rowptrT, colT, (i64)n_rows, valT, arg, g, (int)F, gx); \
+  } while (0)
+  DISPATCH_F(LAUNCH_MAX_BWD);
+#undef LAUNCH_MAX_BWD
   return launch_status();
 }
 

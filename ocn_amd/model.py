@@ -67,16 +67,30 @@ class DropAdj(nn.Module):
 # autograd glue (training drop-in): the HIP kernels are linear in x / h, their transposes are HIP
 # kernels too
 # ------------------------------------------------------------------------------------------
+def _plain_aggr(kw) -> None:
+    if kw.get("pre") is not None or kw.get("post") is not None or kw.get("self_mode", 0):
+        raise ValueError(f"{kw['mode']} aggregation under autograd takes no pre / post / self term")
+
+
 class _SpmmFn(torch.autograd.Function):
     """y = M x for one of the encoder operators.  The drivers' adjacencies are symmetric
     (``to_symmetric``, NeighborOverlap_large.py:63, ogbdataset.py:45), and so are A, P(A+I)P and
     D^-½(A+I)D^-½: the backward is the same kernel applied to the gradient.  A valued adjacency
     (DropAdj masks directed entries, so it is no longer symmetric) uses its transpose.  ``mean``
-    (D⁻¹A) has the transpose A D⁻¹; ``max`` is not differentiated here."""
+    (D⁻¹A, D = the forward's entry count per row, at least 1) has the transpose Aᵀ D⁻¹: the sum kernel over
+    Aᵀ (with its values) with ``pre`` = 1/count indexed by the original row.  ``max`` records the winning column id
+    per output feature in the forward (``ops.spmm_max_arg``; ties to the first maximum in row order) and hands each
+    gradient to its winner, times the entry value (``ops.spmm_max_backward`` over Aᵀ).  That record is N·F int32 per
+    max layer kept for the backward (241 MB at the collab shape, N = 235 868, F = 256)."""
 
     @staticmethod
     def forward(ctx, x, adj, kw):
         ctx.adj, ctx.kw = adj, kw
+        if kw.get("mode", "sum") == "max":
+            _plain_aggr(kw)
+            y, arg = ops.spmm_max_arg(adj._rowptr, adj._col, x, val=adj._value, n_cols=adj.sparse_sizes()[1])
+            ctx.save_for_backward(arg)
+            return y
         return ops.spmm_csr(adj._rowptr, adj._col, x, val=adj._value, **kw)
 
     @staticmethod
@@ -84,12 +98,19 @@ class _SpmmFn(torch.autograd.Function):
         adj, kw = ctx.adj, dict(ctx.kw)
         g = g.contiguous()
         mode = kw.get("mode", "sum")
+        n_rows, n_cols = adj.sparse_sizes()
+        if mode in ("mean", "max"):
+            _plain_aggr(kw)
         if mode == "max":
-            raise NotImplementedError("backward of max aggregation")
+            (arg,) = ctx.saved_tensors
+            at = adj.t() if (adj._value is not None or n_rows != n_cols) else adj
+            return ops.spmm_max_backward(at._rowptr, at._col, arg, g, val=at._value, n_cols=n_rows), None, None
+        if mode == "mean" and adj._value is not None:
+            cnt = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
+            at = adj.t()
+            return ops.spmm_csr(at._rowptr, at._col, g, pre=1.0 / cnt, mode="sum", val=at._value), None, None
         if adj._value is not None:
             adj = adj.t()
-            if mode == "mean":
-                raise NotImplementedError("backward of mean aggregation over a valued adjacency")
         if mode == "mean":
             deg = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
             return ops.spmm_csr(adj._rowptr, adj._col, g, pre=1.0 / deg, mode="sum"), None, None

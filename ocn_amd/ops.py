@@ -661,6 +661,52 @@ def spmm_csr(rowptr: Tensor, col: Tensor, x: Tensor, pre: Optional[Tensor] = Non
 
 
 @_on_device
+def spmm_max_arg(rowptr: Tensor, col: Tensor, x: Tensor, val: Optional[Tensor] = None,
+                 n_cols: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """(y, arg): y = the max aggregation of ``spmm_csr(mode="max")`` (valued: max_k val_ik * x_k), arg [n, F] int32 = the
+    column id of each winner (first maximum in row order; -1 in an empty row) — what ``spmm_max_backward`` reads.
+    ``n_cols``: the operator's column count; x must have that many rows (every column id indexes a row of x)."""
+    _req(rowptr, torch.int64, "rowptr", 1); _req(col, torch.int32, "col", 1)
+    _req(x, torch.float32, "x", 2)
+    if n_cols is not None and x.shape[0] != n_cols:
+        raise ValueError(f"x has {x.shape[0]} rows, the operator {n_cols} columns")
+    n = rowptr.numel() - 1
+    if val is not None and _req(val, torch.float32, "val", 1).numel() != col.numel():
+        raise ValueError("val must have one entry per stored column")
+    if col.numel() == 0:                                  # no entries: every row is empty
+        return (torch.zeros(n, x.shape[1], dtype=torch.float32, device=x.device),
+                torch.full((n, x.shape[1]), -1, dtype=torch.int32, device=x.device))
+    y = torch.empty(n, x.shape[1], dtype=torch.float32, device=x.device)
+    arg = torch.empty(n, x.shape[1], dtype=torch.int32, device=x.device)
+    check(_lib.lib().ocn_spmm_csr_max_arg(ptr(rowptr), ptr(col), ptr(val), n, ptr(x), x.shape[1], ptr(y), ptr(arg),
+                                          stream_ptr()), "ocn_spmm_csr_max_arg")
+    return y, arg
+
+
+@_on_device
+def spmm_max_backward(rowptrT: Tensor, colT: Tensor, arg: Tensor, g: Tensor, val: Optional[Tensor] = None,
+                      n_cols: Optional[int] = None) -> Tensor:
+    """gx = the input gradient of ``spmm_max_arg``: gx[k] = Σ_{i: arg[i] == k} val_ik * g[i], over the CSR of Aᵀ
+    (rowptrT, colT, its values ``val``), in Aᵀ's row order (deterministic).  ``n_cols``: Aᵀ's column count (= A's rows);
+    arg and g must have that many rows (every column id of Aᵀ indexes a row of both)."""
+    _req(rowptrT, torch.int64, "rowptrT", 1); _req(colT, torch.int32, "colT", 1)
+    _req(arg, torch.int32, "arg", 2); _req(g, torch.float32, "g", 2)
+    if arg.shape != g.shape:
+        raise ValueError("arg and g must have the same shape")
+    if n_cols is not None and arg.shape[0] != n_cols:
+        raise ValueError(f"arg / g have {arg.shape[0]} rows, the transposed operator {n_cols} columns")
+    if val is not None and _req(val, torch.float32, "val", 1).numel() != colT.numel():
+        raise ValueError("val must have one entry per stored column")
+    n = rowptrT.numel() - 1
+    if colT.numel() == 0:
+        return torch.zeros(n, g.shape[1], dtype=torch.float32, device=g.device)
+    gx = torch.empty(n, g.shape[1], dtype=torch.float32, device=g.device)
+    check(_lib.lib().ocn_spmm_max_backward(ptr(rowptrT), ptr(colT), ptr(val), n, ptr(arg), ptr(g), g.shape[1], ptr(gx),
+                                           stream_ptr()), "ocn_spmm_max_backward")
+    return gx
+
+
+@_on_device
 def deg_rsqrt(rowptr: Tensor, add: float = 1.0, val: Optional[Tensor] = None) -> Tensor:
     _req(rowptr, torch.int64, "rowptr", 1)
     n = rowptr.numel() - 1

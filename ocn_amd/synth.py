@@ -17,6 +17,7 @@ from torch import Tensor
 # public OGB / Planetoid statistics; nnz = stored directed entries
 SHAPES = {
     "cora":      dict(n=2_708,     nnz=7_400,      max_deg=120,   feat=1433, clique_frac=0.3),
+    "citeseer":  dict(n=3_327,     nnz=9_104,      max_deg=99,    feat=3703, clique_frac=0.3),
     "collab":    dict(n=235_868,   nnz=2_360_000,  max_deg=671,   feat=128,  clique_frac=0.6),
     "ppa":       dict(n=576_289,   nnz=42_500_000, max_deg=3_241, feat=58,   clique_frac=0.3),
     "citation2": dict(n=2_927_963, nnz=60_000_000, max_deg=10_000, feat=128, clique_frac=0.2),
