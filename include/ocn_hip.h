@@ -36,7 +36,8 @@ extern "C" {
  *    ocn_gather_schedule a segment; + ocn_cn_gather3_backward, ocn_cn_gather_backward_det_lists, ocn_ln_drop_relu_*.
  * 9: + ocn_heads_small_batch (ocn_heads_fused picks its small-batch form by the batch size; same bits), ocn_spgemm_bit_rows
  *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
- *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val). */
+ *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
+ *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -101,6 +102,12 @@ int ocn_batch_prep(const int64_t* rowptrA, const int64_t* src, int64_t B, int64_
                    int32_t n_zero, void* stream);
 int ocn_order_by_node_finish(const int64_t* node, int64_t B, int64_t n_nodes, int64_t* order, void* workspace,
                              void* stream);
+/* ocn_order_by_node_finish for the pattern route's intersection pass: the scatter that gives a batch row its slot also
+ * writes the slot's record (ocn_cn_flags `rec`): words 0 - 2 complete, word 3 = off[e] (`off` as ocn_batch_prep /
+ * ocn_edge_offsets left it, on the same stream).  ocn_cn_flags_rec then starts every slot from that one 32-byte load. */
+int ocn_order_by_node_finish_rec(const int64_t* node /* src */, const int64_t* dst, const int64_t* rowptrA,
+                                 const int64_t* off, int64_t B, int64_t n_nodes, int64_t* order, uint64_t* rec /* [B][4] */,
+                                 void* workspace, void* stream);
 
 /* Forward work-item offsets of the walk route: out[slot] = number of items of the earlier processing
  * slots, out[B] = number of items.  A batch row's items are groups of consecutive chunks of
@@ -156,6 +163,18 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA,
                  int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
                  uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
                  int32_t* status, uint64_t* rec /* [B][4] or NULL */, int32_t* gcost /* [ceil(B/4)] or NULL */, void* stream);
+/* The same pass behind ocn_order_by_node_finish_rec: `order` and `rec` are required, the records arrive with words 0 - 2
+ * and the offset written and leave as ocn_cn_flags leaves them; src / dst / rowptrA are then not read per slot.  Every
+ * output is identical to ocn_cn_flags' on the same arguments. */
+int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA,
+                     const int64_t* rowptrT1, const int32_t* colT1,
+                     const int64_t* rowptrT2, const int32_t* colT2,
+                     const uint32_t* bitmapT1 /* or NULL */, int64_t bm1_stride_words,
+                     const uint32_t* bitmapT2 /* or NULL */, int64_t bm_stride_words,
+                     const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
+                     int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
+                     uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
+                     int32_t* status, uint64_t* rec /* [B][4] */, int32_t* gcost /* [ceil(B/4)] or NULL */, void* stream);
 
 /* The pygho route get_cn1_cn2 (NeighborOverlap_large_ppa.py:147-173, NeighborOverlapCitation2.py:
  * 78-104) without forming Ej·A: cn1 = N(i) ∩ N(j) as above; cn2[e,k] = |N(k) ∩ N(j)| (number of

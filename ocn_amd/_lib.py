@@ -31,9 +31,12 @@ SIGNATURES = {
     "ocn_order_workspace_bytes": (c_int64, [c_int64]),
     "ocn_order_by_node": (c_int32, [_P, c_int64, c_int64, _P, _P, _P]),
     "ocn_order_by_node_finish": (c_int32, [_P, c_int64, c_int64, _P, _P, _P]),
+    "ocn_order_by_node_finish_rec": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P]),
     "ocn_batch_prep": (c_int32, [_P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, c_int32, _P]),
     "ocn_cn_flags": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P,
                                _P, _P, _P, _P, _P, _P]),
+    "ocn_cn_flags_rec": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P,
+                                   _P, _P, _P, _P, _P, _P]),
     "ocn_chunk_offsets": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P]),
     "ocn_walk_chunk": (c_int32, []),
     "ocn_cn_walk_flags": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P,

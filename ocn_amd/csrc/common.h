@@ -15,6 +15,7 @@ typedef unsigned long long u64;
 // instead of three 32-bit ones), walks = sum of the walk counts of column c (valued cn2 only).
 #define HF_BITS 21
 #define HF_MASK ((1ull << HF_BITS) - 1ull)
+#define REC_LEN_SHIFT 40                     /* slot record word 2 (ocn_hip.h: ocn_cn_flags `rec`): row start (nnz < 2^40) | row length << 40 */
 __device__ __forceinline__ int hf_n1(u64 w) { return (int)(w & HF_MASK); }
 __device__ __forceinline__ int hf_n2(u64 w) { return (int)((w >> HF_BITS) & HF_MASK); }
 __device__ __forceinline__ int hf_nu(u64 w) { return (int)((w >> (2 * HF_BITS)) & HF_MASK); }

@@ -282,6 +282,29 @@ __global__ __launch_bounds__(OCN_BLOCK) void order_scatter(const i64* __restrict
   }
 }
 
+// The same scatter for the pattern route's intersection pass: the row that learns its slot also writes the slot's record
+// (ocn_hip.h: ocn_cn_flags `rec`) — batch row, both endpoints, the source row's extent and the flag offset (word 3, which
+// the intersection pass completes with its count bits).  That pass then starts from ONE 32-byte load instead of the chain
+// order -> src / dst -> rowptr / off.  `off` comes from the prep launch in front of this one; a poisoned offset scan leaves
+// words the intersection pass does not trust (it tests off[B] itself).
+__global__ __launch_bounds__(OCN_BLOCK) void order_scatter_rec(const i64* __restrict__ node, const i64* __restrict__ dst,
+                                                               const i64* __restrict__ rowptrA, const i64* __restrict__ off, i64 B,
+                                                               unsigned long long* __restrict__ cursor, const i64* __restrict__ total,
+                                                               i64* __restrict__ order, int32_t* __restrict__ counts,
+                                                               u64* __restrict__ rec) {
+  const bool poisoned = total[0] < 0;
+  for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < B; e += (i64)gridDim.x * blockDim.x) {
+    const i64 v = node[e], j = dst[e];
+    const i64 a0 = rowptrA[v], da = rowptrA[v + 1] - a0, base = off[e];
+    const i64 slot = poisoned ? e : (i64)atomicAdd(cursor + v, 1ull);
+    order[slot] = e;
+    counts[v] = 0;
+    ulonglong2* r = reinterpret_cast<ulonglong2*>(rec + 4 * slot);
+    r[0] = make_ulonglong2((u64)e, (u64)v | ((u64)j << 32));
+    r[1] = make_ulonglong2((u64)a0 | ((u64)da << REC_LEN_SHIFT), (u64)base);
+  }
+}
+
 __global__ __launch_bounds__(OCN_BLOCK) void check_edges_kernel(const i64* __restrict__ src, const i64* __restrict__ dst,
                                                                i64 B, i64 n_src, i64 n_dst, int32_t* __restrict__ bad) {
   bool b = false;
@@ -371,6 +394,25 @@ int ocn_order_by_node_finish(const int64_t* node, int64_t B, int64_t n_nodes, in
   if (rc) return rc;
   hipLaunchKernelGGL(order_scatter, dim3(grid), dim3(OCN_BLOCK), 0, st, (const i64*)node, (i64)B,
                      (unsigned long long*)offs, (const i64*)(offs + n_nodes), (i64*)order, counts);
+  return launch_status();
+}
+
+int ocn_order_by_node_finish_rec(const int64_t* node, const int64_t* dst, const int64_t* rowptrA, const int64_t* off,
+                                 int64_t B, int64_t n_nodes, int64_t* order, uint64_t* rec, void* workspace, void* stream) {
+  if (B < 0 || n_nodes <= 0) return OCN_EINVAL;
+  if (B == 0) return 0;
+  if (!node || !dst || !rowptrA || !off || !order || !rec || !workspace) return OCN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* counts = (int32_t*)workspace;
+  i64* offs = (i64*)((char*)workspace + order_counts_bytes(n_nodes));
+  void* scan_ws = (void*)(offs + n_nodes + 1);
+  const int grid = grid_for((B + OCN_BLOCK - 1) / OCN_BLOCK, 1024);
+  I32In op{counts};
+  int rc = run_scan(op, (i64)n_nodes, offs, scan_ws, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(order_scatter_rec, dim3(grid), dim3(OCN_BLOCK), 0, st, (const i64*)node, (const i64*)dst,
+                     (const i64*)rowptrA, (const i64*)off, (i64)B, (unsigned long long*)offs, (const i64*)(offs + n_nodes),
+                     (i64*)order, counts, (u64*)rec);
   return launch_status();
 }
 

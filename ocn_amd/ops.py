@@ -291,7 +291,14 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     zb = (ctypes.c_int64 * len(zs))(*[t.numel() * t.element_size() for t in zs])
     check(_lib.lib().ocn_batch_prep(ptr(rowptrA), ptr(src), B, ptr(off), ptr(sws), n_src, ptr(ows), zp, zb, len(zs),
                                     stream_ptr()), "ocn_batch_prep")
-    if want_order:
+    rec_in = want_order and rec is not None and not walk      # the scatter that orders the batch starts the slot records too
+    if rec_in:
+        _req(dst, torch.int64, "dst", 1)
+        if _req(rec, torch.int64, "rec").numel() < 4 * B:
+            raise ValueError("rec: int64 [B, 4]")
+        check(_lib.lib().ocn_order_by_node_finish_rec(ptr(src), ptr(dst), ptr(rowptrA), ptr(off), B, n_src, ptr(order), ptr(rec),
+                                                      ptr(ows), stream_ptr()), "ocn_order_by_node_finish_rec")
+    elif want_order:
         check(_lib.lib().ocn_order_by_node_finish(ptr(src), B, n_src, ptr(order), ptr(ows), stream_ptr()),
               "ocn_order_by_node_finish")
     bound = B * max(int(max_deg_a), 0)
@@ -329,7 +336,7 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
             _req(t1_bitmap, torch.int32, "t1_bitmap", 2)
             if t1_bitmap.shape[0] != t1[0].numel() - 1 or t1_bitmap.shape[1] * 32 < n_cols:
                 raise ValueError("t1_bitmap does not match the T1 adjacency")
-        check(_lib.lib().ocn_cn_flags(ptr(rowptrA), ptr(colA), ptr(t1[0]), ptr(t1[1]),
+        check((_lib.lib().ocn_cn_flags_rec if rec_in else _lib.lib().ocn_cn_flags)(ptr(rowptrA), ptr(colA), ptr(t1[0]), ptr(t1[1]),
                                       ptr(t2[0] if t2 else None), ptr(t2[1] if t2 else None),
                                       ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
                                       ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
