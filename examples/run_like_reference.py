@@ -118,6 +118,11 @@ def main(argv=None):
     ap.add_argument("--feat", type=int, default=0, help="feature width override for the synthetic x")
     ap.add_argument("--gnnedp", type=float, default=0.0, help="DropAdj probability of the encoder's adjacency (train only)")
     ap.add_argument("--res", action="store_true", help="residual connections in the encoder")
+    # forwarded to the predictor for cn8 only, as the reference driver does (NeighborOverlap_large.py:210-214, 275-276)
+    ap.add_argument("--beta", type=float, default=1)
+    ap.add_argument("--use_xlin", action="store_true")
+    ap.add_argument("--tailact", action="store_true")
+    ap.add_argument("--twolayerlin", action="store_true")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
@@ -129,8 +134,9 @@ def main(argv=None):
     fin = args.hiddim if data.max_x >= 0 else data.x.shape[1]
     model = GCN(fin, args.hiddim, args.hiddim, args.mplayers, 0.05, True, args.res, data.max_x, args.model, True, args.gnnedp,
                 xdropout=0.3, taildropout=0.1).to(dev)
-    predictor = predictor_dict[args.predictor](args.hiddim, args.hiddim, 1, args.nnlayers, 0.05, 0.0, True,
-                                               use_xlin=True, tailact=True).to(dev)
+    heads = (dict(use_xlin=args.use_xlin, tailact=args.tailact, twolayerlin=args.twolayerlin, beta=args.beta)
+             if args.predictor == "cn8" else dict(use_xlin=True, tailact=True))
+    predictor = predictor_dict[args.predictor](args.hiddim, args.hiddim, 1, args.nnlayers, 0.05, 0.0, True, **heads).to(dev)
     optimizer = torch.optim.Adam([{'params': model.parameters(), "lr": args.gnnlr},
                                   {'params': predictor.parameters(), 'lr': args.prelr}])
     out = []

@@ -37,7 +37,7 @@ extern "C" {
  * 9: + ocn_heads_small_batch (ocn_heads_fused picks its small-batch form by the batch size; same bits), ocn_spgemm_bit_rows
  *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
  *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
- *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass). */
+ *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool. */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -301,6 +301,26 @@ int ocn_cn_gather(const int64_t* rowptrA, const int32_t* colA,
                   const int32_t* cnt1, const int32_t* cnt2, const uint64_t* rec /* or NULL */,
                   const int32_t* perm /* ocn_gather_schedule's, or NULL */, const float* rowsum /* or NULL */,
                   void* stream);
+/* cn8 (CNLinkPredictorbaselearnablation, model.py:3233-3449; pattern route): intersection and pooling in ONE pass.  cn8
+ * pools without column weights, so a candidate's vectors depend on nothing but the candidate:
+ *   xcn1[e] = sum_{k in N(i) ∩ T1(j)} h[k]   xcn2[e] = sum_{k in N(i) ∩ T2(j)} h[k]   xij[e] = h[i] (.) h[j]
+ * for e = (i, j) = (src[e], dst[e]).  N(i) (row i of A) is walked in ascending column order by one lane group, hub rows
+ * included, and every member's row is added at once: one fp32 add per feature and entry, in that order — the order of a
+ * sequential spmm over the sorted row.  cnt1[e] / cnt2[e] = the number of members (int32).  A candidate without members
+ * gets zero rows and zero counts.  No flag bytes, no histogram and no weights are written or read.
+ * T1 / T2: dense bit rows (row j at bitmap + j * stride words, bit k = column k, stride * 32 >= n_cols) where given, else
+ * the CSR row j (sorted columns); at least one form of each is required.  order: as for ocn_cn_flags (or NULL).
+ * h is [n_cols][H] row-major fp32, H in {16, 32, 64, 128, 256, 512}; outputs [B][H], indexed by the batch row.
+ * NULL pointers, B < 0, another H, a matrix with neither form or bit rows too short: OCN_EINVAL before any HIP call. */
+int ocn_cn8_pool(const int64_t* rowptrA, const int32_t* colA,
+                 const int64_t* rowptrT1 /* or NULL */, const int32_t* colT1 /* or NULL */,
+                 const int64_t* rowptrT2 /* or NULL */, const int32_t* colT2 /* or NULL */,
+                 const uint32_t* bitmapT1 /* or NULL */, int64_t bm1_stride_words,
+                 const uint32_t* bitmapT2 /* or NULL */, int64_t bm2_stride_words,
+                 const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
+                 const float* h, int32_t H, float* xcn1, float* xcn2, float* xij,
+                 int32_t* cnt1, int32_t* cnt2, void* stream);
+
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the
  * collab shape).  perm[] = inside each XCD's contiguous eighth of the groups, the groups stable-sorted by descending cost:

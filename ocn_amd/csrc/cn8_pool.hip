@@ -1,0 +1,177 @@
+// cn8 (CNLinkPredictorbaselearnablation, model.py:3233-3449): intersection and pooling of a candidate batch in ONE pass.
+// cn8's pooled vectors carry no column weight — xcn1 = sum of h[k] over N(i) ∩ N(j), xcn2 = the same over N(i) ∩ T2(j) —
+// so nothing of a candidate's score depends on the rest of the batch: no flag bytes, no histogram, no weights buffer.
+// See include/ocn_hip.h (ocn_cn8_pool).
+#include "common.h"
+
+// membership of key in the sorted row a[0..n) (memory): the lanes of a group search the same row, so the top of the
+// tree is shared cache lines
+__device__ __forceinline__ bool cn8_row_has(const int32_t* __restrict__ a, i64 n, int32_t key) {
+  i64 lo = 0, hi = n;
+  bool found = false;
+  while (lo < hi) {
+    const i64 mid = (lo + hi) >> 1;
+    const int32_t v = a[mid];
+    found |= (v == key);
+    if (v < key) lo = mid + 1; else hi = mid;
+  }
+  return found;
+}
+
+constexpr int CN8_UNR = 4;      // embedding rows in flight per lane group
+
+// LPE lanes cooperate on one candidate (64 / LPE candidates per wave); a lane owns NV float4 of the H = LPE * NV * 4
+// features.  A round tests LPE * PT positions of the source row N(i) — one membership probe pair per lane and position —
+// and then adds the rows of the members, position by position in ascending order, into the two accumulators: one fp32
+// add per feature and entry, the order of a sequential spmm over the sorted row.  A hub row is walked by the same group
+// in the same order (it only takes more rounds).
+template <int LPE, int NV>
+__global__ __launch_bounds__(OCN_BLOCK) void cn8_pool_kernel(
+    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+    const i64* __restrict__ rowptrT1, const int32_t* __restrict__ colT1,
+    const i64* __restrict__ rowptrT2, const int32_t* __restrict__ colT2,
+    const unsigned* __restrict__ bmT1, i64 bm1_stride, const unsigned* __restrict__ bmT2, i64 bm2_stride,
+    const i64* __restrict__ src, const i64* __restrict__ dst, const i64* __restrict__ order, i64 B,
+    const float* __restrict__ h, int H, float* __restrict__ xcn1, float* __restrict__ xcn2, float* __restrict__ xij,
+    int32_t* __restrict__ cnt1, int32_t* __restrict__ cnt2) {
+  constexpr int GPW = OCN_WAVE / LPE;
+  constexpr int PT = GPW < 8 ? GPW : 8;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane % LPE;
+  const int gbase = lane - gl;
+  // workgroups are dealt round-robin over the 8 XCDs: every XCD takes one contiguous eighth of the processing order
+  // (candidates with neighbouring sources then share an L2), as the pooling of cn5 / cn7 does
+  i64 bid = blockIdx.x;
+  if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+  const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  if (slot >= B) return;                    // whole group leaves together
+  const i64 e = order ? order[slot] : slot;
+  const i64 i = src[e], j = dst[e];
+  const i64 a0 = rowptrA[i], da = rowptrA[i + 1] - a0;
+  const unsigned* bm1_row = bmT1 ? bmT1 + j * bm1_stride : nullptr;
+  const unsigned* bm2_row = bmT2 ? bmT2 + j * bm2_stride : nullptr;
+  i64 b0 = 0, db = 0, c0 = 0, dc = 0;
+  if (!bmT1) { b0 = rowptrT1[j]; db = rowptrT1[j + 1] - b0; }
+  if (!bmT2) { c0 = rowptrT2[j]; dc = rowptrT2[j + 1] - c0; }
+  const float4* h4 = reinterpret_cast<const float4*>(h);
+  const i64 rowq = H >> 2;                  // float4 per row
+  f32x4 acc1[NV], acc2[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc1[v] = acc2[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int c1 = 0, c2 = 0;
+  for (i64 p0 = 0; p0 < da; p0 += LPE * PT) {
+    int32_t k[PT];
+    unsigned f[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      const i64 p = p0 + t * LPE + gl;
+      k[t] = p < da ? colA[a0 + p] : -1;
+    }
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      f[t] = 0;
+      if (k[t] >= 0) {
+        const bool f1 = bm1_row ? ((bm1_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : cn8_row_has(colT1 + b0, db, k[t]);
+        const bool f2 = bm2_row ? ((bm2_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : cn8_row_has(colT2 + c0, dc, k[t]);
+        f[t] = (f1 ? OCN_F_CN1 : 0u) | (f2 ? OCN_F_CN2 : 0u);
+        c1 += f1;
+        c2 += f2;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {             // ascending position order: tile t, then lane
+      unsigned long long m = __ballot(f[t] != 0);
+      if (LPE < 64) m = (m >> gbase) & ((1ull << (LPE & 63)) - 1ull);
+      while (m) {
+        int bsel[CN8_UNR];
+#pragma unroll
+        for (int u = 0; u < CN8_UNR; ++u) {
+          bsel[u] = m ? (__ffsll((long long)m) - 1) : -1;
+          m &= m - 1;                          // no-op once m == 0
+        }
+        unsigned ff[CN8_UNR];
+        float4 x[CN8_UNR][NV];
+#pragma unroll
+        for (int u = 0; u < CN8_UNR; ++u) {
+          const int sl = gbase + (bsel[u] < 0 ? 0 : bsel[u]);
+          const int32_t kk = __shfl(k[t], sl, OCN_WAVE);
+          ff[u] = bsel[u] < 0 ? 0u : (unsigned)__shfl((int)f[t], sl, OCN_WAVE);
+          if (bsel[u] >= 0) {
+            const float4* row = h4 + (i64)kk * rowq + gl;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < CN8_UNR; ++u) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            const f32x4 xv = {x[u][v].x, x[u][v].y, x[u][v].z, x[u][v].w};
+            if (ff[u] & OCN_F_CN1) acc1[v] = acc1[v] + xv;
+            if (ff[u] & OCN_F_CN2) acc2[v] = acc2[v] + xv;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = LPE / 2; o > 0; o >>= 1) {
+    c1 += __shfl_xor(c1, o, OCN_WAVE);
+    c2 += __shfl_xor(c2, o, OCN_WAVE);
+  }
+  if (gl == 0) { cnt1[e] = c1; cnt2[e] = c2; }
+  const float4* hi = h4 + i * rowq + gl;
+  const float4* hj = h4 + j * rowq + gl;
+  float4* o1 = reinterpret_cast<float4*>(xcn1) + e * rowq + gl;
+  float4* o2 = reinterpret_cast<float4*>(xcn2) + e * rowq + gl;
+  float4* o3 = reinterpret_cast<float4*>(xij) + e * rowq + gl;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const float4 a = hi[v * LPE], b = hj[v * LPE];
+    o1[v * LPE] = make_float4(acc1[v].x, acc1[v].y, acc1[v].z, acc1[v].w);
+    o2[v * LPE] = make_float4(acc2[v].x, acc2[v].y, acc2[v].z, acc2[v].w);
+    o3[v * LPE] = make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
+  }
+}
+
+extern "C" {
+
+int ocn_cn8_pool(const int64_t* rowptrA, const int32_t* colA,
+                 const int64_t* rowptrT1, const int32_t* colT1,
+                 const int64_t* rowptrT2, const int32_t* colT2,
+                 const uint32_t* bitmapT1, int64_t bm1_stride_words,
+                 const uint32_t* bitmapT2, int64_t bm2_stride_words,
+                 const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B, int64_t n_cols,
+                 const float* h, int32_t H, float* xcn1, float* xcn2, float* xij,
+                 int32_t* cnt1, int32_t* cnt2, void* stream) {
+  if (B < 0 || n_cols < 0) return OCN_EINVAL;
+  if (H != 16 && H != 32 && H != 64 && H != 128 && H != 256 && H != 512) return OCN_EINVAL;
+  if (!rowptrA || !colA || !src || !dst || !h || !xcn1 || !xcn2 || !xij || !cnt1 || !cnt2) return OCN_EINVAL;
+  if (!bitmapT1 && !(rowptrT1 && colT1)) return OCN_EINVAL;
+  if (!bitmapT2 && !(rowptrT2 && colT2)) return OCN_EINVAL;
+  if (bitmapT1 && bm1_stride_words * 32 < n_cols) return OCN_EINVAL;
+  if (bitmapT2 && bm2_stride_words * 32 < n_cols) return OCN_EINVAL;
+  if (B == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_CN8(LPE, NV)                                                                                        \
+  do {                                                                                                             \
+    const i64 epb = (i64)OCN_WPB * (OCN_WAVE / LPE);                                                               \
+    hipLaunchKernelGGL((cn8_pool_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,  \
+                       (const i64*)rowptrA, colA, (const i64*)rowptrT1, colT1, (const i64*)rowptrT2, colT2,        \
+                       (const unsigned*)bitmapT1, (i64)bm1_stride_words, (const unsigned*)bitmapT2,                \
+                       (i64)bm2_stride_words, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B, h,      \
+                       (int)H, xcn1, xcn2, xij, cnt1, cnt2);                                                       \
+  } while (0)
+  switch (H) {
+    case 16: LAUNCH_CN8(4, 1); break;
+    case 32: LAUNCH_CN8(8, 1); break;
+    case 64: LAUNCH_CN8(16, 1); break;
+    case 128: LAUNCH_CN8(32, 1); break;
+    case 256: LAUNCH_CN8(64, 1); break;
+    default: LAUNCH_CN8(64, 2); break;
+  }
+#undef LAUNCH_CN8
+  return launch_status();
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 """Drop-in for the hot-path classes of the reference's ``model.py``.
 
 Exports ``predictor_dict`` (``cn5`` = CNLinkPredictorOringin, model.py:2171-2443; ``cn7`` =
-CNLinkPredictorbaselearn, model.py:3021-3229), ``convdict`` / ``convdict2`` / ``convdict3``,
+CNLinkPredictorbaselearn, model.py:3021-3229; ``cn8`` = CNLinkPredictorbaselearnablation, model.py:3233-3449), ``convdict`` / ``convdict2`` / ``convdict3``,
 ``GCN`` / ``GCN2`` / ``GCN3`` (model.py:232-511), ``PureConv*``, ``DropAdj``, ``DropEdge`` with the
 reference's constructor signatures and ``state_dict`` key layout, so checkpoints and the unchanged
 drivers work.  The sparse arithmetic runs in libocn_hip.so (no torch_sparse / pygho / PyG); in eval the
@@ -1165,6 +1165,68 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
         return self.multidomainforward(x, adj, cn1, cn2, tar_ei, filled1, [])
 
 
+class CNLinkPredictorbaselearnablation(_CNPredictorBase):
+    """cn8 (model.py:3233-3449): cn7 without the normalisation — the raw cn1 and the raw cn2 (1.0, or the 2-walk counts of
+    ``get_cn1_cn2``) are pooled as they are (:3340, :3395; the column sums in front are dead code, the diagonal is T0 = I);
+    same heads, same mix.  ``args.sum`` is read and has no effect; ``innerprod`` and ``n`` are never touched.  No quantity
+    of a candidate depends on the rest of the batch.  The pools run through the flag pass and the pooling of cn5 / cn7 with the
+    unit weights {1, 0, 1, 0} per column, whose transpose is the backward: autograd on, training mode, the walk route, explicit
+    [B, N] matrices — and eval too by default.  With ``ops.cn8_fused_eval`` (``OCN_CN8_FUSED=1``) eval on ``adjoverlap`` handles
+    intersects and pools in ONE pass instead (``ocn_cn8_pool``: no flags, no histogram, no weights; same bits; opt-in until it is
+    measured against the chain).  An edge-sharded cn8 exchanges nothing."""
+    _xcn2_on_union = False
+
+    def _fused_state(self, x, cn1, cn2, tar_ei, ws):
+        """The one-pass batch state where it applies (eval, no grad, pattern handles, a width the kernel has), else None."""
+        if (not ops.cn8_fused_eval or self.training or torch.is_grad_enabled() or not torch.is_tensor(x) or x.dim() != 2
+                or x.dtype != torch.float32 or x.shape[1] not in ops.LN_WIDTHS):
+            return None
+        from .utils import fuse8
+        st = fuse8(cn1, cn2, tar_ei, ws)
+        if st is not None:
+            st.cls, st._cls_decided = None, True       # (the class order needs the counts this pass itself produces: batch order)
+        return st
+
+    def multidomainforward(self, x, adj, cn1, cn2, tar_ei, args, filled1: bool = False,
+                           cndropprobs: Iterable[float] = []):
+        getattr(args, "sum", None)                     # model.py:3332, 3388: read, multiplied into a matrix that is then dropped
+        st = self._fused_state(x, cn1, cn2, tar_ei, self._scratch(x))
+        if st is not None:
+            xcn1, xcn2, xij = st.pool(x.contiguous())
+            return self._heads(x, xcn1, xcn2, xij, None)
+        st = fuse(cn1, cn2, tar_ei, self._scratch(x), adj=adj)
+        xcn1, xcn2, xij = self._pool(st, self._weights(st, args), x)
+        return self._heads(x, xcn1, xcn2, xij, getattr(st, "cls", None))
+
+    def _weights(self, st, args):
+        return ops.unit_weights(st.N, st.src.device)
+
+    def begin(self, x, adj, cn1, cn2, tar_ei, slot: int = 0, args=None):
+        """Phase A: the one-pass pooling (pattern handles), or the flag pass, the class order and the pooling with unit
+        weights (walk route).  No collective, sharded or not: there is nothing to exchange."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("begin / finish is the no-grad scoring path: call .eval() under torch.no_grad()")
+        n_sets = max(2, int(ops.overlap_depth), int(ops.overlap_depth_small))
+        if len(getattr(self, "_ws_slots", ())) != n_sets:
+            self._ws_slots = [dict() for _ in range(n_sets)]
+        ws = self._ws_slots[slot % n_sets]
+        st = self._fused_state(x, cn1, cn2, tar_ei, ws)
+        if st is not None:
+            st.pooled = st.pool(x.contiguous())
+            return st, None, None
+        st = fuse(cn1, cn2, tar_ei, ws, adj=adj)
+        w = self._weights(st, args)
+        if ops.phase_a_extras:
+            self._class_order(st, x)
+            st.prepare_schedule(x.shape[1])
+            if ops.phase_a_pool:
+                st.pooled = self._pool(st, w, x)
+        return st, None, w
+
+    def forward(self, x, adj, cn1, cn2, tar_ei, filled1: bool = False):
+        return self.multidomainforward(x, adj, cn1, cn2, tar_ei, filled1, [])
+
+
 class CNLinkPredictor3hopCNs(_CNPredictorBase):
     """cn6 (model.py:2445-2951): the 3-hop predictor.  cn1 / cn2 as cn5; cn3 = N(i) ∩ N³(j) is
     orthogonalised against BOTH normalised matrices and column-normalised; a fourth head ``xcn3lin`` and
@@ -1222,4 +1284,5 @@ predictor_dict = {
     "cn5": CNLinkPredictorOringin,
     "cn6": CNLinkPredictor3hopCNs,
     "cn7": CNLinkPredictorbaselearn,
+    "cn8": CNLinkPredictorbaselearnablation,
 }

@@ -508,6 +508,95 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
     return out[0], out[1], out[2]
 
 
+_unit_w: dict = {}
+
+
+def unit_weights(n: int, device) -> Tensor:
+    """Column weights {1, 0, 1, 0} for every column (float32 [n, 4], cached per size and device): with them the pooling
+    forms w1 = [cn1] and w2 = [cn2] * v — cn8's unnormalised pools — and its transpose the matching gradient."""
+    key = (int(n), str(device))
+    w = _unit_w.get(key)
+    if w is None:
+        if len(_unit_w) > 8:
+            _unit_w.clear()
+        w = _unit_w[key] = torch.tensor([1.0, 0.0, 1.0, 0.0], device=device).repeat(int(n), 1).contiguous()
+    return w
+
+
+@_on_device
+def order_by_node(node: Tensor, n_nodes: int, wsd=None) -> Tensor:
+    """A stable processing order of the batch rows by node id (ocn_hip.h: ocn_order_by_node) — the order ``cn_flags`` forms for
+    itself through ocn_batch_prep / ocn_order_by_node_finish, for a pass that has no offsets to scan.  It uses the scratch names
+    ``order`` / ``order_ws`` of ``cn_flags`` on purpose: a scratch set serves one batch state at a time (a predictor's slot runs
+    either the flag pass or the one-pass cn8 pooling for a batch, never both), the shapes agree and the workspace is left zero."""
+    _req(node, torch.int64, "node", 1)
+    B = node.numel()
+    order = buf(wsd, "order", B, torch.int64, node.device)
+    ows = buf(wsd, "order_ws", int(_lib.lib().ocn_order_workspace_bytes(n_nodes)) // 8 + 1, torch.int64, node.device, zero_init=True)
+    check(_lib.lib().ocn_order_by_node(ptr(node), B, int(n_nodes), ptr(order), ptr(ows), stream_ptr()), "ocn_order_by_node")
+    return order
+
+
+# cn8 in eval on adjoverlap handles: ocn_cn8_pool when on, else flags -> unit weights -> the pooling of cn5 / cn7.  OFF by default:
+# the one pass is built and tested bit-equal, but it gives up the chain's longest-first schedule and class-major head rows, and the
+# default goes to it only on a measurement that shows its range below the chain's (DESIGN.md section 4, cn8; tools/cn8bench.py).
+cn8_fused_eval = os.environ.get("OCN_CN8_FUSED", "0") == "1"
+
+
+@_on_device
+def cn8_pool(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor], Optional[Tensor]]],
+             t2: Optional[Tuple[Optional[Tensor], Optional[Tensor]]], src: Tensor, dst: Tensor, h: Tensor,
+             t1_bitmap: Optional[Tensor] = None, t2_bitmap: Optional[Tensor] = None, order: Optional[Tensor] = None, wsd=None,
+             n_cols: Optional[int] = None):
+    """cn8's intersection and pooling in one pass (ocn_hip.h: ocn_cn8_pool; pattern route).  ``t1`` / ``t2`` = (rowptr, col)
+    of the matrices whose rows ``dst`` are intersected with N(src), and / or their dense bit rows; ``order``: an optional
+    processing order (a permutation of the batch rows); ``n_cols``: the column count of A, T1 and T2 (default: the rows of
+    ``h``, which it must equal — every column id indexes a row of h).  T1 and T2 must have the same number of rows, whichever
+    form they come in: ``dst`` is bounds-checked against it.  Returns (xcn1, xcn2, xij [B, H], cnt1, cnt2 int32 [B])."""
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
+    _req(h, torch.float32, "h", 2)
+    B, (N, H) = src.numel(), h.shape
+    if dst.numel() != B:
+        raise ValueError("src/dst length mismatch")
+    if H not in LN_WIDTHS:
+        raise NotImplementedError(f"cn8 pooling supports hidden widths {LN_WIDTHS}, got {H}")
+    if n_cols is not None and int(n_cols) != N:
+        raise ValueError(f"h has {N} rows, the adjacency {int(n_cols)} columns")
+    csr, n_rows = [], []
+    for t, bm, nm in ((t1, t1_bitmap, "T1"), (t2, t2_bitmap, "T2")):
+        rp, col = (None, None) if t is None else t
+        if rp is None or col is None:
+            if bm is None:
+                raise ValueError(f"{nm}: needs its CSR arrays or its bit rows")
+            rp = col = None
+        else:
+            _req(rp, torch.int64, "rowptr" + nm, 1); _req(col, torch.int32, "col" + nm, 1)
+        if bm is not None:
+            _req(bm, torch.int32, nm.lower() + "_bitmap", 2)
+            if (rp is not None and bm.shape[0] != rp.numel() - 1) or bm.shape[1] * 32 < N:
+                raise ValueError(f"{nm.lower()}_bitmap does not match the {nm} adjacency")
+        csr.append((rp, col))
+        n_rows.append(rp.numel() - 1 if rp is not None else bm.shape[0])
+    if n_rows[0] != n_rows[1]:                     # (the kernel indexes both with dst: one bound must hold for both)
+        raise ValueError(f"T1 has {n_rows[0]} rows, T2 {n_rows[1]}")
+    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
+        raise ValueError("order: one entry per candidate")
+    check_edges(src, dst, rowptrA.numel() - 1, n_rows[0])
+    out = buf(wsd, "pooled", (3, B, H), torch.float32, h.device)
+    cnt = buf(wsd, "cn8_cnt", (2, B), torch.int32, h.device)
+    if B == 0:
+        return out[0], out[1], out[2], cnt[0], cnt[1]
+    _mark("cn_prep")
+    check(_lib.lib().ocn_cn8_pool(ptr(rowptrA), ptr(colA), ptr(csr[0][0]), ptr(csr[0][1]), ptr(csr[1][0]), ptr(csr[1][1]),
+                                  ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
+                                  ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
+                                  ptr(src), ptr(dst), ptr(order), B, N, ptr(h), H, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                  ptr(cnt[0]), ptr(cnt[1]), stream_ptr()), "ocn_cn8_pool")
+    _mark("cn8_pool")
+    return out[0], out[1], out[2], cnt[0], cnt[1]
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 

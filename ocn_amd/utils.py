@@ -345,6 +345,56 @@ def fuse(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None, adj: Optional[Spar
     return CNState(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, ws=ws)
 
 
+class CN8State:
+    """A cn8 batch on the pattern route: cn8 pools without column weights, so the batch needs no flags, histogram or
+    weights — only the operands of ``ops.cn8_pool`` (intersection and pooling in one pass).  ``pool(h)`` runs it and leaves
+    the integer CN counts in ``cnt1`` / ``cnt2``."""
+
+    def __init__(self, adj: SparseTensor, t1: SparseTensor, t2: SparseTensor, tarei: Tensor, ws: Optional[dict] = None):
+        if tarei.dim() != 2 or tarei.shape[0] != 2:
+            raise ValueError("tarei must be [2, B]")
+        for t in (t1, t2):
+            if t.sparse_sizes() != adj.sparse_sizes():
+                raise ValueError("adjoverlap: adjacency sizes differ")    # utils.py:164 assert
+        self.adj, self.t1, self.t2, self.ws = adj, t1, t2, ws
+        self.src = tarei[0].to(torch.int64).contiguous()
+        self.dst = tarei[1].to(torch.int64).contiguous()
+        self.B, self.N = self.src.numel(), adj.size(1)
+        self.walk = False
+        self.cnt1 = self.cnt2 = self.order = None
+
+    def pool(self, h: Tensor):
+        """(xcn1, xcn2, x_i * x_j) of the batch; sets ``cnt1`` / ``cnt2``."""
+        adj, t1, t2 = self.adj, self.t1, self.t2
+        if h.dim() != 2 or h.shape[0] != self.N:
+            raise ValueError("h must have one row per column of the adjacency")
+        # T2: the bit rows the product arrived with (rows built on demand: the ones this batch probes — on one stream only,
+        # as CNState), else its CSR; T1: bit rows where they fit (small dense graphs), else its CSR
+        lazy = t2.rows_on_demand() and not getattr(ops, "_overlap_active", False)
+        bm2 = t2.product_bit_rows(self.dst) if lazy else t2.product_bit_rows()
+        csr2 = None if bm2 is not None else (t2._rowptr, t2._col)
+        bm1 = t1.bit_rows()
+        if self.B >= ops.sort_edges_min_batch:
+            self.order = ops.order_by_node(self.src, adj.size(0), self.ws)
+        x1, x2, xij, self.cnt1, self.cnt2 = ops.cn8_pool(adj._rowptr, adj._col, (t1._rowptr, t1._col), csr2, self.src, self.dst, h,
+                                                         t1_bitmap=bm1, t2_bitmap=bm2, order=self.order, wsd=self.ws, n_cols=self.N)
+        return x1, x2, xij
+
+
+def fuse8(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None) -> Optional[CN8State]:
+    """The cn8 batch of two pattern-mode ``adjoverlap`` handles (same adjacency, same candidate edges: the checks of
+    ``fuse``), or None for anything else — walk handles and explicit matrices take the flag form (``fuse``)."""
+    if not (isinstance(cn1, CNBatch) and isinstance(cn2, CNBatch) and cn1.mode == "pattern" and cn2.mode == "pattern"):
+        return None
+    if cn1.adj1 is not cn2.adj1:
+        raise NotImplementedError("cn1 and cn2 must select their source rows from the same adjacency")
+    if cn1.tarei.shape != cn2.tarei.shape or cn1.tarei.shape != tar_ei.shape:
+        raise ValueError("cn1, cn2 and tar_ei describe different numbers of candidate edges")
+    if ops.validate_indices and not (_same_edges(cn1.tarei, cn2.tarei) and _same_edges(cn1.tarei, tar_ei)):
+        raise NotImplementedError("cn1, cn2 and tar_ei must be built from the same candidate edges")
+    return CN8State(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, ws=ws)
+
+
 def adjoverlap(adj1: SparseTensor, adj2: SparseTensor, tarei: Tensor, filled1: bool = False,
                calresadj: bool = False, cnsampledeg: int = -1, ressampledeg: int = -1) -> CNBatch:
     """utils.py:248-285.  ``calresadj`` / sampling belong to the cn2-cn4 predictors, which no
