@@ -9,6 +9,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset collab --scale 0.05 --hiddim 64 --batch_size 8192
     python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
         --gnnedp 0.07 --res --maskinput --batch_size 384
+    python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
 """
 import argparse
 import os
@@ -20,6 +21,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
+from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
@@ -97,6 +99,20 @@ def test(model, predictor, data, split_edge, evaluator, batch_size, use_valedges
     return results, h
 
 
+@torch.no_grad()
+def test_heuristic(kind, data, split_edge, evaluator, batch_size, args):
+    """The dataset's metric for one training-free heuristic (ocn_amd.heuristics) on valid and test: the scores of test()
+    with the encoder and the predictor left out.  Test candidates see the validation edges with --use_valedges_as_input."""
+    dev = data.x.device
+    out = {}
+    for split, adj in (("valid", data.adj_t), ("test", data.full_adj_t)):
+        adj2 = build_adj2(adj, args) if kind in TWO_HOP else None
+        pos = score_edges_heuristic(adj, adj2, split_edge[split]['edge'].to(dev), batch_size, kind)
+        neg = score_edges_heuristic(adj, adj2, split_edge[split]['edge_neg'].to(dev), batch_size, kind)
+        out[split] = evaluator.eval({'y_pred_pos': pos, 'y_pred_neg': neg})[evaluator.eval_metric]
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="cora")
@@ -123,6 +139,7 @@ def main(argv=None):
     ap.add_argument("--use_xlin", action="store_true")
     ap.add_argument("--tailact", action="store_true")
     ap.add_argument("--twolayerlin", action="store_true")
+    ap.add_argument("--heuristic", default=None, choices=KINDS, help="skip training: print the dataset's metric for this link heuristic")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
@@ -130,6 +147,12 @@ def main(argv=None):
     data.x = data.x.to(dev)
     data.adj_t = data.adj_t.to_device(dev)
     data.full_adj_t = data.full_adj_t.to_device(dev) if args.use_valedges_as_input else data.adj_t
+    if args.heuristic:
+        if evaluator.eval_metric == "mrr":
+            ap.error("--heuristic: this driver scores the Hits@K datasets (as its test() does)")
+        res = test_heuristic(args.heuristic, data, split_edge, evaluator, args.testbs, args)
+        print(f"heuristic {args.heuristic} {evaluator.eval_metric} valid/test {res['valid']:.4f}/{res['test']:.4f}", flush=True)
+        return res
     torch.manual_seed(0)
     fin = args.hiddim if data.max_x >= 0 else data.x.shape[1]
     model = GCN(fin, args.hiddim, args.hiddim, args.mplayers, 0.05, True, args.res, data.max_x, args.model, True, args.gnnedp,

@@ -37,7 +37,7 @@ extern "C" {
  * 9: + ocn_heads_small_batch (ocn_heads_fused picks its small-batch form by the batch size; same bits), ocn_spgemm_bit_rows
  *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
  *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
- *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool. */
+ *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums. */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -320,6 +320,25 @@ int ocn_cn8_pool(const int64_t* rowptrA, const int32_t* colA,
                  const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
                  const float* h, int32_t H, float* xcn1, float* xcn2, float* xij,
                  int32_t* cnt1, int32_t* cnt2, void* stream);
+/* Link heuristics (common neighbours, Adamic-Adar, resource allocation, Jaccard, preferential attachment and their 2-hop
+ * forms: ocn_amd/heuristics.py) in ONE pass, the shape of ocn_cn8_pool with a 16-byte node row in place of an embedding row:
+ *   sum1[e][q] = sum_{k in N(i) ∩ T1(j)} w[k][q]   sum2[e][q] = sum_{k in N(i) ∩ T2(j)} w[k][q]   q = 0..3
+ * for e = (i, j) = (src[e], dst[e]); cnt1[e] / cnt2[e] = the number of members (int32); deg[e] (or NULL; needs rowptrT1)
+ * = {length of row i of A, length of row j of T1} as fp32.  N(i) is walked in ascending column order by one lane group, hub
+ * rows included: every sum starts from 0 and takes one fp32 add per member and weight column, in that order.  A candidate
+ * without members gets zeros.  No atomics, no workspace; nothing of a candidate depends on the rest of the batch.
+ * T1 / T2, order: as for ocn_cn8_pool, except that ALL of T2 may be NULL: then sum2 and cnt2 are written as zeros.
+ * w is [n_cols][4] row-major fp32 (16-byte aligned); sum1 / sum2 [B][4], deg [B][2], all indexed by the batch row.
+ * NULL required pointers, B < 0, n_cols < 0, T1 with neither form, T2 with half a CSR, bit rows narrower than n_cols,
+ * deg without rowptrT1: OCN_EINVAL before any HIP call.  B == 0 returns 0. */
+int ocn_cn_node_sums(const int64_t* rowptrA, const int32_t* colA,
+                     const int64_t* rowptrT1 /* or NULL */, const int32_t* colT1 /* or NULL */,
+                     const int64_t* rowptrT2 /* or NULL */, const int32_t* colT2 /* or NULL */,
+                     const uint32_t* bitmapT1 /* or NULL */, int64_t bm1_stride_words,
+                     const uint32_t* bitmapT2 /* or NULL */, int64_t bm2_stride_words,
+                     const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
+                     const float* w /* [n_cols][4] */, float* sum1, float* sum2, int32_t* cnt1, int32_t* cnt2,
+                     float* deg /* or NULL */, void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

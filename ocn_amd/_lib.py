@@ -56,6 +56,8 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P]),
     "ocn_cn8_pool": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int32, _P, _P,
                                _P, _P, _P, _P]),
+    "ocn_cn_node_sums": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P,
+                                   _P, _P]),
     "ocn_gather_schedule": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "ocn_coo_to_csr_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     "ocn_coo_to_csr": (c_int32, [_P, _P, c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

@@ -597,6 +597,60 @@ def cn8_pool(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor],
     return out[0], out[1], out[2], cnt[0], cnt[1]
 
 
+@_on_device
+def cn_node_sums(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor], Optional[Tensor]]],
+                 t2: Optional[Tuple[Optional[Tensor], Optional[Tensor]]], src: Tensor, dst: Tensor, w: Tensor,
+                 t1_bitmap: Optional[Tensor] = None, t2_bitmap: Optional[Tensor] = None, order: Optional[Tensor] = None, wsd=None,
+                 n_cols: Optional[int] = None):
+    """Sums of a node table over the common neighbours of a candidate batch, in one pass (ocn_hip.h: ocn_cn_node_sums) — what
+    the link heuristics are made of (ocn_amd/heuristics.py).  ``t1`` / ``t2``, the bit rows, ``order`` and ``n_cols``: as for
+    ``cn8_pool``, except that T2 may be left out altogether (``t2`` and ``t2_bitmap`` None: zero 2-hop outputs).  ``w``:
+    float32 [N, 4], N = the column count of A, T1 and T2.  Returns (sum1, sum2 float32 [B, 4], cnt1, cnt2 int32 [B],
+    deg float32 [B, 2] = {row length of src in A, of dst in T1}, or None where T1 has no CSR form)."""
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
+    _req(w, torch.float32, "w", 2)
+    B, N = src.numel(), w.shape[0]
+    if dst.numel() != B:
+        raise ValueError("src/dst length mismatch")
+    if w.shape[1] != 4:
+        raise ValueError(f"w must be [N, 4], got {tuple(w.shape)}")
+    if n_cols is not None and int(n_cols) != N:
+        raise ValueError(f"w has {N} rows, the adjacency {int(n_cols)} columns")
+    csr, n_rows = [], []
+    for t, bm, nm in ((t1, t1_bitmap, "T1"), (t2, t2_bitmap, "T2")):
+        rp, col = (None, None) if t is None else t
+        if rp is None or col is None:
+            if bm is None and nm == "T1":
+                raise ValueError("T1: needs its CSR arrays or its bit rows")
+            rp = col = None
+        else:
+            _req(rp, torch.int64, "rowptr" + nm, 1); _req(col, torch.int32, "col" + nm, 1)
+        if bm is not None:
+            _req(bm, torch.int32, nm.lower() + "_bitmap", 2)
+            if (rp is not None and bm.shape[0] != rp.numel() - 1) or bm.shape[1] * 32 < N:
+                raise ValueError(f"{nm.lower()}_bitmap does not match the {nm} adjacency")
+        csr.append((rp, col))
+        n_rows.append(rp.numel() - 1 if rp is not None else (bm.shape[0] if bm is not None else None))
+    if n_rows[1] is not None and n_rows[0] != n_rows[1]:       # (the kernel indexes both with dst: one bound must hold for both)
+        raise ValueError(f"T1 has {n_rows[0]} rows, T2 {n_rows[1]}")
+    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
+        raise ValueError("order: one entry per candidate")
+    check_edges(src, dst, rowptrA.numel() - 1, n_rows[0])
+    sums = buf(wsd, "heur_sums", (2, B, 4), torch.float32, w.device)
+    cnt = buf(wsd, "heur_cnt", (2, B), torch.int32, w.device)
+    deg = buf(wsd, "heur_deg", (B, 2), torch.float32, w.device) if csr[0][0] is not None else None
+    if B == 0:
+        return sums[0], sums[1], cnt[0], cnt[1], deg
+    check(_lib.lib().ocn_cn_node_sums(ptr(rowptrA), ptr(colA), ptr(csr[0][0]), ptr(csr[0][1]), ptr(csr[1][0]), ptr(csr[1][1]),
+                                      ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
+                                      ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
+                                      ptr(src), ptr(dst), ptr(order), B, N, ptr(w), ptr(sums[0]), ptr(sums[1]),
+                                      ptr(cnt[0]), ptr(cnt[1]), ptr(deg), stream_ptr()), "ocn_cn_node_sums")
+    _mark("cn_node_sums")
+    return sums[0], sums[1], cnt[0], cnt[1], deg
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 
