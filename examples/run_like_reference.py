@@ -10,6 +10,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
         --gnnedp 0.07 --res --maskinput --batch_size 384
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
+    python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
 """
 import argparse
 import os
@@ -23,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
+from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
 from ocn_amd.utils import PermIterator, adjoverlap, sparse_tensor_multiply          # noqa: E402
@@ -113,6 +115,25 @@ def test_heuristic(kind, data, split_edge, evaluator, batch_size, args):
     return out
 
 
+@torch.no_grad()
+def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5):
+    """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
+    the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1."""
+    dev = data.x.device
+    adj = data.full_adj_t
+    adj2 = build_adj2(adj, args)
+    sources = split_edge['test']['edge'][:n_sources, 0].to(dev).contiguous()
+    if args.heuristic:
+        dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
+    else:
+        model.eval(); predictor.eval()
+        dst, score = recommend_links(predictor, model(data.x, adj), adj, adj2, sources, k, args.testbs, args)
+    for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
+        print(f"recommend source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
+              flush=True)
+    return dst, score
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="cora")
@@ -140,6 +161,8 @@ def main(argv=None):
     ap.add_argument("--tailact", action="store_true")
     ap.add_argument("--twolayerlin", action="store_true")
     ap.add_argument("--heuristic", default=None, choices=KINDS, help="skip training: print the dataset's metric for this link heuristic")
+    ap.add_argument("--recommend", type=int, default=0, metavar="K",
+                    help="after the last epoch (at once with --heuristic): print the top-K predicted targets of the first few test sources")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
@@ -152,6 +175,8 @@ def main(argv=None):
             ap.error("--heuristic: this driver scores the Hits@K datasets (as its test() does)")
         res = test_heuristic(args.heuristic, data, split_edge, evaluator, args.testbs, args)
         print(f"heuristic {args.heuristic} {evaluator.eval_metric} valid/test {res['valid']:.4f}/{res['test']:.4f}", flush=True)
+        if args.recommend:
+            recommend(args.recommend, data, split_edge, args)
         return res
     torch.manual_seed(0)
     fin = args.hiddim if data.max_x >= 0 else data.x.shape[1]
@@ -174,6 +199,8 @@ def main(argv=None):
                 "  ".join(f"{k} train/valid/test {v[0]:.3f}/{v[1]:.3f}/{v[2]:.3f}" for k, v in results.items()))
         print(line, flush=True)
         out.append((loss, results))
+    if args.recommend:
+        recommend(args.recommend, data, split_edge, args, model, predictor)
     return out
 
 

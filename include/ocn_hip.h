@@ -37,7 +37,8 @@ extern "C" {
  * 9: + ocn_heads_small_batch (ocn_heads_fused picks its small-batch form by the batch size; same bits), ocn_spgemm_bit_rows
  *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
  *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
- *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums. */
+ *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums;
+ *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -339,6 +340,40 @@ int ocn_cn_node_sums(const int64_t* rowptrA, const int32_t* colA,
                      const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
                      const float* w /* [n_cols][4] */, float* sum1, float* sum2, int32_t* cnt1, int32_t* cnt2,
                      float* deg /* or NULL */, void* stream);
+
+/* Candidate generation for link recommendation (ocn_amd/recommend.py): the row difference of two CSR matrices with the same
+ * rows, for the rows a caller names.  For query q with s = rows[q] (int64; a source may repeat, its rows may be empty) the
+ * set is P[s,:] \ M[s,:], without column s too when drop_self != 0, in ascending column order.  With P = the pattern of A²
+ * and M = A that is the 2-hop neighbourhood of s that is not yet linked: the targets with a non-empty cn1 or cn2.
+ * Two phases around a caller-side allocation, as for the A*A pattern: count -> ocn_scan_i32 -> fill.
+ *   count[q] (int32) = the size of query q's set;
+ *   edges (int64 [T][2], T = off[Q], 16-byte aligned) takes the pairs (s, c) of query q row-major from edges[off[q]] on: the
+ *   layout of split_edge[...]['edge'], what the scoring loops take.  A pair that would land at off[q + 1] or beyond is
+ *   dropped: offsets that do not belong to these inputs leave holes, they never write past their own segment.
+ * Both passes run ONE kernel body: a wave owns a query, stages the M row in LDS when it has at most
+ * ocn_row_diff_stage_cols() columns (searched in memory beyond), streams the P row 64 columns at a time — hub rows of A²
+ * included, they only take more rounds — and compacts by ballot and popcount behind a running base.  No atomics, no
+ * workspace.  Both matrices: sorted, duplicate-free int32 columns; rows[] must be valid row ids of both (not checked here).
+ * NULL pointers or Q < 0: OCN_EINVAL before any HIP call.  Q == 0 returns 0. */
+int32_t ocn_row_diff_stage_cols(void);
+int ocn_row_diff_count(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
+                       const int64_t* rows, int64_t Q, int32_t drop_self, int32_t* count /* [Q] */, void* stream);
+int ocn_row_diff_fill(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
+                      const int64_t* rows, int64_t Q, int32_t drop_self, const int64_t* off /* [Q + 1], from ocn_scan_i32 */,
+                      int64_t* edges /* [off[Q]][2] */, void* stream);
+/* The k best entries of every segment scores[ptr[q] .. ptr[q + 1]) of a flat fp32 vector, best first, 1 <= k <=
+ * ocn_segment_topk_max_k() (128: two slots per lane).  top_val [Q][k] = the scores, top_pos [Q][k] (int64) = their positions
+ * in the FLAT vector, so that one index gathers whatever else the caller keeps per entry; a segment with fewer than k
+ * entries fills the rest with -inf and -1.  The order is total and part of the contract: the higher score first (fp32
+ * comparison, +0.0 == -0.0); equal scores by ascending position; NaN after every number, -inf included, NaNs among
+ * themselves by position.  The scores are returned as they were stored (a NaN's payload and a zero's sign survive).
+ * A wave owns a segment and keeps its running best sorted across its lanes; the segment is consumed 64 scores at a time
+ * and a chunk in which nothing beats the current k-th best costs one ballot.  Segments are independent: no atomics, no
+ * workspace, the result is fixed by the input.  A segment must have fewer than 2^32 - 1 entries.
+ * NULL pointers, Q < 0, k < 1 or k above the limit: OCN_EINVAL before any HIP call.  Q == 0 returns 0. */
+int32_t ocn_segment_topk_max_k(void);
+int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t k, float* top_val, int64_t* top_pos,
+                     void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

@@ -1,0 +1,219 @@
+// Link recommendation: the candidate set of a source as a row difference of two CSR matrices (its 2-hop neighbourhood
+// that is not yet linked: pattern(A² row s) \ (N(s) ∪ {s})), and the k best entries of every segment of a flat score
+// vector.  Both are ragged and row-parallel: a wave owns a query / a segment from its first load to its last store, no
+// atomics, no workspace, and the output of every row is fixed by its input alone.
+// See include/ocn_hip.h (ocn_row_diff_count / ocn_row_diff_fill, ocn_segment_topk).
+#include "common.h"
+
+// orders a wave's own LDS writes before its own LDS reads (and the reverse, for the next query's writes): LDS executes a
+// wave's instructions in order, so only the compiler has to be kept from moving them
+__device__ __forceinline__ void rd_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------------------
+// row difference P[s,:] \ M[s,:]
+// ---------------------------------------------------------------------------------------------
+// Columns of the M row a wave stages in LDS: 2 KiB per wave, 8 KiB per workgroup — eight workgroups per CU keep 64 of the
+// CU's 160 KiB, so the staging never lowers the occupancy the registers allow.  M is an adjacency: rows beyond 512 entries
+// are the few hubs of a power-law graph, and those are searched where they lie (their top-of-tree lines stay in L1 / L2).
+constexpr int RD_STAGE = 512;
+
+// membership of key in the sorted row a[0..n): the number of steps depends on n alone, which every lane of the wave shares,
+// and every load is in bounds for any key (a lane without a column carries -1, which no row holds)
+template <typename Row>
+__device__ __forceinline__ bool rd_row_has(Row a, int n, int32_t key) {
+  if (n <= 0) return false;
+  int base = 0;
+  for (int len = n; len > 1;) {
+    const int half = len >> 1;
+    base += (a[base + half] <= key) ? half : 0;
+    len -= half;
+  }
+  return a[base] == key;
+}
+
+// One body for both passes, so they cannot disagree: FILL == false leaves the size of every query's set in count[q],
+// FILL == true writes the (s, c) pairs of query q from edges[off[q]] on, in ascending column order.  The P row is streamed
+// 64 columns at a time; each lane searches its column in the M row, a ballot of the columns that stay gives every such
+// lane its place (the popcount of the lanes below it) and the wave's running base moves on by the popcount of the ballot.
+template <bool FILL>
+__global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
+    const i64* __restrict__ rowptrP, const int32_t* __restrict__ colP,
+    const i64* __restrict__ rowptrM, const int32_t* __restrict__ colM,
+    const i64* __restrict__ rows, i64 Q, int drop_self,
+    int32_t* __restrict__ count, const i64* __restrict__ off, longlong2* __restrict__ edges) {
+  __shared__ int32_t s_m[OCN_WPB][RD_STAGE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t* sm = s_m[wave];
+  for (i64 q = (i64)blockIdx.x * OCN_WPB + wave; q < Q; q += (i64)gridDim.x * OCN_WPB) {
+    const i64 s = rows[q];
+    const i64 p0 = rowptrP[s], dp = rowptrP[s + 1] - p0;
+    const i64 m0 = rowptrM[s];
+    const int dm = (int)(rowptrM[s + 1] - m0);               // (columns are distinct int32 ids: a row has fewer than 2^31)
+    const bool staged = dm <= RD_STAGE;
+    if (staged) {
+      for (int t = lane; t < dm; t += OCN_WAVE) sm[t] = colM[m0 + t];
+      rd_wave_lds_sync();
+    }
+    const int32_t self = drop_self ? (int32_t)s : -1;
+    i64 base = FILL ? off[q] : 0;
+    const i64 end = FILL ? off[q + 1] : 0;
+    for (i64 c0 = 0; c0 < dp; c0 += OCN_WAVE) {
+      const i64 p = c0 + lane;
+      const int32_t cv = colP[p0 + (p < dp ? p : dp - 1)];
+      const int32_t c = p < dp ? cv : -1;
+      const bool in_m = staged ? rd_row_has(sm, dm, c) : rd_row_has(colM + m0, dm, c);
+      const bool keep = (c >= 0) & !in_m & (c != self);
+      const u64 mask = __ballot(keep);
+      if (FILL) {
+        const i64 at = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (keep && at < end) edges[at] = make_longlong2(s, (i64)c);       // (at < end: offsets of another input write nothing past their own segment)
+      }
+      base += __popcll(mask);
+    }
+    if (!FILL && lane == 0) count[q] = (int32_t)base;
+    if (staged) rd_wave_lds_sync();                          // the next query's staging writes stay behind this one's reads
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// segmented top-k
+// ---------------------------------------------------------------------------------------------
+constexpr int TOPK_MAX = 2 * OCN_WAVE;                       // two slots per lane
+constexpr int TOPK_AHEAD = 4;                                // chunks of 64 scores loaded ahead of their tests
+
+// The order of the contract as ONE unsigned comparison (larger = better): the high word is the score's monotone image —
+// -0.0 is folded onto +0.0 first, every NaN goes to 0, below -inf (0x007fffff) — the low word is ~(position in the segment),
+// so that among equal scores (and among NaNs) the lower position wins.  A segment has fewer than 2^32 - 1 entries: no entry
+// has the key 0, which marks an empty slot.
+__device__ __forceinline__ u64 topk_key(float x, unsigned rel) {
+  unsigned b = __float_as_uint(x);
+  if (b == 0x80000000u) b = 0u;
+  unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  if (x != x) u = 0u;
+  return ((u64)u << 32) | (u64)(0xffffffffu - rel);
+}
+
+__device__ __forceinline__ u64 topk_readlane(u64 v, int l) {
+  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
+  return ((u64)hi << 32) | lo;
+}
+
+__device__ __forceinline__ u64 topk_shfl_up1(u64 v) {
+  const unsigned lo = __shfl_up((unsigned)v, 1, OCN_WAVE), hi = __shfl_up((unsigned)(v >> 32), 1, OCN_WAVE);
+  return ((u64)hi << 32) | lo;
+}
+
+// A wave keeps the best keys of its segment sorted, best first, across its lanes: slot j lives in lane j & 63, register
+// j >> 6 (NS registers: one for k <= 64, two up to 128).  The segment is consumed 64 scores at a time; a chunk none of whose
+// keys beats the k-th best costs one ballot.  Otherwise the keys that do are inserted one by one, in lane order: every slot
+// keeps its key if that beats the new one, else it takes the new key or its upper neighbour's, whichever is smaller — one
+// shuffle per register — and the k-th best is read again, so a later key of the chunk that no longer beats it is dropped
+// unseen.  Keys are distinct, so the list, and with it the output, is fixed by the segment alone.
+template <int NS>
+__global__ __launch_bounds__(OCN_BLOCK) void segment_topk_kernel(
+    const float* __restrict__ scores, const i64* __restrict__ ptr, i64 Q, int k,
+    float* __restrict__ top_val, i64* __restrict__ top_pos) {
+  const int lane = threadIdx.x & 63;
+  const int kl = (k - 1) & 63;                               // the k-th best lives in this lane of the last register
+  for (i64 q = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); q < Q; q += (i64)gridDim.x * OCN_WPB) {
+    const i64 b = ptr[q], n = ptr[q + 1] - b;
+    u64 v[NS];
+#pragma unroll
+    for (int r = 0; r < NS; ++r) v[r] = 0ull;
+    u64 thr = 0ull;
+    for (i64 c0 = 0; c0 < n; c0 += (i64)OCN_WAVE * TOPK_AHEAD) {
+      float x[TOPK_AHEAD];
+#pragma unroll
+      for (int t = 0; t < TOPK_AHEAD; ++t) {
+        const i64 p = c0 + t * OCN_WAVE + lane;
+        x[t] = scores[b + (p < n ? p : n - 1)];
+      }
+#pragma unroll
+      for (int t = 0; t < TOPK_AHEAD; ++t) {
+        const i64 p = c0 + t * OCN_WAVE + lane;
+        const u64 key = p < n ? topk_key(x[t], (unsigned)p) : 0ull;
+        u64 m = __ballot(key > thr);
+        while (m) {                                          // (the same trip count in every lane)
+          const int sl = __ffsll((long long)m) - 1;
+          m &= m - 1;
+          const u64 nk = topk_readlane(key, sl);
+          if (nk <= thr) continue;
+          u64 up[NS];
+#pragma unroll
+          for (int r = 0; r < NS; ++r) up[r] = topk_shfl_up1(v[r]);
+          if (NS == 2) { const u64 carry = topk_readlane(v[0], 63); if (lane == 0) up[NS - 1] = carry; }
+          if (lane == 0) up[0] = ~0ull;
+#pragma unroll
+          for (int r = 0; r < NS; ++r) v[r] = v[r] > nk ? v[r] : (up[r] > nk ? nk : up[r]);
+          thr = topk_readlane(v[NS - 1], kl);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NS; ++r) {
+      const int j = r * OCN_WAVE + lane;
+      if (j < k) {
+        const bool has = v[r] != 0ull;
+        const i64 at = b + (i64)(0xffffffffu - (unsigned)v[r]);
+        top_val[q * k + j] = has ? scores[at] : -__builtin_inff();
+        top_pos[q * k + j] = has ? at : -1;
+      }
+    }
+  }
+}
+
+static inline unsigned wave_grid(i64 items) { return (unsigned)grid_for((items + OCN_WPB - 1) / OCN_WPB, 256 * 8); }
+
+extern "C" {
+
+int32_t ocn_row_diff_stage_cols(void) { return RD_STAGE; }
+
+static int row_diff_launch(bool fill, const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
+                           const int64_t* rows, int64_t Q, int32_t drop_self, int32_t* count, const int64_t* off, int64_t* edges,
+                           void* stream) {
+  if (Q < 0 || !rowptrP || !colP || !rowptrM || !colM || !rows) return OCN_EINVAL;
+  if (fill ? (!off || !edges) : !count) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  const dim3 grid(wave_grid(Q));
+  if (fill)
+    hipLaunchKernelGGL(row_diff_kernel<true>, grid, dim3(OCN_BLOCK), 0, (hipStream_t)stream, (const i64*)rowptrP, colP,
+                       (const i64*)rowptrM, colM, (const i64*)rows, (i64)Q, (int)drop_self, (int32_t*)nullptr, (const i64*)off,
+                       (longlong2*)edges);
+  else
+    hipLaunchKernelGGL(row_diff_kernel<false>, grid, dim3(OCN_BLOCK), 0, (hipStream_t)stream, (const i64*)rowptrP, colP,
+                       (const i64*)rowptrM, colM, (const i64*)rows, (i64)Q, (int)drop_self, count, (const i64*)nullptr,
+                       (longlong2*)nullptr);
+  return launch_status();
+}
+
+int ocn_row_diff_count(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
+                       const int64_t* rows, int64_t Q, int32_t drop_self, int32_t* count, void* stream) {
+  return row_diff_launch(false, rowptrP, colP, rowptrM, colM, rows, Q, drop_self, count, nullptr, nullptr, stream);
+}
+
+int ocn_row_diff_fill(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
+                      const int64_t* rows, int64_t Q, int32_t drop_self, const int64_t* off, int64_t* edges, void* stream) {
+  return row_diff_launch(true, rowptrP, colP, rowptrM, colM, rows, Q, drop_self, nullptr, off, edges, stream);
+}
+
+int32_t ocn_segment_topk_max_k(void) { return TOPK_MAX; }
+
+int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t k, float* top_val, int64_t* top_pos,
+                     void* stream) {
+  if (Q < 0 || k < 1 || k > TOPK_MAX || !ptr || !top_val || !top_pos) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  if (!scores) return OCN_EINVAL;
+  const dim3 grid(wave_grid(Q));
+  if (k <= OCN_WAVE)
+    hipLaunchKernelGGL(segment_topk_kernel<1>, grid, dim3(OCN_BLOCK), 0, (hipStream_t)stream, scores, (const i64*)ptr, (i64)Q,
+                       (int)k, top_val, (i64*)top_pos);
+  else
+    hipLaunchKernelGGL(segment_topk_kernel<2>, grid, dim3(OCN_BLOCK), 0, (hipStream_t)stream, scores, (const i64*)ptr, (i64)Q,
+                       (int)k, top_val, (i64*)top_pos);
+  return launch_status();
+}
+
+}  // extern "C"

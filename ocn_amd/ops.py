@@ -651,6 +651,83 @@ def cn_node_sums(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tens
     return sums[0], sums[1], cnt[0], cnt[1], deg
 
 
+def row_diff_stage_cols() -> int:
+    """Columns of an M row ``ocn_row_diff_*`` stages in LDS; longer rows are searched in memory."""
+    return int(_lib.lib().ocn_row_diff_stage_cols())
+
+
+def _row_diff_args(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor) -> int:
+    """The operand checks of both row-difference passes.  The columns of P and of M must be sorted and duplicate-free in every
+    row, as every ``SparseTensor`` of the project stores them: the kernel does not sort again and this layer cannot see it."""
+    _req(rowptrP, torch.int64, "rowptrP", 1); _req(colP, torch.int32, "colP", 1)
+    _req(rowptrM, torch.int64, "rowptrM", 1); _req(colM, torch.int32, "colM", 1)
+    _req(rows, torch.int64, "rows", 1)
+    if rowptrP.numel() < 1 or rowptrP.numel() != rowptrM.numel():
+        raise ValueError(f"P has {rowptrP.numel() - 1} rows, M {rowptrM.numel() - 1}")
+    n = rowptrP.numel() - 1
+    check_edges(rows, rows, n, n)
+    return rows.numel()
+
+
+@_on_device
+def row_diff_count(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, drop_self: bool = True) -> Tensor:
+    """count[q] = |P[s,:] \\ M[s,:]| for s = rows[q], without column s too under ``drop_self`` (ocn_hip.h: ocn_row_diff_count):
+    int32 [Q].  ``scan_i32`` of it gives the offsets ``row_diff_fill`` writes at."""
+    Q = _row_diff_args(rowptrP, colP, rowptrM, colM, rows)
+    count = torch.empty(Q, dtype=torch.int32, device=rows.device)
+    if Q:
+        check(_lib.lib().ocn_row_diff_count(ptr(rowptrP), ptr(colP), ptr(rowptrM), ptr(colM), ptr(rows), Q, int(bool(drop_self)),
+                                            ptr(count), stream_ptr()), "ocn_row_diff_count")
+        _mark("row_diff_count")
+    return count
+
+
+@_on_device
+def row_diff_fill(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, off: Tensor,
+                  drop_self: bool = True, total: Optional[int] = None) -> Tensor:
+    """The pairs (s, c) of every query's set, ascending in c, row-major in int64 [T, 2] from ``off[q]`` on (ocn_hip.h:
+    ocn_row_diff_fill).  ``off``: ``scan_i32(row_diff_count(...))`` of the same operands; ``total`` = ``off[-1]`` where the
+    caller has read it already (else it is read here: one host sync for the output size)."""
+    Q = _row_diff_args(rowptrP, colP, rowptrM, colM, rows)
+    if _req(off, torch.int64, "off", 1).numel() != Q + 1:
+        raise ValueError("off: one entry per query and the total")
+    T = _total(off[-1]) if total is None else int(total)
+    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    if Q and T:
+        check(_lib.lib().ocn_row_diff_fill(ptr(rowptrP), ptr(colP), ptr(rowptrM), ptr(colM), ptr(rows), Q, int(bool(drop_self)),
+                                           ptr(off), ptr(edges), stream_ptr()), "ocn_row_diff_fill")
+        _mark("row_diff_fill")
+    return edges
+
+
+def segment_topk_max_k() -> int:
+    return int(_lib.lib().ocn_segment_topk_max_k())
+
+
+@_on_device
+def segment_topk(scores: Tensor, seg_ptr: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """The ``k`` best entries of every segment ``scores[seg_ptr[q] : seg_ptr[q + 1]]``, best first (ocn_hip.h: ocn_segment_topk):
+    (values float32 [Q, k], positions int64 [Q, k] into the flat vector; -inf and -1 where a segment has fewer than k).
+    Order: higher score first, equal scores by position, +0.0 == -0.0, NaN after every number.  ``seg_ptr`` is trusted to be
+    ascending offsets into ``scores`` with ``seg_ptr[-1] <= scores.numel()`` (checking it would cost a host sync)."""
+    k = int(k)
+    if not 1 <= k <= segment_topk_max_k():
+        raise ValueError(f"k must be in 1..{segment_topk_max_k()}, got {k}")
+    _req(scores, torch.float32, "scores", 1); _req(seg_ptr, torch.int64, "ptr", 1)
+    if seg_ptr.numel() < 1:
+        raise ValueError("ptr: [Q + 1] offsets")
+    if scores.numel() >= (1 << 32) - 1:
+        raise ValueError("scores: segments of 2^32 - 1 entries or more are not supported")
+    Q = seg_ptr.numel() - 1
+    val = torch.empty(Q, k, dtype=torch.float32, device=scores.device)
+    pos = torch.empty(Q, k, dtype=torch.int64, device=scores.device)
+    if Q:
+        src = scores if scores.numel() else scores.new_empty(1)          # (no score to read: every segment is empty, the entry still wants a pointer)
+        check(_lib.lib().ocn_segment_topk(ptr(src), ptr(seg_ptr), Q, k, ptr(val), ptr(pos), stream_ptr()), "ocn_segment_topk")
+        _mark("segment_topk")
+    return val, pos
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 

@@ -1,0 +1,108 @@
+"""Top-K link recommendation: "for these nodes, which links do you predict?".
+
+The scoring loops (``pipeline.score_edges``, ``heuristics.score_edges_heuristic``) take candidate pairs that somebody else
+made and return a flat score vector.  This module makes the pairs and picks from the scores, both on the device:
+
+* the natural candidate set of a common-neighbour predictor is the 2-hop neighbourhood of a source that is not yet linked,
+  ``pattern(A² row s) \\ (N(s) ∪ {s})`` — any other target has empty ``cn1`` and ``cn2`` and is scored from ``x_i ⊙ x_j``
+  alone.  ``two_hop_candidates`` enumerates that set difference row by row (``ops.row_diff_count`` -> ``ops.scan_i32`` ->
+  ``ops.row_diff_fill``) straight into the [T, 2] layout the scoring loops take: no dense [Q, N] mask, no host loop;
+* candidate lists are ragged — under a power law from a handful to tens of thousands per source — so the best ``k`` per
+  source are selected segment by segment (``ops.segment_topk``) instead of padding to a [Q, max_len] rectangle.
+
+Everything runs on one GPU; dealing the sources over several is not built here.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import ops
+from .sparse import SparseTensor
+
+
+def _check_k(k) -> int:
+    k = int(k)
+    if not 1 <= k <= ops.segment_topk_max_k():
+        raise ValueError(f"k must be in 1..{ops.segment_topk_max_k()}, got {k}")
+    return k
+
+
+def two_hop_candidates(adj: SparseTensor, adj2: SparseTensor, sources: Tensor,
+                       known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+    """The candidate targets of ``sources`` (int64 [Q]; a source may repeat): for each source ``s``, in source order, the
+    columns of row ``s`` of ``adj2`` that are neither ``s`` nor in row ``s`` of ``known``, ascending.  Returns
+    (``ptr`` int64 [Q + 1], ``edges`` int64 [T, 2]): ``edges[ptr[q]:ptr[q + 1]]`` are the pairs ``(sources[q], c)`` — the
+    layout of ``split_edge[...]['edge']``, which ``pipeline.score_edges`` takes as it is.
+
+    ``adj2``: the project's A² (diagonal included), or any square ``SparseTensor`` of ``adj``'s size.  ``known``: the links
+    that are no news, ``adj`` by default; pass ``full_adj_t`` to exclude the validation edges as well.  It must have
+    ``adj``'s size.  Reading the CSR of ``adj2`` forces the deferred passes of a product: the fill pass of ``A @ A`` whose
+    column ids were left for later, and the counting pass as well of a product formed under autograd.
+
+    ``sources`` are bounds-checked once (one host sync); the output size costs a second one."""
+    known = adj if known is None else known
+    if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
+        raise ValueError("sources must be a 1-d int64 tensor of node ids")
+    n = adj.size(0)
+    for name, m in (("adj", adj), ("adj2", adj2), ("known", known)):
+        if tuple(m.sparse_sizes()) != (n, n):
+            raise ValueError(f"{name} is {tuple(m.sparse_sizes())}, expected the square size ({n}, {n}) of adj")
+    sources = sources.contiguous()
+    rp2, col2, rpk, colk = adj2._rowptr, adj2._col, known._rowptr, known._col
+    with ops.prevalidated(sources, sources, n, n):
+        count = ops.row_diff_count(rp2, col2, rpk, colk, sources, drop_self=True)
+        ptr = ops.scan_i32(count)
+        edges = ops.row_diff_fill(rp2, col2, rpk, colk, sources, ptr, drop_self=True)
+    return ptr, edges
+
+
+def segment_topk(scores: Tensor, ptr: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """The ``k`` best scores of every segment ``scores[ptr[q]:ptr[q + 1]]``, best first: (values float32 [Q, k], positions
+    int64 [Q, k] into ``scores``), padded with -inf and -1.  The order is total: the higher score first (+0.0 and -0.0 are
+    equal), equal scores by ascending position, NaN after every number and NaNs among themselves by position."""
+    return ops.segment_topk(scores, ptr, _check_k(k))
+
+
+def _select(scores: Tensor, ptr: Tensor, edges: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    val, pos = ops.segment_topk(scores, ptr, k)
+    if edges.shape[0] == 0:
+        return torch.full_like(pos, -1), val
+    dst = edges[:, 1][pos.clamp(min=0)]
+    return torch.where(pos >= 0, dst, torch.full_like(dst, -1)), val
+
+
+@torch.no_grad()
+def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: SparseTensor, sources: Tensor, k: int, batch_size: int,
+                    args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6) -> Tuple[Tensor, Tensor]:
+    """The ``k`` best predicted links of every source: (``dst`` int64 [Q, k], ``score`` float32 [Q, k]), best first, ``dst``
+    = -1 and ``score`` = -inf where a source has fewer than ``k`` candidates.
+
+    The candidates of all ``Q`` sources (``two_hop_candidates``, in source order) are scored by ONE
+    ``pipeline.score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)`` call and selected per source.
+    The normalisation of cn5 and cn7 couples the candidates of a batch, so the contract is stated in terms of that call:
+    the scores are exactly those ``score_edges`` returns for the flat candidate list at this ``batch_size``.  Another set of
+    ``sources`` or another ``batch_size`` puts other candidates into a batch and changes cn5 / cn7 scores — as it does in the
+    reference's ``test()``.  Ties go to the lower node id (candidates are in ascending order)."""
+    from .pipeline import score_edges
+    if predictor.training:
+        raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
+    k = _check_k(k)
+    ptr, edges = two_hop_candidates(adj, adj2, sources, known)
+    scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
+    return _select(scores, ptr, edges, k)
+
+
+@torch.no_grad()
+def recommend_links_heuristic(adj: SparseTensor, adj2: SparseTensor, sources: Tensor, k: int, batch_size: int, kind: str,
+                              known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+    """``recommend_links`` with one training-free heuristic (``heuristics.score_edges_heuristic``) in place of a model.  A
+    heuristic score depends on its candidate alone: the result does not change with ``batch_size`` or with the other sources."""
+    from .heuristics import _check_kinds, score_edges_heuristic
+    _check_kinds((kind,), adj2)
+    k = _check_k(k)
+    ptr, edges = two_hop_candidates(adj, adj2, sources, known)
+    scores = score_edges_heuristic(adj, adj2, edges, batch_size, kind)
+    return _select(scores, ptr, edges, k)
