@@ -11,6 +11,7 @@ argument parser is the reference's call sequence with the three import lines swa
         --gnnedp 0.07 --res --maskinput --batch_size 384
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
 """
 import argparse
 import os
@@ -118,10 +119,11 @@ def test_heuristic(kind, data, split_edge, evaluator, batch_size, args):
 @torch.no_grad()
 def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5):
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
-    the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1."""
+    the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1.
+    --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route."""
     dev = data.x.device
     adj = data.full_adj_t
-    adj2 = build_adj2(adj, args)
+    adj2 = None if args.recommend_walk else build_adj2(adj, args)
     sources = split_edge['test']['edge'][:n_sources, 0].to(dev).contiguous()
     if args.heuristic:
         dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
@@ -163,7 +165,11 @@ def main(argv=None):
     ap.add_argument("--heuristic", default=None, choices=KINDS, help="skip training: print the dataset's metric for this link heuristic")
     ap.add_argument("--recommend", type=int, default=0, metavar="K",
                     help="after the last epoch (at once with --heuristic): print the top-K predicted targets of the first few test sources")
+    ap.add_argument("--recommend-walk", action="store_true",
+                    help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
     args = ap.parse_args(argv)
+    if args.recommend_walk and args.heuristic in TWO_HOP:
+        ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

@@ -38,7 +38,8 @@ extern "C" {
  *    (ocn_cn_flags accepts rowptrT2 == NULL beside bitmapT2).  Later additions to 9 (backward-compatible): ocn_spmm_csr_max_arg,
  *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
  *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums;
- *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation). */
+ *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation); ocn_two_hop_diff_count / _fill (its candidates
+ *    expanded from A, where A² is not stored). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -361,6 +362,28 @@ int ocn_row_diff_count(const int64_t* rowptrP, const int32_t* colP, const int64_
 int ocn_row_diff_fill(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
                       const int64_t* rows, int64_t Q, int32_t drop_self, const int64_t* off /* [Q + 1], from ocn_scan_i32 */,
                       int64_t* edges /* [off[Q]][2] */, void* stream);
+/* The same candidate set without a stored A²: for query q with s = rows[q] the set is
+ *   ( U_{m in A[s,:]} A[m,:] ) \ M[s,:], without column s too when drop_self != 0,
+ * in ascending column order — with M = A exactly pattern(A² row s) \ (N(s) U {s}), what ocn_row_diff_* yields from a
+ * materialised A².  The contract of ocn_row_diff_* holds word for word: count -> ocn_scan_i32 -> fill, count[q] int32, edges
+ * int64 [off[Q]][2] pairs (s, c) row-major, a source may repeat and its rows may be empty, a pair that would land at
+ * off[q + 1] or beyond is dropped.  Both passes run ONE kernel body: a workgroup owns a query and keeps the set as a bitmap in
+ * LDS, as the A*A pattern kernel keeps an output row; the column limit of that kernel is lifted by sweeping the column range
+ * in windows of window_cols columns (every neighbour's row is entered at the window's lower bound by binary search), so any
+ * n_cols < 2^31 is served.  LDS atomics only: no global atomics, no workspace, the output is fixed by the input.
+ * window_cols: 0 = ocn_two_hop_window_cols() (what fits the CU's LDS; a multiple of 64), else a positive multiple of 64 no
+ * larger than that — a small window exercises the sweep on a small graph, it is never faster.  The bitmap takes
+ * min(window_cols, n_cols rounded up to 64) / 8 bytes of LDS.  A and M: square, n_cols rows and columns, sorted duplicate-free
+ * int32 columns; rows[] must be valid row ids (not checked here).
+ * NULL pointers, Q < 0, n_cols <= 0 or >= 2^31, a bad window_cols: OCN_EINVAL before any HIP call.  Q == 0 returns 0. */
+int64_t ocn_two_hop_window_cols(void);
+int ocn_two_hop_diff_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self,
+                           int64_t window_cols /* 0: the default */, int32_t* count /* [Q] */, void* stream);
+int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self,
+                          int64_t window_cols /* 0: the default */, const int64_t* off /* [Q + 1], from ocn_scan_i32 */,
+                          int64_t* edges /* [off[Q]][2] */, void* stream);
 /* The k best entries of every segment scores[ptr[q] .. ptr[q + 1]) of a flat fp32 vector, best first, 1 <= k <=
  * ocn_segment_topk_max_k() (128: two slots per lane).  top_val [Q][k] = the scores, top_pos [Q][k] (int64) = their positions
  * in the FLAT vector, so that one index gathers whatever else the caller keeps per entry; a segment with fewer than k

@@ -3,6 +3,9 @@
 // vector.  Both are ragged and row-parallel: a wave owns a query / a segment from its first load to its last store, no
 // atomics, no workspace, and the output of every row is fixed by its input alone.
 // See include/ocn_hip.h (ocn_row_diff_count / ocn_row_diff_fill, ocn_segment_topk).
+// Where A² is not stored (more columns than the A*A pattern takes, or simply too large) the same candidate set is expanded
+// from A itself: a workgroup owns a query and keeps the union of its neighbours' rows as a bitmap in LDS, one window of the
+// column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
 #include "common.h"
 
 // orders a wave's own LDS writes before its own LDS reads (and the reverse, for the next query's writes): LDS executes a
@@ -75,6 +78,107 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
     }
     if (!FILL && lane == 0) count[q] = (int32_t)base;
     if (staged) rd_wave_lds_sync();                          // the next query's staging writes stay behind this one's reads
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 2-hop row difference ( U_{m in A[s,:]} A[m,:] ) \ M[s,:], expanded from A
+// ---------------------------------------------------------------------------------------------
+// The default window: what the A*A pattern kernel keeps of the CU's 160 KiB (2 KiB are left to the scan's words and the
+// runtime), as bits.  1 294 336 columns, a multiple of 64.
+constexpr i64 TH_WINDOW = (i64)(160 * 1024 - 2048) * 8;
+
+// first position of the sorted row a[0..n) whose column is not below key; the same steps and the same loads in every lane
+__device__ __forceinline__ i64 th_lower_bound(const int32_t* __restrict__ a, i64 n, i64 key) {
+  i64 lo = 0, hi = n;
+  while (lo < hi) {
+    const i64 mid = lo + ((hi - lo) >> 1);
+    if ((i64)a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One body for both passes, so they cannot disagree.  A workgroup owns query q; the column range is swept in windows
+// [w0, w1) of `window` columns, the window's part of the set as a bitmap in LDS:
+//   1. the bitmap is cleared;
+//   2. a wave takes a neighbour m of s, finds where row m enters the window (binary search, skipped for the first window)
+//      and sets a bit per column below w1 — LDS atomicOr: the lanes of a wave, and the waves, do meet in one word;
+//   3. the bits of M[s,:] inside the window, and of s itself under drop_self, are cleared (atomicAnd);
+//   4. every thread counts the bits of its contiguous words; the block scan of these counts (wave prefixes through LDS) places
+//      the thread's columns behind the query's running base, which moves on by the window's total.
+// Every barrier is reached by the whole workgroup: the query loop and the window loop run on blockIdx and kernel arguments
+// alone, never on a row length.  A column outside [w0, w1) never touches the bitmap, whatever the rows hold.
+template <bool FILL>
+__global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
+    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+    const i64* __restrict__ rowptrM, const int32_t* __restrict__ colM, i64 n_cols,
+    const i64* __restrict__ rows, i64 Q, int drop_self, i64 window,
+    int32_t* __restrict__ count, const i64* __restrict__ off, longlong2* __restrict__ edges) {
+  extern __shared__ __attribute__((aligned(16))) unsigned th_bm[];
+  __shared__ i64 sh[2 * OCN_WPB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (i64 q = blockIdx.x; q < Q; q += gridDim.x) {
+    const i64 s = rows[q];
+    const i64 a0 = rowptrA[s], da = rowptrA[s + 1] - a0;
+    const i64 m0 = rowptrM[s], dm = rowptrM[s + 1] - m0;
+    i64 base = FILL ? off[q] : 0;
+    const i64 end = FILL ? off[q + 1] : 0;
+    for (i64 w0 = 0; w0 < n_cols; w0 += window) {
+      const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
+      const int words = (int)((w1 - w0 + 31) >> 5);
+      for (int w = threadIdx.x; w < words; w += OCN_BLOCK) th_bm[w] = 0u;
+      __syncthreads();
+      for (i64 t = wave; t < da; t += OCN_WPB) {
+        const i64 m = colA[a0 + t];
+        const i64 b0 = rowptrA[m], db = rowptrA[m + 1] - b0;
+        const i64 lo = w0 > 0 ? th_lower_bound(colA + b0, db, w0) : 0;
+        for (i64 p = lo + lane; p < db; p += OCN_WAVE) {
+          const i64 c = colA[b0 + p];
+          if (c >= w1) break;                                // (sorted: so is every later column of this lane)
+          if (c >= w0) {
+            const unsigned k = (unsigned)(c - w0);
+            atomicOr(&th_bm[k >> 5], 1u << (k & 31u));
+          }
+        }
+      }
+      __syncthreads();
+      const i64 lo_m = w0 > 0 ? th_lower_bound(colM + m0, dm, w0) : 0;
+      for (i64 p = lo_m + threadIdx.x; p < dm; p += OCN_BLOCK) {
+        const i64 c = colM[m0 + p];
+        if (c >= w1) break;
+        if (c >= w0) {
+          const unsigned k = (unsigned)(c - w0);
+          atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
+        }
+      }
+      if (drop_self && threadIdx.x == 0 && s >= w0 && s < w1) {
+        const unsigned k = (unsigned)(s - w0);
+        atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
+      }
+      __syncthreads();
+      const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;   // contiguous words per thread: ascending columns in thread order
+      const int t0 = (int)threadIdx.x * wpt < words ? (int)threadIdx.x * wpt : words;
+      const int t1 = (t0 + wpt) < words ? (t0 + wpt) : words;
+      i64 c = 0;
+      for (int w = t0; w < t1; ++w) c += __popc(th_bm[w]);
+      i64 tot;
+      const i64 ex = block_excl_scan(c, sh, &tot);
+      if (FILL) {
+        i64 at = base + ex;
+        for (int w = t0; w < t1; ++w) {
+          unsigned bits = th_bm[w];
+          while (bits) {
+            const int b = __ffs((int)bits) - 1;
+            bits &= bits - 1;
+            if (at < end) edges[at] = make_longlong2(s, w0 + ((i64)w << 5) + b);   // (at < end: as in the row difference)
+            ++at;
+          }
+        }
+      }
+      base += tot;
+      __syncthreads();                                       // the next window's clear stays behind this one's reads
+    }
+    if (!FILL && threadIdx.x == 0) count[q] = (int32_t)base;
   }
 }
 
@@ -197,6 +301,51 @@ int ocn_row_diff_count(const int64_t* rowptrP, const int32_t* colP, const int64_
 int ocn_row_diff_fill(const int64_t* rowptrP, const int32_t* colP, const int64_t* rowptrM, const int32_t* colM,
                       const int64_t* rows, int64_t Q, int32_t drop_self, const int64_t* off, int64_t* edges, void* stream) {
   return row_diff_launch(true, rowptrP, colP, rowptrM, colM, rows, Q, drop_self, nullptr, off, edges, stream);
+}
+
+int64_t ocn_two_hop_window_cols(void) { return TH_WINDOW; }
+
+static int two_hop_launch(bool fill, const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, int32_t* count,
+                          const int64_t* off, int64_t* edges, void* stream) {
+  if (Q < 0 || !rowptrA || !colA || !rowptrM || !colM || !rows) return OCN_EINVAL;
+  if (fill ? (!off || !edges) : !count) return OCN_EINVAL;
+  if (n_cols <= 0 || n_cols >= ((int64_t)1 << 31)) return OCN_EINVAL;
+  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > TH_WINDOW) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  const i64 window = window_cols ? (i64)window_cols : TH_WINDOW;
+  const i64 padded = (n_cols + 63) / 64 * 64;
+  const size_t lds = (size_t)((window < padded ? window : padded) / 8);       // a small graph keeps several workgroups per CU
+  const dim3 grid((unsigned)grid_for(Q));
+  hipError_t err;
+  if (fill) {
+    err = hipFuncSetAttribute((const void*)two_hop_diff_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return (int)err;
+    hipLaunchKernelGGL(two_hop_diff_kernel<true>, grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, (const i64*)rowptrA, colA,
+                       (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self, window,
+                       (int32_t*)nullptr, (const i64*)off, (longlong2*)edges);
+  } else {
+    err = hipFuncSetAttribute((const void*)two_hop_diff_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return (int)err;
+    hipLaunchKernelGGL(two_hop_diff_kernel<false>, grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, (const i64*)rowptrA, colA,
+                       (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self, window, count,
+                       (const i64*)nullptr, (longlong2*)nullptr);
+  }
+  return launch_status();
+}
+
+int ocn_two_hop_diff_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols,
+                           int32_t* count, void* stream) {
+  return two_hop_launch(false, rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, count, nullptr, nullptr,
+                        stream);
+}
+
+int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols,
+                          const int64_t* off, int64_t* edges, void* stream) {
+  return two_hop_launch(true, rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, nullptr, off, edges,
+                        stream);
 }
 
 int32_t ocn_segment_topk_max_k(void) { return TOPK_MAX; }

@@ -700,6 +700,58 @@ def row_diff_fill(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, 
     return edges
 
 
+def two_hop_window_cols() -> int:
+    """Columns of one LDS window of ``ocn_two_hop_diff_*``; a graph with more columns is swept in several."""
+    return int(_lib.lib().ocn_two_hop_window_cols())
+
+
+def _two_hop_args(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, window_cols: int) -> Tuple[int, int]:
+    """The operand checks of both 2-hop passes: those of the row difference (A and M square and of one size, sorted
+    duplicate-free columns, which this layer cannot see) and the window.  Returns (Q, n)."""
+    Q = _row_diff_args(rowptrA, colA, rowptrM, colM, rows)
+    n = rowptrA.numel() - 1
+    if not 0 < n < (1 << 31):
+        raise ValueError(f"A has {n} rows: int32 columns serve 1 .. 2^31 - 1")
+    window_cols = int(window_cols)
+    if window_cols < 0 or window_cols % 64 or window_cols > two_hop_window_cols():
+        raise ValueError(f"window_cols must be 0 or a multiple of 64 up to {two_hop_window_cols()}, got {window_cols}")
+    return Q, n
+
+
+@_on_device
+def two_hop_diff_count(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, drop_self: bool = True,
+                       window_cols: int = 0) -> Tensor:
+    """count[q] = |(U_{m in A[s,:]} A[m,:]) \\ M[s,:]| for s = rows[q], without column s too under ``drop_self`` (ocn_hip.h:
+    ocn_two_hop_diff_count): int32 [Q] — ``row_diff_count`` of the pattern of A·A without that product.  ``window_cols``:
+    0, the library's window, except in tests of the sweep."""
+    Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols)
+    count = torch.empty(Q, dtype=torch.int32, device=rows.device)
+    if Q:
+        check(_lib.lib().ocn_two_hop_diff_count(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
+                                                int(bool(drop_self)), int(window_cols), ptr(count), stream_ptr()),
+              "ocn_two_hop_diff_count")
+        _mark("two_hop_diff_count")
+    return count
+
+
+@_on_device
+def two_hop_diff_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, off: Tensor,
+                      drop_self: bool = True, total: Optional[int] = None, window_cols: int = 0) -> Tensor:
+    """The pairs (s, c) of every query's set, ascending in c, row-major in int64 [T, 2] from ``off[q]`` on (ocn_hip.h:
+    ocn_two_hop_diff_fill).  ``off``, ``total``: as for ``row_diff_fill``."""
+    Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols)
+    if _req(off, torch.int64, "off", 1).numel() != Q + 1:
+        raise ValueError("off: one entry per query and the total")
+    T = _total(off[-1]) if total is None else int(total)
+    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    if Q and T:
+        check(_lib.lib().ocn_two_hop_diff_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
+                                               int(bool(drop_self)), int(window_cols), ptr(off), ptr(edges), stream_ptr()),
+              "ocn_two_hop_diff_fill")
+        _mark("two_hop_diff_fill")
+    return edges
+
+
 def segment_topk_max_k() -> int:
     return int(_lib.lib().ocn_segment_topk_max_k())
 

@@ -98,6 +98,62 @@ def score_edges(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     return scores
 
 
+def _score_walk(predictor, h: Tensor, adj, src_all: Tensor, dst_all: Tensor, batch_size: int, args, run_ahead, group) -> Tensor:
+    """The walk-route loop over the candidates (src_all[i], dst_all[i]): the body of ``score_edges_walk`` and of both halves of
+    ``score_mrr_split``.  ``run_ahead`` = None: no flow control (the MRR splits' loop, as it always ran)."""
+    from .utils import get_cn1_cn2
+    outs, done = [], []
+    if src_all.numel() == 0:
+        return h.new_zeros(0)
+    adj.warm(walk=True)            # (degree sums of the two-sided sweep: built on the caller's stream, before the side streams fork)
+    with ops.prevalidated(src_all, dst_all, adj.size(0), adj.size(0)):
+        perms = list(PermIterator(src_all.device, src_all.shape[0], batch_size, training=False))
+        mine, world = _dealt(perms, group)
+        graphed = _graphed(predictor, h, adj, lambda e: get_cn1_cn2(adj, e), batch_size, args, len(mine))
+
+        def begin(it):
+            e = torch.stack((src_all[perms[mine[it]]], dst_all[perms[mine[it]]]))
+            if graphed is not None:
+                return graphed.begin(it, e)
+            cn1, cn2 = get_cn1_cn2(adj, e)
+            return predictor.begin(h, adj, cn1, cn2, e, slot=it, args=args)
+
+        def flow(it):
+            if len(done) >= max(run_ahead, 1):
+                done.pop(0).synchronize()
+
+        fin = graphed.finish if graphed is not None else (lambda tok: predictor.finish(h, tok, args))
+        for out in overlapped_steps(begin, fin, len(mine), before_step=None if run_ahead is None else flow, batch=batch_size,
+                                    device=h.device):
+            outs.append(out.reshape(-1).clone() if graphed is not None else out.reshape(-1))
+            if run_ahead is not None:
+                done.append(torch.cuda.current_stream(h.device).record_event())
+    if world > 1:
+        from .dist import gather_dealt
+        scores = gather_dealt(outs, [int(p.numel()) for p in perms], None if group is True else group)
+    else:
+        scores = torch.cat(outs, dim=0)
+    predictor.check_errors()
+    return scores
+
+
+@torch.no_grad()
+def score_edges_walk(predictor, h: Tensor, adj, edges: Tensor, batch_size: int, args=None, run_ahead: int = 6,
+                     group=None) -> Tensor:
+    """The walk-route twin of ``score_edges``: scores for ``edges`` [n, 2] with every batch's cn1 / cn2 from
+    ``get_cn1_cn2(adj, e)`` (per-batch walk counts on A itself, as the ppa and citation2 drivers score) instead of a stored
+    A² — for graphs on which that product cannot be formed.  Batched like ``PermIterator(.., training=False)``, the host at
+    most ``run_ahead`` batches ahead of the GPU, ``group`` as in ``score_edges``; returns a [n] fp32 tensor on the device.
+    This is the loop ``score_mrr_split`` runs over its positives and its negatives: for the same candidates in the same order
+    at the same ``batch_size`` the scores are bit-equal.  cn2 carries walk counts here and a pattern in ``score_edges``, so
+    the two routes score the same candidate differently by design."""
+    if predictor.training:
+        raise RuntimeError("score_edges_walk is the eval path; call predictor.eval() first")
+    if edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be [n, 2]")
+    return _score_walk(predictor, h, adj, edges[:, 0], edges[:, 1], batch_size, args, run_ahead, group)
+
+
 @torch.no_grad()
 def score_mrr_split(predictor, h: Tensor, adj, source: Tensor, target: Tensor, target_neg: Tensor,
                     batch_size: int, args=None, evaluator=None, group=None):
@@ -108,37 +164,11 @@ def score_mrr_split(predictor, h: Tensor, adj, source: Tensor, target: Tensor, t
     or, with an ``evaluator``, the mean of its ``mrr_list``.  ``group``: whole batches dealt over the ranks, as in
     ``score_edges`` — the partition that suits the drivers' 2 048-candidate batches (a dense histogram all-reduce per such
     batch costs more link time than the batch costs compute)."""
-    from .utils import get_cn1_cn2
     if predictor.training:
         raise RuntimeError("score_mrr_split is the eval path; call predictor.eval() first")
 
     def run(src_all: Tensor, dst_all: Tensor) -> Tensor:
-        outs = []
-        if src_all.numel() == 0:
-            return h.new_zeros(0)
-        adj.warm(walk=True)            # (degree sums of the two-sided sweep: built on the caller's stream, before the side streams fork)
-        with ops.prevalidated(src_all, dst_all, adj.size(0), adj.size(0)):
-            perms = list(PermIterator(src_all.device, src_all.shape[0], batch_size, training=False))
-            mine, world = _dealt(perms, group)
-            graphed = _graphed(predictor, h, adj, lambda e: get_cn1_cn2(adj, e), batch_size, args, len(mine))
-
-            def begin(it):
-                e = torch.stack((src_all[perms[mine[it]]], dst_all[perms[mine[it]]]))
-                if graphed is not None:
-                    return graphed.begin(it, e)
-                cn1, cn2 = get_cn1_cn2(adj, e)
-                return predictor.begin(h, adj, cn1, cn2, e, slot=it, args=args)
-
-            fin = graphed.finish if graphed is not None else (lambda tok: predictor.finish(h, tok, args))
-            for out in overlapped_steps(begin, fin, len(mine), batch=batch_size, device=h.device):
-                outs.append(out.reshape(-1).clone() if graphed is not None else out.reshape(-1))
-        if world > 1:
-            from .dist import gather_dealt
-            scores = gather_dealt(outs, [int(p.numel()) for p in perms], None if group is True else group)
-        else:
-            scores = torch.cat(outs, dim=0)
-        predictor.check_errors()
-        return scores
+        return _score_walk(predictor, h, adj, src_all, dst_all, batch_size, args, None, group)
 
     pos_pred = run(source, target)
     n_neg = target_neg.shape[1]

@@ -7,6 +7,9 @@ made and return a flat score vector.  This module makes the pairs and picks from
   ``pattern(A² row s) \\ (N(s) ∪ {s})`` — any other target has empty ``cn1`` and ``cn2`` and is scored from ``x_i ⊙ x_j``
   alone.  ``two_hop_candidates`` enumerates that set difference row by row (``ops.row_diff_count`` -> ``ops.scan_i32`` ->
   ``ops.row_diff_fill``) straight into the [T, 2] layout the scoring loops take: no dense [Q, N] mask, no host loop;
+* where A² is not stored — more columns than the A·A pattern kernel takes, or a product too large to keep, the ppa and
+  citation2 shapes — ``adj2=None`` expands the same set from A itself (``ops.two_hop_diff_count`` / ``_fill``) and the
+  model scores it on the walk route (``pipeline.score_edges_walk``), as the drivers of those datasets score;
 * candidate lists are ragged — under a power law from a handful to tens of thousands per source — so the best ``k`` per
   source are selected segment by segment (``ops.segment_topk``) instead of padding to a [Q, max_len] rectangle.
 
@@ -30,7 +33,7 @@ def _check_k(k) -> int:
     return k
 
 
-def two_hop_candidates(adj: SparseTensor, adj2: SparseTensor, sources: Tensor,
+def two_hop_candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor,
                        known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
     """The candidate targets of ``sources`` (int64 [Q]; a source may repeat): for each source ``s``, in source order, the
     columns of row ``s`` of ``adj2`` that are neither ``s`` nor in row ``s`` of ``known``, ascending.  Returns
@@ -42,20 +45,32 @@ def two_hop_candidates(adj: SparseTensor, adj2: SparseTensor, sources: Tensor,
     ``adj``'s size.  Reading the CSR of ``adj2`` forces the deferred passes of a product: the fill pass of ``A @ A`` whose
     column ids were left for later, and the counting pass as well of a product formed under autograd.
 
+    ``adj2=None``: row ``s`` of the pattern of A·A is expanded from ``adj`` on the fly (the union of the rows of the
+    neighbours of ``s``; ``ops.two_hop_diff_*``) — the same pairs as with the materialised product, for a graph of any size:
+    neither the column limit of the A·A pattern kernel nor the memory of A² applies.  It redoes per call the expansion that a
+    stored A² holds ready.
+
     ``sources`` are bounds-checked once (one host sync); the output size costs a second one."""
     known = adj if known is None else known
     if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
         raise ValueError("sources must be a 1-d int64 tensor of node ids")
     n = adj.size(0)
     for name, m in (("adj", adj), ("adj2", adj2), ("known", known)):
-        if tuple(m.sparse_sizes()) != (n, n):
+        if m is not None and tuple(m.sparse_sizes()) != (n, n):
             raise ValueError(f"{name} is {tuple(m.sparse_sizes())}, expected the square size ({n}, {n}) of adj")
     sources = sources.contiguous()
-    rp2, col2, rpk, colk = adj2._rowptr, adj2._col, known._rowptr, known._col
+    rpk, colk = known._rowptr, known._col
     with ops.prevalidated(sources, sources, n, n):
-        count = ops.row_diff_count(rp2, col2, rpk, colk, sources, drop_self=True)
-        ptr = ops.scan_i32(count)
-        edges = ops.row_diff_fill(rp2, col2, rpk, colk, sources, ptr, drop_self=True)
+        if adj2 is None:
+            rpa, cola = adj._rowptr, adj._col
+            count = ops.two_hop_diff_count(rpa, cola, rpk, colk, sources, drop_self=True)
+            ptr = ops.scan_i32(count)
+            edges = ops.two_hop_diff_fill(rpa, cola, rpk, colk, sources, ptr, drop_self=True)
+        else:
+            rp2, col2 = adj2._rowptr, adj2._col
+            count = ops.row_diff_count(rp2, col2, rpk, colk, sources, drop_self=True)
+            ptr = ops.scan_i32(count)
+            edges = ops.row_diff_fill(rp2, col2, rpk, colk, sources, ptr, drop_self=True)
     return ptr, edges
 
 
@@ -75,8 +90,8 @@ def _select(scores: Tensor, ptr: Tensor, edges: Tensor, k: int) -> Tuple[Tensor,
 
 
 @torch.no_grad()
-def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: SparseTensor, sources: Tensor, k: int, batch_size: int,
-                    args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6) -> Tuple[Tensor, Tensor]:
+def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, k: int,
+                    batch_size: int, args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6) -> Tuple[Tensor, Tensor]:
     """The ``k`` best predicted links of every source: (``dst`` int64 [Q, k], ``score`` float32 [Q, k]), best first, ``dst``
     = -1 and ``score`` = -inf where a source has fewer than ``k`` candidates.
 
@@ -85,21 +100,32 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: SparseTensor,
     The normalisation of cn5 and cn7 couples the candidates of a batch, so the contract is stated in terms of that call:
     the scores are exactly those ``score_edges`` returns for the flat candidate list at this ``batch_size``.  Another set of
     ``sources`` or another ``batch_size`` puts other candidates into a batch and changes cn5 / cn7 scores — as it does in the
-    reference's ``test()``.  Ties go to the lower node id (candidates are in ascending order)."""
-    from .pipeline import score_edges
+    reference's ``test()``.  Ties go to the lower node id (candidates are in ascending order).
+
+    ``adj2=None``: the candidates come from ``adj`` alone and the one scoring call is
+    ``pipeline.score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)``; the contract is the same sentence
+    with that call in it.  The candidate LIST is the one a materialised A² gives; the SCORES are not those of the pattern
+    route: on the walk route cn2 carries walk counts (``utils.get_cn1_cn2``, the route of the ppa and citation2 drivers), by
+    design, so the two routes may rank a source's candidates differently."""
+    from .pipeline import score_edges, score_edges_walk
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
     ptr, edges = two_hop_candidates(adj, adj2, sources, known)
-    scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
+    if adj2 is None:
+        scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
+    else:
+        scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
     return _select(scores, ptr, edges, k)
 
 
 @torch.no_grad()
-def recommend_links_heuristic(adj: SparseTensor, adj2: SparseTensor, sources: Tensor, k: int, batch_size: int, kind: str,
-                              known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+def recommend_links_heuristic(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, k: int, batch_size: int,
+                              kind: str, known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
     """``recommend_links`` with one training-free heuristic (``heuristics.score_edges_heuristic``) in place of a model.  A
-    heuristic score depends on its candidate alone: the result does not change with ``batch_size`` or with the other sources."""
+    heuristic score depends on its candidate alone: the result does not change with ``batch_size`` or with the other sources.
+    ``adj2=None`` serves the 1-hop kinds (cn, aa, ra, jaccard, pa), which never read A²: same candidates, same scores as with
+    the product given.  The 2-hop kinds intersect with the rows of ``adj2`` and refuse None."""
     from .heuristics import _check_kinds, score_edges_heuristic
     _check_kinds((kind,), adj2)
     k = _check_k(k)
