@@ -12,6 +12,8 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
+    python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
+    python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
 """
 import argparse
 import os
@@ -25,7 +27,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
+from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
+from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
 from ocn_amd.utils import PermIterator, adjoverlap, sparse_tensor_multiply          # noqa: E402
@@ -38,12 +42,16 @@ def build_adj2(adj, args):
     return SparseTensor.from_torch_sparse_coo_tensor(spadj @ spadj, False)
 
 
-def train(model, predictor, data, split_edge, optimizer, batch_size, maskinput, args):
+def train(model, predictor, data, split_edge, optimizer, batch_size, maskinput, args, epoch=0):
     model.train(); predictor.train()
     pos_train_edge = split_edge['train']['edge'].to(data.x.device).t()
     total_loss = []
     adjmask = torch.ones_like(pos_train_edge[0], dtype=torch.bool)
-    negedge = torch.randint(0, data.num_nodes, pos_train_edge.shape, device=pos_train_edge.device)
+    if args.structured_negatives:
+        # non-edges only, as the reference's negative_sampling call returns them (NeighborOverlap_large.py:51); one draw per epoch
+        negedge = negative_edges(data.adj_t, pos_train_edge.shape[1], seed=epoch)
+    else:
+        negedge = torch.randint(0, data.num_nodes, pos_train_edge.shape, device=pos_train_edge.device)
     for perm in PermIterator(adjmask.device, adjmask.shape[0], batch_size):
         optimizer.zero_grad()
         if maskinput:
@@ -100,6 +108,25 @@ def test(model, predictor, data, split_edge, evaluator, batch_size, use_valedges
                 for p, n in (("pos_train", "neg_valid"), ("pos_valid", "neg_valid"), ("pos_test", "neg_test"))]
         results[f'Hits@{K}'] = tuple(hits)
     return results, h
+
+
+@torch.no_grad()
+def test_mrr(model, predictor, data, split_edge, evaluator, batch_size, use_valedges_as_input, args):
+    """The citation2 evaluation (NeighborOverlapCitation2.py:227-254): per positive (source, target) the negatives that share
+    its source, scored on the walk route by ``pipeline.score_mrr_split``; the mean reciprocal rank of valid and test.  The
+    negatives are the split's own (uniform random targets), or with --structured-negatives as many per source from
+    ``negative_targets(data.full_adj_t, ..)``: never the source itself and never a link the model has seen."""
+    model.eval(); predictor.eval()
+    dev = data.x.device
+    out = []
+    for seed, (split, adj) in enumerate((("valid", data.adj_t), ("test", data.full_adj_t if use_valedges_as_input else data.adj_t))):
+        source = split_edge[split]['edge'][:, 0].to(dev).contiguous()
+        target = split_edge[split]['edge'][:, 1].to(dev).contiguous()
+        neg = split_edge[split]['edge_neg'][..., 1].to(dev).contiguous()
+        if args.structured_negatives:
+            neg = negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
+        out.append(score_mrr_split(predictor, model(data.x, adj), adj, source, target, neg, batch_size, args, evaluator))
+    return {'MRR': tuple(out)}, None
 
 
 @torch.no_grad()
@@ -165,6 +192,9 @@ def main(argv=None):
     ap.add_argument("--heuristic", default=None, choices=KINDS, help="skip training: print the dataset's metric for this link heuristic")
     ap.add_argument("--recommend", type=int, default=0, metavar="K",
                     help="after the last epoch (at once with --heuristic): print the top-K predicted targets of the first few test sources")
+    ap.add_argument("--structured-negatives", action="store_true",
+                    help="draw the training negatives (and citation2's evaluation negatives) from the non-edges on the device "
+                         "(ocn_amd.sampling) instead of torch.randint pairs, which can be links")
     ap.add_argument("--recommend-walk", action="store_true",
                     help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
     args = ap.parse_args(argv)
@@ -196,13 +226,15 @@ def main(argv=None):
     out = []
     for epoch in range(1, 1 + args.epochs):
         t1 = time.time()
-        loss = train(model, predictor, data, split_edge, optimizer, args.batch_size, args.maskinput, args)
+        loss = train(model, predictor, data, split_edge, optimizer, args.batch_size, args.maskinput, args, epoch)
         t2 = time.time()
-        results, _ = test(model, predictor, data, split_edge, evaluator, args.testbs, args.use_valedges_as_input, args)
+        run_test = test_mrr if evaluator.eval_metric == "mrr" else test
+        results, _ = run_test(model, predictor, data, split_edge, evaluator, args.testbs, args.use_valedges_as_input, args)
         torch.cuda.synchronize()
         t3 = time.time()
         line = (f"epoch {epoch:3d} loss {loss:.4f} train {t2 - t1:.2f}s test {t3 - t2:.2f}s  " +
-                "  ".join(f"{k} train/valid/test {v[0]:.3f}/{v[1]:.3f}/{v[2]:.3f}" for k, v in results.items()))
+                "  ".join(f"{k} {'train/valid/test' if len(v) == 3 else 'valid/test'} " + "/".join(f"{x:.3f}" for x in v)
+                          for k, v in results.items()))
         print(line, flush=True)
         out.append((loss, results))
     if args.recommend:

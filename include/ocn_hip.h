@@ -39,7 +39,8 @@ extern "C" {
  *    ocn_spmm_max_backward (max aggregation under autograd); ocn_spmm_csr's max mode takes the entry values (val);
  *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums;
  *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation); ocn_two_hop_diff_count / _fill (its candidates
- *    expanded from A, where A² is not stored). */
+ *    expanded from A, where A² is not stored); ocn_philox4x32, ocn_complement_count, ocn_sample_stage_cols,
+ *    ocn_sample_complement_rows, ocn_sample_complement_pairs (structured negative sampling). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -397,6 +398,49 @@ int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int
 int32_t ocn_segment_topk_max_k(void);
 int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t k, float* top_val, int64_t* top_pos,
                      void* stream);
+
+/* Structured negative sampling (ocn_amd/sampling.py): pairs that are guaranteed not to be links of a square `known` matrix
+ * (sorted, duplicate-free int32 columns, n_cols rows and columns, 1 <= n_cols < 2^31), drawn exactly uniformly, with
+ * replacement, without a rejection loop — a hub row or a dense graph costs what a sparse one does.  Where the reference
+ * calls PyG's negative_sampling (NeighborOverlap_large.py:51, NeighborOverlap_large_ppa.py:67) these entries draw on the device from the CSR the
+ * scoring loops read.
+ *
+ * For a row s the excluded set is X(s) = known[s,:] U {s} — s is counted once, whether or not the row stores it — and its
+ * complement C(s) has m_s = n_cols - |X(s)| members.  The r-th smallest member of C(s) (0-based) is r + i, where i is the
+ * smallest index with x_i - i > r over the ascending members x_0 < x_1 < ... of X(s), and |X(s)| if there is none: a binary
+ * search on the row.
+ *
+ * Random words: Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85; ten rounds), key = (seed & 0xffffffff, seed >> 32).  A draw takes u = out[0] | out[1] << 32 of one counter and
+ * r = floor(u * m / 2^64) (the high word of the 128-bit product: a bias below m / 2^64).  Counters:
+ *   per-source sample j of query q : (j, q & 0xffffffff, q >> 32, 2)
+ *   pair sample t                  : (t & 0xffffffff, t >> 32, 0, 1)
+ * so a sample is a function of (seed, its own index, known) and of nothing else — not of the launch geometry, not of per, Q
+ * or T.  No atomics, no workspace, the output is fixed by the input.
+ *
+ * ocn_philox4x32: out[i] = Philox4x32-10(ctr[i], (key0, key1)), the generator itself; ctr and out 16-byte aligned.
+ * ocn_complement_count: count[s] = m_s for every row; ocn_scan_i32 of it gives the int64 prefix cptr[n_cols + 1], whose last
+ *   entry is M, the number of ordered non-edge, non-self pairs.
+ * ocn_sample_complement_rows: out[q][j] (int64 [Q][per], 1 <= per < 2^31) = the member of C(rows[q]) selected by the counter
+ *   of (q0 + q, j), or -1 where m_s == 0.  q0 >= 0 lets a caller produce a long split in chunks with identical results.  A
+ *   wave owns one (query, 64-sample chunk): it stages the row in LDS when it has at most ocn_sample_stage_cols() columns
+ *   (searched in memory beyond) and stores 64 consecutive samples.  rows[] must be valid row ids (not checked here).
+ * ocn_sample_complement_pairs: sample t0 + t draws r in [0, M) with M = cptr[n_cols]; its row s is the last row with
+ *   cptr[s] <= r (a row with an empty complement is never chosen), its column the member of C(s) of rank r - cptr[s]:
+ *   uniform over the ordered non-edge, non-self pairs.  out (int64 [2][T]) = sources, then targets: the layout of tar_ei.
+ *   One thread per sample.  M == 0 is the caller's to refuse: the kernel then writes -1 and searches nothing.
+ * NULL pointers, Q / T / n < 0, q0 / t0 < 0, n_cols outside 1 .. 2^31 - 1, per outside 1 .. 2^31 - 1: OCN_EINVAL before any
+ * HIP call.  Q == 0, T == 0, n == 0 return 0 (after the checks). */
+int ocn_philox4x32(const uint32_t* ctr /* [n][4] */, uint32_t key0, uint32_t key1, int64_t n, uint32_t* out /* [n][4] */,
+                   void* stream);
+int ocn_complement_count(const int64_t* rowptrK, const int32_t* colK, int64_t n_cols, int32_t* count /* [n_cols] */,
+                         void* stream);
+int32_t ocn_sample_stage_cols(void);
+int ocn_sample_complement_rows(const int64_t* rowptrK, const int32_t* colK, int64_t n_cols, const int64_t* rows, int64_t Q,
+                               int64_t per, int64_t q0, uint64_t seed, int64_t* out /* [Q][per] */, void* stream);
+int ocn_sample_complement_pairs(const int64_t* rowptrK, const int32_t* colK, int64_t n_cols,
+                                const int64_t* cptr /* [n_cols + 1] */, int64_t T, int64_t t0, uint64_t seed,
+                                int64_t* out /* [2][T] */, void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

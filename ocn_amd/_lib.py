@@ -66,6 +66,11 @@ SIGNATURES = {
     "ocn_two_hop_diff_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, _P]),
     "ocn_segment_topk_max_k": (c_int32, []),
     "ocn_segment_topk": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
+    "ocn_philox4x32": (c_int32, [_P, ctypes.c_uint32, ctypes.c_uint32, c_int64, _P, _P]),
+    "ocn_complement_count": (c_int32, [_P, _P, c_int64, _P, _P]),
+    "ocn_sample_stage_cols": (c_int32, []),
+    "ocn_sample_complement_rows": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int64, c_int64, ctypes.c_uint64, _P, _P]),
+    "ocn_sample_complement_pairs": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int64, ctypes.c_uint64, _P, _P]),
     "ocn_gather_schedule": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "ocn_coo_to_csr_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     "ocn_coo_to_csr": (c_int32, [_P, _P, c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

@@ -780,6 +780,101 @@ def segment_topk(scores: Tensor, seg_ptr: Tensor, k: int) -> Tuple[Tensor, Tenso
     return val, pos
 
 
+@_on_device
+def philox4x32(ctr: Tensor, key0: int, key1: int) -> Tensor:
+    """Philox4x32-10 of every counter row (ocn_hip.h: ocn_philox4x32): ``ctr`` int32 [n, 4] holds the bit patterns of the four
+    uint32 counter words, ``key0`` / ``key1`` are the key words (0 .. 2^32 - 1); returns the four output words, int32 [n, 4]
+    bit patterns again.  The generator of the samplers below, exposed so that its stream of words can be pinned on its own."""
+    _req(ctr, torch.int32, "ctr", 2)
+    if ctr.shape[1] != 4:
+        raise ValueError(f"ctr: expected [n, 4], got {tuple(ctr.shape)}")
+    key0, key1 = int(key0), int(key1)
+    if not (0 <= key0 < (1 << 32) and 0 <= key1 < (1 << 32)):
+        raise ValueError("key words must be in 0 .. 2^32 - 1")
+    out = torch.empty_like(ctr)
+    if ctr.shape[0]:
+        check(_lib.lib().ocn_philox4x32(ptr(ctr), key0, key1, ctr.shape[0], ptr(out), stream_ptr()), "ocn_philox4x32")
+        _mark("philox4x32")
+    return out
+
+
+def sample_stage_cols() -> int:
+    """Columns of a row ``ocn_sample_complement_rows`` stages in LDS; longer rows are searched in memory."""
+    return int(_lib.lib().ocn_sample_stage_cols())
+
+
+def _known_args(rowptrK: Tensor, colK: Tensor) -> int:
+    """The operand checks of the samplers' ``known`` matrix: square (its size is its row count), 1 .. 2^31 - 1 rows.  Its columns
+    must be sorted and duplicate-free in every row, as every ``SparseTensor`` of the project stores them."""
+    _req(rowptrK, torch.int64, "rowptrK", 1); _req(colK, torch.int32, "colK", 1)
+    n = rowptrK.numel() - 1
+    if not 0 < n < (1 << 31):
+        raise ValueError(f"known has {n} rows: int32 columns serve 1 .. 2^31 - 1")
+    return n
+
+
+def _seed(seed: int) -> int:
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("seed must be in 0 .. 2^64 - 1")
+    return seed
+
+
+@_on_device
+def complement_count(rowptrK: Tensor, colK: Tensor) -> Tensor:
+    """count[s] = n - |known[s,:] U {s}| for every row of the square ``known`` (ocn_hip.h: ocn_complement_count): int32 [n].
+    ``scan_i32`` of it gives the prefix ``sample_complement_pairs`` searches."""
+    n = _known_args(rowptrK, colK)
+    count = torch.empty(n, dtype=torch.int32, device=rowptrK.device)
+    check(_lib.lib().ocn_complement_count(ptr(rowptrK), ptr(colK), n, ptr(count), stream_ptr()), "ocn_complement_count")
+    _mark("complement_count")
+    return count
+
+
+@_on_device
+def sample_complement_rows(rowptrK: Tensor, colK: Tensor, rows: Tensor, per: int, seed: int, first: int = 0) -> Tensor:
+    """``per`` uniform draws, with replacement, from the columns outside ``known[s,:] U {s}`` for every s = rows[q] (ocn_hip.h:
+    ocn_sample_complement_rows): int64 [Q, per], -1 where nothing is left outside.  Sample j of query q is fixed by
+    (seed, first + q, j, known) alone."""
+    n = _known_args(rowptrK, colK)
+    _req(rows, torch.int64, "rows", 1)
+    per, first = int(per), int(first)
+    if not 1 <= per < (1 << 31):
+        raise ValueError(f"per must be in 1 .. 2^31 - 1, got {per}")
+    if first < 0:
+        raise ValueError(f"first must not be negative, got {first}")
+    seed = _seed(seed)
+    check_edges(rows, rows, n, n)
+    Q = rows.numel()
+    out = torch.empty(Q, per, dtype=torch.int64, device=rows.device)
+    if Q:
+        check(_lib.lib().ocn_sample_complement_rows(ptr(rowptrK), ptr(colK), n, ptr(rows), Q, per, first, seed, ptr(out),
+                                                    stream_ptr()), "ocn_sample_complement_rows")
+        _mark("sample_complement_rows")
+    return out
+
+
+@_on_device
+def sample_complement_pairs(rowptrK: Tensor, colK: Tensor, cptr: Tensor, num: int, seed: int, first: int = 0) -> Tensor:
+    """``num`` uniform draws, with replacement, from the ordered pairs (s, c), c outside ``known[s,:] U {s}`` (ocn_hip.h:
+    ocn_sample_complement_pairs): int64 [2, num], sources then targets.  ``cptr``: ``scan_i32(complement_count(...))`` of the
+    same matrix; a total ``cptr[-1]`` of 0 is the caller's to refuse (the kernel then writes -1).  Sample t is fixed by
+    (seed, first + t, known) alone."""
+    n = _known_args(rowptrK, colK)
+    if _req(cptr, torch.int64, "cptr", 1).numel() != n + 1:
+        raise ValueError("cptr: one entry per row and the total")
+    num, first = int(num), int(first)
+    if num < 0 or first < 0:
+        raise ValueError(f"num and first must not be negative, got {num}, {first}")
+    seed = _seed(seed)
+    out = torch.empty(2, num, dtype=torch.int64, device=rowptrK.device)
+    if num:
+        check(_lib.lib().ocn_sample_complement_pairs(ptr(rowptrK), ptr(colK), n, ptr(cptr), num, first, seed, ptr(out),
+                                                     stream_ptr()), "ocn_sample_complement_pairs")
+        _mark("sample_complement_pairs")
+    return out
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 
