@@ -4,20 +4,6 @@
 // See include/ocn_hip.h (ocn_cn8_pool).
 #include "common.h"
 
-// membership of key in the sorted row a[0..n) (memory): the lanes of a group search the same row, so the top of the
-// tree is shared cache lines
-__device__ __forceinline__ bool cn8_row_has(const int32_t* __restrict__ a, i64 n, int32_t key) {
-  i64 lo = 0, hi = n;
-  bool found = false;
-  while (lo < hi) {
-    const i64 mid = (lo + hi) >> 1;
-    const int32_t v = a[mid];
-    found |= (v == key);
-    if (v < key) lo = mid + 1; else hi = mid;
-  }
-  return found;
-}
-
 constexpr int CN8_UNR = 4;      // embedding rows in flight per lane group
 
 // LPE lanes cooperate on one candidate (64 / LPE candidates per wave); a lane owns NV float4 of the H = LPE * NV * 4
@@ -39,10 +25,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn8_pool_kernel(
   const int lane = threadIdx.x & 63;
   const int gl = lane % LPE;
   const int gbase = lane - gl;
-  // workgroups are dealt round-robin over the 8 XCDs: every XCD takes one contiguous eighth of the processing order
-  // (candidates with neighbouring sources then share an L2), as the pooling of cn5 / cn7 does
-  i64 bid = blockIdx.x;
-  if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+  const i64 bid = xcd_block();           // an XCD's eighth of the processing order, as the pooling of cn5 / cn7 takes
   const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
   if (slot >= B) return;                    // whole group leaves together
   const i64 e = order ? order[slot] : slot;
@@ -71,8 +54,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn8_pool_kernel(
     for (int t = 0; t < PT; ++t) {
       f[t] = 0;
       if (k[t] >= 0) {
-        const bool f1 = bm1_row ? ((bm1_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : cn8_row_has(colT1 + b0, db, k[t]);
-        const bool f2 = bm2_row ? ((bm2_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : cn8_row_has(colT2 + c0, dc, k[t]);
+        const bool f1 = bm1_row ? ((bm1_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : sorted_has(colT1 + b0, db, k[t]);
+        const bool f2 = bm2_row ? ((bm2_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : sorted_has(colT2 + c0, dc, k[t]);
         f[t] = (f1 ? OCN_F_CN1 : 0u) | (f2 ? OCN_F_CN2 : 0u);
         c1 += f1;
         c2 += f2;
@@ -162,14 +145,7 @@ int ocn_cn8_pool(const int64_t* rowptrA, const int32_t* colA,
                        (i64)bm2_stride_words, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B, h,      \
                        (int)H, xcn1, xcn2, xij, cnt1, cnt2);                                                       \
   } while (0)
-  switch (H) {
-    case 16: LAUNCH_CN8(4, 1); break;
-    case 32: LAUNCH_CN8(8, 1); break;
-    case 64: LAUNCH_CN8(16, 1); break;
-    case 128: LAUNCH_CN8(32, 1); break;
-    case 256: LAUNCH_CN8(64, 1); break;
-    default: LAUNCH_CN8(64, 2); break;
-  }
+  OCN_SWITCH_WIDTH(H, LAUNCH_CN8)
 #undef LAUNCH_CN8
   return launch_status();
 }

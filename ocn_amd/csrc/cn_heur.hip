@@ -13,6 +13,7 @@ constexpr int HEUR_EPB = OCN_WPB * HEUR_GPW;     // candidates per workgroup
 // membership of key in the sorted row a[0..n): the largest q with a[q] <= key is found in a number of steps that depends
 // on n alone — the lanes of a group search the same row, so they stay together — and every load is unconditional and in
 // bounds for any key (a key of -1, a lane without a position, is simply not found)
+// (not common.h's sorted_has: that one's trip count and branches depend on the key, and it has no load for an empty lane)
 __device__ __forceinline__ bool heur_row_has(const int32_t* __restrict__ a, i64 n, int32_t key) {
   if (n <= 0) return false;
   i64 base = 0;
@@ -46,10 +47,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_node_sums_kernel(
   const int lane = threadIdx.x & 63;
   const int gl = lane % HEUR_LPE;
   const int gbase = lane - gl;
-  // workgroups are dealt round-robin over the 8 XCDs: every XCD takes one contiguous eighth of the processing order
-  // (candidates with neighbouring sources then share an L2), as cn8_pool_kernel does
-  i64 bid = blockIdx.x;
-  if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+  const i64 bid = xcd_block();           // an XCD's eighth of the processing order, as cn8_pool_kernel takes
   const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * HEUR_GPW + lane / HEUR_LPE;
   if (slot >= B) return;                    // whole group leaves together
   const i64 e = order ? order[slot] : slot;

@@ -15,10 +15,23 @@ typedef unsigned long long u64;
 // instead of three 32-bit ones), walks = sum of the walk counts of column c (valued cn2 only).
 #define HF_BITS 21
 #define HF_MASK ((1ull << HF_BITS) - 1ull)
-#define REC_LEN_SHIFT 40                     /* slot record word 2 (ocn_hip.h: ocn_cn_flags `rec`): row start (nnz < 2^40) | row length << 40 */
 __device__ __forceinline__ int hf_n1(u64 w) { return (int)(w & HF_MASK); }
 __device__ __forceinline__ int hf_n2(u64 w) { return (int)((w >> HF_BITS) & HF_MASK); }
 __device__ __forceinline__ int hf_nu(u64 w) { return (int)((w >> (2 * HF_BITS)) & HF_MASK); }
+
+// ---------------------------------------------------------------------------------------------
+// the contract between the intersection pass (cn_flags.hip; scan.hip writes the record's first half) and the pooling
+// (cn_pool.hip): the slot record layout and the schedule's cost unit
+// ---------------------------------------------------------------------------------------------
+#define REC_LEN_SHIFT 40                     /* slot record word 2 (ocn_hip.h: ocn_cn_flags `rec`): row start (nnz < 2^40) | row length << 40 */
+#define REC_FULL2_BIT 61     /* record word 3: every position of the source row is a cn2 entry (cnt2 == row length) */
+// a group's cost: the largest entry count among its four candidates (a wave walks one candidate), in buckets of 32 —
+// measured at the collab shape (pooling): sum / max and 4 .. 256-entry buckets all land within
+// 0.184 - 0.200 ms against 0.206 unscheduled; coarse buckets keep more of the source order's L2 locality
+#define SCHED_COST(t, c) ((t) > (c) ? (t) : (c))
+constexpr int SCHED_SHIFT = 5;
+constexpr int POOL_LPE = 64;    /* lanes per candidate of the H = 256 pooling (64: one candidate per wave) */
+#define SCHED_GROUP OCN_WPB    /* slots per scheduling group: a workgroup of the intersection pass == one of the H = 256 pooling */
 
 // cn5 / cn6: nip = innerprod / scale from the column statistics word (cn5_column_stats: 0 = no union entry,
 // -1 = union entries but no column with n1 >= 2, else min{n1 >= 2} - INT_MAX - 1); model.py:2370-2376
@@ -43,6 +56,19 @@ static inline int grid_for(i64 items_per_block_units, i64 cap = (1 << 20)) {
   i64 g = items_per_block_units < 1 ? 1 : items_per_block_units;
   return (int)(g > cap ? cap : g);
 }
+
+// H -> (LPE lanes per row, NV float4 per lane) of the kernels whose lane groups own a row of H = LPE * NV * 4 features:
+// M(LPE, NV) launches the instance; any other width is refused (host code)
+#define OCN_SWITCH_WIDTH(H, M)           \
+  switch (H) {                           \
+    case 16:  M(4, 1); break;            \
+    case 32:  M(8, 1); break;            \
+    case 64:  M(16, 1); break;           \
+    case 128: M(32, 1); break;           \
+    case 256: M(64, 1); break;           \
+    case 512: M(64, 2); break;           \
+    default: return OCN_EINVAL;          \
+  }
 
 // ---------------------------------------------------------------------------------------------
 // wave / block primitives
@@ -81,6 +107,41 @@ __device__ __forceinline__ i64 block_excl_scan(i64 v, i64* sh, i64* total) {
   __syncthreads();
   *total = tot;
   return base + inc - v;
+}
+
+// orders a wave's own LDS writes before its own LDS reads (and the reverse, for the next item's writes): LDS executes a
+// wave's instructions in order, so only the compiler has to be kept from moving them
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  The candidates are visited in source-node
+// order, so give every XCD one contiguous eighth of that order: candidates with neighbouring sources then share an L2
+// instead of being spread over all eight.  Returns the workgroup's place in that order (blockIdx.x where the grid is
+// no multiple of eight).
+__device__ __forceinline__ i64 xcd_block() {
+  i64 bid = blockIdx.x;
+  if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+  return bid;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sorted-list membership
+// ---------------------------------------------------------------------------------------------
+// Branch-uniform binary search over a[0..n) (global or LDS): every lane of a wave searches the same
+// row, so the trip count is wave-uniform and the top levels of the tree are shared cache lines.
+template <typename P>
+__device__ __forceinline__ bool sorted_has(P a, i64 n, int32_t key) {
+  i64 lo = 0, hi = n;
+  bool found = false;
+  while (lo < hi) {
+    const i64 mid = (lo + hi) >> 1;
+    const int32_t v = a[mid];
+    found |= (v == key);
+    if (v < key) lo = mid + 1; else hi = mid;
+  }
+  return found;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -243,17 +243,6 @@ static inline unsigned ln_thresh(float p) {
 #define LN_BWD_GROUPS 4096
 int64_t ocn_ln_drop_relu_workspace_bytes(int32_t H) { return (int64_t)LN_BWD_GROUPS * 2 * H * (int64_t)sizeof(float); }
 
-#define LN_DISPATCH(M)                   \
-  switch (H) {                           \
-    case 16:  M(4, 1); break;            \
-    case 32:  M(8, 1); break;            \
-    case 64:  M(16, 1); break;           \
-    case 128: M(32, 1); break;           \
-    case 256: M(64, 1); break;           \
-    case 512: M(64, 2); break;           \
-    default: return OCN_EINVAL;          \
-  }
-
 int ocn_ln_drop_relu_forward(const float* x, const float* gamma, const float* beta, float eps, float p, uint64_t seed, int32_t relu,
                              int64_t rows, int32_t H, float* y, float* stats, void* stream) {
   if (rows < 0 || H <= 0 || !(p >= 0.f) || p >= 1.f || (gamma != nullptr) != (beta != nullptr)) return OCN_EINVAL;
@@ -267,7 +256,7 @@ int ocn_ln_drop_relu_forward(const float* x, const float* gamma, const float* be
     hipLaunchKernelGGL((ln_drop_relu_fwd_kernel<LPE, NV>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(OCN_BLOCK), 0, \
                        (hipStream_t)stream, x, gamma, beta, eps, th, scale, (u64)seed, (int)relu, (i64)rows, (int)H, y, stats); \
   } while (0)
-  LN_DISPATCH(LN_FWD)
+  OCN_SWITCH_WIDTH(H, LN_FWD)
 #undef LN_FWD
   return launch_status();
 }
@@ -288,7 +277,7 @@ int ocn_ln_drop_relu_backward(const float* g, const float* x, const float* y, co
     hipLaunchKernelGGL((ln_drop_relu_bwd_kernel<LPE, NV>), dim3((unsigned)(LN_BWD_GROUPS / gpb)), dim3(OCN_BLOCK), 0,    \
                        (hipStream_t)stream, g, x, y, stats, gamma, th, scale, (u64)seed, (int)relu, (i64)rows, (int)H, chunk, dx, part); \
   } while (0)
-  LN_DISPATCH(LN_BWD)
+  OCN_SWITCH_WIDTH(H, LN_BWD)
 #undef LN_BWD
   if (gamma) {
     // column groups of 64 over [dgamma | dbeta]; widths below 64 take one group per vector (lanes beyond H idle)

@@ -100,15 +100,7 @@ int ocn_rows_ln_relu(const float* x, const float* gamma, const float* beta, floa
   if (rows < 0 || H <= 0) return OCN_EINVAL;
   if (rows == 0) return 0;
   if (!x || !gamma || !beta || !y) return OCN_EINVAL;
-  switch (H) {
-    case 16:  LAUNCH_LN(4, 1); break;
-    case 32:  LAUNCH_LN(8, 1); break;
-    case 64:  LAUNCH_LN(16, 1); break;
-    case 128: LAUNCH_LN(32, 1); break;
-    case 256: LAUNCH_LN(64, 1); break;
-    case 512: LAUNCH_LN(64, 2); break;
-    default: return OCN_EINVAL;
-  }
+  OCN_SWITCH_WIDTH(H, LAUNCH_LN)
   return launch_status();
 }
 

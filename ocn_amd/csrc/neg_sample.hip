@@ -37,6 +37,7 @@ __device__ __forceinline__ u64 sample_rank(uint4 ctr, u64 seed, u64 m) {
 // ---------------------------------------------------------------------------------------------
 // number of leading positions k of the sorted row a[0..n) with a[k] - k <= r  (= the first index i with a[i] - i > r, n if
 // there is none).  The steps depend on n alone and every load is in bounds for any r.
+// (not common.h's sorted_has: it searches the derived sequence a[k] - k and returns a count, in fixed trips)
 template <typename Row>
 __device__ __forceinline__ i64 free_below(Row a, i64 n, i64 r) {
   i64 at = 0;
@@ -50,6 +51,7 @@ __device__ __forceinline__ i64 free_below(Row a, i64 n, i64 r) {
 }
 
 // position of `key` in the sorted row (the number of columns below it) and whether the row stores it
+// (not common.h's sorted_has: it returns the position beside the membership, in fixed trips with in-bounds loads)
 template <typename Row>
 __device__ __forceinline__ i64 row_lower_bound(Row a, i64 n, i64 key, bool& found) {
   i64 at = 0;
@@ -109,13 +111,6 @@ __global__ __launch_bounds__(OCN_BLOCK) void complement_count_kernel(const i64* 
 // its search tree stays in L1 / L2 for the wave's 64 lanes.
 constexpr int NS_STAGE = 512;
 
-// orders a wave's own LDS writes before its own LDS reads (and the reverse, for the next item's writes): LDS executes a wave's
-// instructions in order, so only the compiler has to be kept from moving them
-__device__ __forceinline__ void ns_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // A wave owns one (query, 64-sample chunk): it stages the query's row once, every lane draws one word and searches the row
 // for its own rank, and the wave stores 64 consecutive int64 (512 contiguous bytes).  No workgroup barrier anywhere: the item
 // loop runs on the wave's index and kernel arguments alone.
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void sample_rows_kernel(
     const bool staged = d <= NS_STAGE;
     if (staged) {
       for (i64 t = lane; t < d; t += OCN_WAVE) sr[t] = col[k0 + t];
-      ns_wave_lds_sync();
+      wave_lds_sync();
     }
     const SelfSplice sp = staged ? splice_self(sr, d, s, n_cols) : splice_self(col + k0, d, s, n_cols);
     const u64 qq = (u64)(q0 + q);
@@ -144,7 +139,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void sample_rows_kernel(
       v = staged ? complement_select(sr, d, sp, r) : complement_select(col + k0, d, sp, r);
     }
     if (j < per) out[q * per + j] = v;
-    if (staged) ns_wave_lds_sync();                          // the next item's staging writes stay behind this one's reads
+    if (staged) wave_lds_sync();                          // the next item's staging writes stay behind this one's reads
   }
 }
 

@@ -8,13 +8,6 @@
 // column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
 #include "common.h"
 
-// orders a wave's own LDS writes before its own LDS reads (and the reverse, for the next query's writes): LDS executes a
-// wave's instructions in order, so only the compiler has to be kept from moving them
-__device__ __forceinline__ void rd_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // ---------------------------------------------------------------------------------------------
 // row difference P[s,:] \ M[s,:]
 // ---------------------------------------------------------------------------------------------
@@ -25,6 +18,7 @@ constexpr int RD_STAGE = 512;
 
 // membership of key in the sorted row a[0..n): the number of steps depends on n alone, which every lane of the wave shares,
 // and every load is in bounds for any key (a lane without a column carries -1, which no row holds)
+// (not common.h's sorted_has: fixed trips for the row length and 32-bit positions, so that a lane carrying -1 runs along)
 template <typename Row>
 __device__ __forceinline__ bool rd_row_has(Row a, int n, int32_t key) {
   if (n <= 0) return false;
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
     const bool staged = dm <= RD_STAGE;
     if (staged) {
       for (int t = lane; t < dm; t += OCN_WAVE) sm[t] = colM[m0 + t];
-      rd_wave_lds_sync();
+      wave_lds_sync();
     }
     const int32_t self = drop_self ? (int32_t)s : -1;
     i64 base = FILL ? off[q] : 0;
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
       base += __popcll(mask);
     }
     if (!FILL && lane == 0) count[q] = (int32_t)base;
-    if (staged) rd_wave_lds_sync();                          // the next query's staging writes stay behind this one's reads
+    if (staged) wave_lds_sync();                          // the next query's staging writes stay behind this one's reads
   }
 }
 
@@ -89,6 +83,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
 constexpr i64 TH_WINDOW = (i64)(160 * 1024 - 2048) * 8;
 
 // first position of the sorted row a[0..n) whose column is not below key; the same steps and the same loads in every lane
+// (not common.h's sorted_has: it returns the position, and the key is a 64-bit window bound)
 __device__ __forceinline__ i64 th_lower_bound(const int32_t* __restrict__ a, i64 n, i64 key) {
   i64 lo = 0, hi = n;
   while (lo < hi) {

@@ -11,7 +11,7 @@
 // ocn_walk_prep replaces the launch chain in front of the walk kernels for small batches (B <= 4096: the drivers
 // use 2048): ONE single-workgroup launch sorts the candidates by source (LDS bitonic sort), scans the flag offsets,
 // forms the groups and decides per group whether it goes to the shared sweep (>= 2 members, target rows that fit
-// the table) or to the per-candidate two-sided kernels of cn_stage.hip, scans the three work-item lists and clears
+// the table) or to the per-candidate two-sided kernels of cn_walk.hip, scans the three work-item lists and clears
 // the per-candidate counters.
 #include "common.h"
 

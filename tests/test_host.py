@@ -245,7 +245,7 @@ def test_training_and_sort_kernels_do_not_spill(tmp_path):
     root = os.path.join(os.path.dirname(__file__), "..")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     seen = {}
-    for name in ("coo_csr", "wgrad", "pool_bwd", "cn_stage", "scan", "colsum"):       # (cn_stage: round 3 shipped a 104-register spill in the H = 512 hub-row kernel)
+    for name in ("coo_csr", "wgrad", "pool_bwd", "cn_flags", "cn_walk", "cn_weights", "cn_pool", "cn_sched", "cn_scatter", "scan", "colsum"):       # (cn_pool: round 3 shipped a 104-register spill in the H = 512 hub-row kernel)
         out = tmp_path / (name + ".s")
         subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S",
                         "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "ocn_amd", "csrc"),

@@ -233,7 +233,7 @@ def test_graph_replayed_scoring_loop_equals_the_eager_loop(hiplib, monkeypatch, 
 def test_two_stream_loop_under_stress_at_every_pooling_width(hiplib):
     """Round 4 found the H = 64 wave pooling kernel returning 64 wrong bytes of one xcn1 row about once in a hundred batches — only
     while another stream's heads ran beside it, so no single-stream test saw it (packed f32 multiply-add with an undefined high source
-    register in chain_rows; now two scalar chains: cn_stage.hip).  Thirty repetitions of the depth-2 loop per
+    register in chain_rows; now two scalar chains: cn_pool.hip).  Thirty repetitions of the depth-2 loop per
     width, every batch against the one-stream loop: a fault at that rate fails this test nine times in ten."""
     from types import SimpleNamespace
     from ocn_amd.model import predictor_dict
