@@ -132,7 +132,7 @@ def test_wgrad_reads_strided_rows(hiplib):
     assert gw0.shape == (8, 4) and not gw0.any() and not gb0.any()
 
 
-def _pool_case(n, avg, mx, B, H, seed, walk=False):
+def _pool_case(n, avg, mx, B, H, seed):
     from oracle import ocn_oracle as O   # graph generator helpers only
     from tests.helpers import batch, make_graph, product_adj2, to_product
     from ocn_amd.utils import adjoverlap
