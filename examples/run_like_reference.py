@@ -29,6 +29,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
+from ocn_amd.update import insert_edges                                             # noqa: E402
 from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
@@ -147,19 +148,35 @@ def test_heuristic(kind, data, split_edge, evaluator, batch_size, args):
 def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5):
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
     the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1.
-    --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route."""
+    --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route.
+    --recommend-accept M: the M best of them are then inserted and the sources asked again."""
     dev = data.x.device
     adj = data.full_adj_t
     adj2 = None if args.recommend_walk else build_adj2(adj, args)
     sources = split_edge['test']['edge'][:n_sources, 0].to(dev).contiguous()
-    if args.heuristic:
-        dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
-    else:
-        model.eval(); predictor.eval()
-        dst, score = recommend_links(predictor, model(data.x, adj), adj, adj2, sources, k, args.testbs, args)
-    for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
-        print(f"recommend source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
-              flush=True)
+
+    def top(adj, adj2, tag):
+        if args.heuristic:
+            dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
+        else:
+            model.eval(); predictor.eval()
+            dst, score = recommend_links(predictor, model(data.x, adj), adj, adj2, sources, k, args.testbs, args)
+        for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
+            print(f"{tag} source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
+                  flush=True)
+        return dst, score
+
+    dst, score = top(adj, adj2, "recommend")
+    if args.recommend_accept > 0:
+        # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
+        # updated, not rebuilt; the encoder is simply run again) and the same sources are asked again
+        pairs = torch.stack([sources.view(-1, 1).expand_as(dst).reshape(-1), dst.reshape(-1)])
+        flat = score.reshape(-1).masked_fill(pairs[1] < 0, float("-inf"))
+        best = flat.topk(min(args.recommend_accept, flat.numel())).indices
+        accepted = pairs[:, best[pairs[1, best] >= 0]].contiguous()
+        adj, adj2 = insert_edges(adj, accepted, adj2, donate=True)
+        print(f"accepted {accepted.shape[1]} links: " + " ".join(f"{a}-{b}" for a, b in accepted.t().tolist()), flush=True)
+        dst, score = top(adj, adj2, "recommend after accepting")
     return dst, score
 
 
@@ -197,6 +214,8 @@ def main(argv=None):
                          "(ocn_amd.sampling) instead of torch.randint pairs, which can be links")
     ap.add_argument("--recommend-walk", action="store_true",
                     help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
+    ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
+                    help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
     args = ap.parse_args(argv)
     if args.recommend_walk and args.heuristic in TWO_HOP:
         ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")

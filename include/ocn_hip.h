@@ -40,7 +40,8 @@ extern "C" {
  *    ocn_order_by_node_finish_rec, ocn_cn_flags_rec (slot records started by the prep pass); ocn_cn8_pool; ocn_cn_node_sums;
  *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation); ocn_two_hop_diff_count / _fill (its candidates
  *    expanded from A, where A² is not stored); ocn_philox4x32, ocn_complement_count, ocn_sample_stage_cols,
- *    ocn_sample_complement_rows, ocn_sample_complement_pairs (structured negative sampling). */
+ *    ocn_sample_complement_rows, ocn_sample_complement_pairs (structured negative sampling); ocn_csr_union_count / _fill,
+ *    ocn_bitrows_insert_workspace_bytes, ocn_bitrows_insert (edge insertion into a resident graph). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -589,6 +590,36 @@ int ocn_bitrows_count(const uint32_t* bits, int64_t bm_stride_words, int64_t n_r
                       void* stream);
 int ocn_bitrows_fill(const uint32_t* bits, int64_t bm_stride_words, int64_t n_rows, int64_t n_cols, const int64_t* rowptr,
                      int32_t* col, void* stream);
+
+/* Edge insertion into a resident graph (the reference adds its validation edges to the adjacency under
+ * use_valedges_as_input, NeighborOverlap_large.py:143-145, and leaves A² stale): A' = A U D without sorting A again, and the
+ * bit rows of A² updated exactly.
+ *
+ * ocn_csr_union_count / ocn_csr_union_fill: C[r,:] = A[r,:] U B[r,:] for two CSR patterns of the same shape, both with
+ * ascending, duplicate-free int32 columns; so is the output.  Two phases around a caller-side allocation: count (int32
+ * [n_rows]) -> ocn_scan_i32 -> fill (colC from rowptrC[r] on; nothing is written past rowptrC[r + 1]).  One kernel body serves
+ * both passes.  A wave owns a row: a row whose other operand is empty is a coalesced copy; else every element's place is its
+ * own index plus the number of smaller elements of the other row that are not duplicates (binary searches, the shorter row
+ * staged in LDS up to 512 columns; no sequential merge, no atomics, no workspace), hub rows only take more rounds.
+ * NULL pointers or n_rows < 0: OCN_EINVAL before any HIP call.  n_rows == 0 returns 0. */
+int ocn_csr_union_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                        int64_t n_rows, int32_t* count, void* stream);
+int ocn_csr_union_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                       int64_t n_rows, const int64_t* rowptrC /* [n_rows + 1], from ocn_scan_i32 */, int32_t* colC, void* stream);
+/* ocn_bitrows_insert: bits |= pattern(D·A') U pattern(A'·D) in place, for square n x n patterns — with bits = the bit rows
+ * of A·A and D a subset of A' = A U D, the bit rows of A'·A' (pattern(A'A') = pattern(AA) U pattern(DA') U pattern(A'D)).
+ * (rowptrA, colA) = A', (rowptrT, colT) = its transpose (the same pointers where A' is symmetric), (rowptrD, colD) = D with
+ * nnzD entries, bits [n][bm_stride_words] (bm_stride_words * 32 >= n), added int32 [n], ZERO on entry: added[r] becomes the
+ * number of bits of row r that this call turned on.  Per entry (u, v) of D: (a) bit k of row u for every k in A' row v,
+ * (b) bit v of row r for every r in A'^T row u.  Work items are chunks of at most 256 row elements, scheduled by a scan of
+ * ceil(len / 256) over both kinds: a hub row is spread over many waves.  Bits are set with 32-bit atomicOr; a bit counts as
+ * new exactly when the returned word did not have it, so the counts are exact when items collide and when D overlaps A or
+ * repeats itself.  workspace: ocn_bitrows_insert_workspace_bytes(nnzD) bytes, any content (16-byte aligned).
+ * NULL pointers, n < 0, nnzD < 0 or >= 2^30, a stride too short: OCN_EINVAL before any HIP call.  n == 0 or nnzD == 0 returns 0. */
+int64_t ocn_bitrows_insert_workspace_bytes(int64_t nnzD);
+int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
+                       const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
+                       int64_t bm_stride_words, int32_t* added, void* workspace, void* stream);
 
 /* Glue for head layouts the fused Linear kernel below does not cover (widths outside 32..256, training
  * mode; model.py:2203-2235, 2429-2437): y = LayerNorm(x) (eps, affine gamma/beta) followed by ReLU when `relu` != 0,

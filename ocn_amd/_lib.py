@@ -104,6 +104,10 @@ SIGNATURES = {
     "ocn_bitrows_from_csr": (c_int32, [_P, _P, c_int64, _P, c_int64, _P]),
     "ocn_bitrows_count": (c_int32, [_P, c_int64, c_int64, c_int64, _P, _P]),
     "ocn_bitrows_fill": (c_int32, [_P, c_int64, c_int64, c_int64, _P, _P, _P]),
+    "ocn_csr_union_count": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P]),
+    "ocn_csr_union_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "ocn_bitrows_insert_workspace_bytes": (c_int64, [c_int64]),
+    "ocn_bitrows_insert": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P]),
     "ocn_rows_ln_relu": (c_int32, [_P, _P, _P, c_float, c_int32, c_int64, c_int32, _P, _P]),
     "ocn_fill_rows": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "ocn_combine3": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P]),

@@ -1099,9 +1099,94 @@ def bitrows_from_csr(rowptr: Tensor, col: Tensor, n_cols: int) -> Tensor:
     return bits
 
 
+def _csr_union_args(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor):
+    """The operand checks of both union passes.  Columns sorted and duplicate-free in every row, as every ``SparseTensor`` of the
+    project stores them.  An empty column array has no address: the library gets a one-element stand-in it never reads."""
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    _req(rowptrB, torch.int64, "rowptrB", 1); _req(colB, torch.int32, "colB", 1)
+    if rowptrA.numel() < 1 or rowptrA.numel() != rowptrB.numel():
+        raise ValueError(f"A has {rowptrA.numel() - 1} rows, B {rowptrB.numel() - 1}")
+    if not colA.numel():
+        colA = torch.zeros(1, dtype=torch.int32, device=colA.device)
+    if not colB.numel():
+        colB = torch.zeros(1, dtype=torch.int32, device=colB.device)
+    return rowptrA.numel() - 1, colA, colB
+
+
 @_on_device
-def spgemm_pattern(rowptrA, colA, rowptrB, colB, n_cols_b: int, defer_fill: bool = False):
-    """CSR pattern of A·B (columns ascending) and, when it fits ``a2_bitmap_max_bytes``, the same
+def csr_union_count(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tensor:
+    """count[r] = |A[r,:] U B[r,:]| (ocn_hip.h: ocn_csr_union_count): int32 [n_rows]; ``scan_i32`` of it gives the row pointers
+    ``csr_union_fill`` writes at."""
+    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
+    count = torch.empty(n, dtype=torch.int32, device=rowptrA.device)
+    if n:
+        check(_lib.lib().ocn_csr_union_count(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(count), stream_ptr()),
+              "ocn_csr_union_count")
+    return count
+
+
+@_on_device
+def csr_union_fill(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor, rowptrC: Tensor, total: Optional[int] = None) -> Tensor:
+    """The columns of every row's union, ascending, int32 [rowptrC[-1]] (ocn_hip.h: ocn_csr_union_fill).  ``rowptrC``:
+    ``scan_i32(csr_union_count(...))`` of the same operands; ``total`` = ``rowptrC[-1]`` where the caller has read it already."""
+    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
+    if _req(rowptrC, torch.int64, "rowptrC", 1).numel() != n + 1:
+        raise ValueError("rowptrC: one entry per row and the total")
+    T = _total(rowptrC[-1]) if total is None else int(total)
+    colC = torch.empty(max(T, 1), dtype=torch.int32, device=rowptrA.device)
+    if n and T:
+        check(_lib.lib().ocn_csr_union_fill(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(rowptrC), ptr(colC), stream_ptr()),
+              "ocn_csr_union_fill")
+    return colC[:T]
+
+
+def csr_union(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tuple[Tensor, Tensor]:
+    """(rowptrC, colC) of the row-wise union: count -> scan -> fill, one host read for the output size."""
+    rowptrC = scan_i32(csr_union_count(rowptrA, colA, rowptrB, colB))
+    return rowptrC, csr_union_fill(rowptrA, colA, rowptrB, colB, rowptrC)
+
+
+@_on_device
+def bitrows_insert(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor, rowptrD: Tensor, colD: Tensor, bits: Tensor) -> Tensor:
+    """ocn_hip.h: ocn_bitrows_insert — ``bits`` (the bit rows of A·A, int32 [n, words]) become those of A'·A' IN PLACE, for
+    A' = (rowptrA, colA) = A U D, its transpose (rowptrT, colT) and the new entries D.  Returns ``added`` int32 [n]: the bits
+    turned on per row."""
+    for t, name in ((rowptrA, "rowptrA"), (rowptrT, "rowptrT"), (rowptrD, "rowptrD")):
+        _req(t, torch.int64, name, 1)
+    for t, name in ((colA, "colA"), (colT, "colT"), (colD, "colD")):
+        _req(t, torch.int32, name, 1)
+    _req(bits, torch.int32, "bits", 2)
+    n = rowptrA.numel() - 1
+    if rowptrT.numel() != n + 1 or rowptrD.numel() != n + 1 or bits.shape[0] != n or bits.shape[1] * 32 < n:
+        raise ValueError("bitrows_insert: A', its transpose, D and the bit rows must all be n x n")
+    added = torch.zeros(n, dtype=torch.int32, device=bits.device)
+    nnzD = colD.numel()
+    if n and nnzD:
+        l = _lib.lib()
+        ws = torch.empty(int(l.ocn_bitrows_insert_workspace_bytes(nnzD)), dtype=torch.uint8, device=bits.device)
+        check(l.ocn_bitrows_insert(ptr(rowptrA), ptr(colA), ptr(rowptrT), ptr(colT), ptr(rowptrD), ptr(colD), n, nnzD, ptr(bits),
+                                   bits.shape[1], ptr(added), ptr(ws), stream_ptr()), "ocn_bitrows_insert")
+    return added
+
+
+@_on_device
+def bitrows_to_cols(bits: Tensor, n_cols: int, rowptr: Tensor) -> Tensor:
+    """The column ids of dense bit rows, ascending per row, at the row pointers of their counts (ocn_hip.h: ocn_bitrows_fill).
+    One host read for the output size."""
+    _req(bits, torch.int32, "bits", 2); _req(rowptr, torch.int64, "rowptr", 1)
+    n = bits.shape[0]
+    if rowptr.numel() != n + 1:
+        raise ValueError("rowptr: one entry per bit row and the total")
+    nnz = _total(rowptr[-1])
+    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=bits.device)
+    if nnz:
+        check(_lib.lib().ocn_bitrows_fill(ptr(bits), bits.shape[1], n, int(n_cols), ptr(rowptr), ptr(col), stream_ptr()), "ocn_bitrows_fill")
+    return col[:nnz]
+
+
+@_on_device
+def spgemm_pattern(rowptrA, colA, rowptrB, colB, n_cols_b: int, defer_fill: bool = False, want_bitmap: bool = True):
+    """CSR pattern of A·B (columns ascending) and, when it fits ``a2_bitmap_max_bytes`` (and ``want_bitmap``), the same
     rows as dense bit rows.  One host sync for the output size — with ``defer_fill`` and bit rows, not before somebody calls
     the returned thunk: ``(rowptrC, fill, bitmap)`` where ``fill()`` -> colC runs the second pass (the counting pass, the scan
     of the row lengths and the bit rows are done)."""
@@ -1117,7 +1202,7 @@ def spgemm_pattern(rowptrA, colA, rowptrB, colB, n_cols_b: int, defer_fill: bool
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
     words = (n_cols_b + 31) // 32
     bitmap = None
-    if n * words * 4 <= a2_bitmap_max_bytes and n > 0:
+    if want_bitmap and n * words * 4 <= a2_bitmap_max_bytes and n > 0:
         bitmap = torch.empty(n, words, dtype=torch.int32, device=dev)       # every row is written in full
     check(l.ocn_spgemm_pattern_count(ptr(rowptrA), ptr(colA), n, ptr(rowptrB), ptr(colB), n_cols_b,
                                      ptr(cnt), ptr(bitmap), words, stream_ptr()), "ocn_spgemm_pattern_count")
