@@ -12,6 +12,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
+    python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
 """
@@ -29,7 +30,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
-from ocn_amd.update import insert_edges                                             # noqa: E402
+from ocn_amd.update import insert_edges, remove_edges                               # noqa: E402
 from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
@@ -149,7 +150,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
     the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1.
     --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route.
-    --recommend-accept M: the M best of them are then inserted and the sources asked again."""
+    --recommend-accept M: the M best of them are then inserted and the sources asked again.
+    --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original."""
     dev = data.x.device
     adj = data.full_adj_t
     adj2 = None if args.recommend_walk else build_adj2(adj, args)
@@ -174,9 +176,22 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         flat = score.reshape(-1).masked_fill(pairs[1] < 0, float("-inf"))
         best = flat.topk(min(args.recommend_accept, flat.numel())).indices
         accepted = pairs[:, best[pairs[1, best] >= 0]].contiguous()
-        adj, adj2 = insert_edges(adj, accepted, adj2, donate=True)
+        was, was2 = adj, adj2
+        adj, adj2 = insert_edges(adj, accepted, adj2, donate=not args.recommend_undo)     # (an undo keeps the old pair to compare with)
         print(f"accepted {accepted.shape[1]} links: " + " ".join(f"{a}-{b}" for a, b in accepted.t().tolist()), flush=True)
         dst, score = top(adj, adj2, "recommend after accepting")
+        if args.recommend_undo:
+            # --recommend-undo: the accepted links leave again (ocn_amd.update.remove_edges: A' = A \ D, the bits of A² that lose
+            # their last witness cleared).  Recommended links are non-edges, so the round trip is exact
+            adj, adj2 = remove_edges(adj, accepted, adj2, donate=True)
+            same = torch.equal(adj._rowptr, was._rowptr) and torch.equal(adj._col, was._col)
+            if adj2 is not None:
+                same = same and torch.equal(adj2._rowptr, was2._rowptr) and torch.equal(adj2._col, was2._col)
+                if adj2.product_bit_rows() is not None and was2.product_bit_rows() is not None:
+                    same = same and torch.equal(adj2.product_bit_rows(), was2.product_bit_rows())
+            print(f"removed {accepted.shape[1]} links again: adj and adj2 restored exactly = {same}", flush=True)
+            if not same:
+                raise SystemExit("--recommend-undo: the restored graph differs from the original")
     return dst, score
 
 
@@ -216,7 +231,12 @@ def main(argv=None):
                     help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
     ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
                     help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
+    ap.add_argument("--recommend-undo", action="store_true",
+                    help="with --recommend-accept: remove the accepted links again (ocn_amd.update.remove_edges) and check that the "
+                         "adjacency and A² are restored exactly")
     args = ap.parse_args(argv)
+    if args.recommend_undo and not (args.recommend and args.recommend_accept > 0):
+        ap.error("--recommend-undo: needs --recommend K --recommend-accept M")
     if args.recommend_walk and args.heuristic in TWO_HOP:
         ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")
     dev = torch.device("cuda:0")

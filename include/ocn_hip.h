@@ -41,7 +41,8 @@ extern "C" {
  *    ocn_row_diff_count / _fill, ocn_segment_topk (link recommendation); ocn_two_hop_diff_count / _fill (its candidates
  *    expanded from A, where A² is not stored); ocn_philox4x32, ocn_complement_count, ocn_sample_stage_cols,
  *    ocn_sample_complement_rows, ocn_sample_complement_pairs (structured negative sampling); ocn_csr_union_count / _fill,
- *    ocn_bitrows_insert_workspace_bytes, ocn_bitrows_insert (edge insertion into a resident graph). */
+ *    ocn_bitrows_insert_workspace_bytes, ocn_bitrows_insert (edge insertion into a resident graph); ocn_csr_minus_count /
+ *    _fill, ocn_bitrows_remove_workspace_bytes, ocn_bitrows_remove (edge removal from a resident graph). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -620,6 +621,44 @@ int64_t ocn_bitrows_insert_workspace_bytes(int64_t nnzD);
 int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
                        const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
                        int64_t bm_stride_words, int32_t* added, void* workspace, void* stream);
+
+/* Edge removal from a resident graph — the way back from the insertion above (the reference has no counterpart: it masks
+ * its target edges out of the adjacency per training batch and forms A² of the remainder from scratch,
+ * NeighborOverlap_large.py:68-74; its use_valedges_as_input, NeighborOverlap_large.py:143-145, only ever adds): A' = A \ D
+ * without sorting A again, and the bit rows of A² updated exactly.
+ *
+ * ocn_csr_minus_count / ocn_csr_minus_fill: C[r,:] = A[r,:] \ B[r,:] for two CSR patterns of the same shape, both with
+ * ascending, duplicate-free int32 columns; so is the output.  The protocol of the union: count (int32 [n_rows]) ->
+ * ocn_scan_i32 -> fill (colC from rowptrC[r] on; nothing is written at or past rowptrC[r + 1]).  One kernel body serves both
+ * passes.  A wave owns a row: a row whose B row is empty is a coalesced copy; else the A row is streamed 64 columns at a time
+ * against the B row (staged in LDS up to 512 columns, searched in memory beyond), an element B holds too is dropped and a kept
+ * one lands at its own index minus the dropped ones before it (ballot prefix plus a running count; no atomics, no workspace).
+ * Entries of B that A lacks are harmless.  NULL pointers or n_rows < 0: OCN_EINVAL before any HIP call.  n_rows == 0 returns 0. */
+int ocn_csr_minus_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                        int64_t n_rows, int32_t* count, void* stream);
+int ocn_csr_minus_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                       int64_t n_rows, const int64_t* rowptrC /* [n_rows + 1], from ocn_scan_i32 */, int32_t* colC, void* stream);
+/* ocn_bitrows_remove: bits = the bit rows of A·A on entry, of A'·A' on return, in place, for square n x n patterns with
+ * A' = A \ D.  A pattern cannot be decremented (that would take walk counts), but a bit can be decided again: bit (r, k) of
+ * A'·A' is set exactly when row r of A' and row k of A'^T share a column, and the only bits that can differ from A·A are those
+ * with a witness walk through a removed entry.  (rowptrA0, colA0) = the OLD A and (rowptrT0, colT0) its transpose: per entry
+ * (u, v) of D they enumerate the candidates, (a) bit k of row u for every k in A row v, (b) bit v of row r for every r in
+ * A^T row u.  (rowptrA, colA) = A' and (rowptrT, colT) its transpose decide them (where the matrices are symmetric the
+ * transposes are the same pointers).  (rowptrD, colD) = D with nnzD entries; any superset of the removed entries gives the
+ * same result, so D may repeat itself or name entries A never had.  bits [n][bm_stride_words] (bm_stride_words * 32 >= n),
+ * removed int32 [n], ZERO on entry: removed[r] becomes the number of bits of row r that this call turned off.  Work items
+ * are chunks of at most 256 elements of the enumerated (old) row, scheduled as in ocn_bitrows_insert: a hub row is spread
+ * over many waves.  Every lane holds one candidate; only a bit that is set is decided: by its lane alone where the shorter
+ * of the two lists has at most 32 columns (a guess, not measured), else by the whole wave striding the shorter list.  A bit
+ * without a witness is cleared with 32-bit atomicAnd and counts exactly when the returned word still had it; the decision
+ * reads A' only, which nothing writes, so bits and counts do not depend on scheduling.  Rows and columns outside [0, n) are
+ * skipped.  workspace: ocn_bitrows_remove_workspace_bytes(nnzD) bytes, any content (16-byte aligned).
+ * NULL pointers, n < 0, nnzD < 0 or >= 2^30, a stride too short: OCN_EINVAL before any HIP call.  n == 0 or nnzD == 0 returns 0. */
+int64_t ocn_bitrows_remove_workspace_bytes(int64_t nnzD);
+int ocn_bitrows_remove(const int64_t* rowptrA0, const int32_t* colA0, const int64_t* rowptrT0, const int32_t* colT0,
+                       const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
+                       const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
+                       int64_t bm_stride_words, int32_t* removed, void* workspace, void* stream);
 
 /* Glue for head layouts the fused Linear kernel below does not cover (widths outside 32..256, training
  * mode; model.py:2203-2235, 2429-2437): y = LayerNorm(x) (eps, affine gamma/beta) followed by ReLU when `relu` != 0,

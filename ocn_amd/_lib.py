@@ -108,6 +108,10 @@ SIGNATURES = {
     "ocn_csr_union_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P]),
     "ocn_bitrows_insert_workspace_bytes": (c_int64, [c_int64]),
     "ocn_bitrows_insert": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P]),
+    "ocn_csr_minus_count": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P]),
+    "ocn_csr_minus_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "ocn_bitrows_remove_workspace_bytes": (c_int64, [c_int64]),
+    "ocn_bitrows_remove": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P]),
     "ocn_rows_ln_relu": (c_int32, [_P, _P, _P, c_float, c_int32, c_int64, c_int32, _P, _P]),
     "ocn_fill_rows": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "ocn_combine3": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P]),

@@ -7,6 +7,10 @@
 // for each new entry (u, v).  The work is one row length of A' per new entry — thousands of bit sets where the product
 // from scratch rewrites every bit row.  OR is idempotent: D may overlap A or repeat itself.
 // See include/ocn_hip.h (ocn_csr_union_count / ocn_csr_union_fill, ocn_bitrows_insert).
+//
+// Edge removal, further down: A' = A \ D as a row-wise difference, and the bit rows of A² turned into those of A'·A' by
+// deciding again every bit that had a witness walk through a removed entry — bit (r, k) stays exactly when row r of A' and
+// row k of A'^T share a column (ocn_csr_minus_count / ocn_csr_minus_fill, ocn_bitrows_remove).
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -191,6 +195,180 @@ __global__ __launch_bounds__(OCN_BLOCK) void bi_apply_kernel(const i64* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// row-wise difference of two CSR patterns
+// ---------------------------------------------------------------------------------------------
+// Streams the row x[0..nx) 64 columns at a time against the sorted row y[0..ny): an element that y holds too is dropped, a
+// kept one lands at its own index minus the dropped ones before it (ballot prefix within the round, the wave's running count
+// across rounds).  Returns the number of dropped elements.
+template <bool FILL, typename RowY>
+__device__ __forceinline__ int mn_stream(const int32_t* __restrict__ x, int nx, RowY y, int ny, int lane,
+                                         int32_t* __restrict__ out, i64 cap) {
+  int dups = 0;
+  for (int i0 = 0; i0 < nx; i0 += OCN_WAVE) {
+    const int i = i0 + lane;
+    bool dup = false;
+    int32_t v = 0;
+    if (i < nx) {
+      v = x[i];
+      const int lb = un_lower_bound(y, ny, v);
+      dup = lb < ny && y[lb] == v;
+    }
+    const u64 m = __ballot(dup);
+    if (FILL && i < nx && !dup) {
+      const i64 at = (i64)i - (dups + __popcll(m & ((1ull << lane) - 1ull)));
+      if (at < cap) out[at] = v;                          // (at >= 0: at most i elements are dropped before element i)
+    }
+    dups += __popcll(m);
+  }
+  return dups;
+}
+
+// C[r, :] = A[r, :] \ B[r, :].  One body for both passes, as csr_union_kernel: FILL == false leaves the size of every row's
+// difference in count[r], FILL == true writes its columns, ascending, from colC[rowptrC[r]] on.  A wave owns a row.  B's row
+// empty (nearly every row: D has few entries) is a coalesced copy of A's; otherwise A's row is streamed against B's, staged in
+// LDS when it fits.  No atomics, nothing written at or past rowptrC[r + 1].
+template <bool FILL>
+__global__ __launch_bounds__(OCN_BLOCK) void csr_minus_kernel(
+    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+    const i64* __restrict__ rowptrB, const int32_t* __restrict__ colB, i64 n_rows,
+    int32_t* __restrict__ count, const i64* __restrict__ rowptrC, int32_t* __restrict__ colC) {
+  __shared__ int32_t s_b[OCN_WPB][UN_STAGE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t* sb = s_b[wave];
+  for (i64 r = (i64)blockIdx.x * OCN_WPB + wave; r < n_rows; r += (i64)gridDim.x * OCN_WPB) {
+    const i64 a0 = rowptrA[r], b0 = rowptrB[r];
+    const int da = (int)(rowptrA[r + 1] - a0), db = (int)(rowptrB[r + 1] - b0);   // (distinct int32 columns: fewer than 2^31)
+    const int32_t* A = colA + a0;
+    const int32_t* B = colB + b0;
+    int32_t* out = FILL ? colC + rowptrC[r] : nullptr;
+    const i64 cap = FILL ? rowptrC[r + 1] - rowptrC[r] : 0;
+    if (db <= 0 || da <= 0) {
+      if (FILL) {
+        for (int i = lane; i < da && i < cap; i += OCN_WAVE) out[i] = A[i];
+      } else if (lane == 0) {
+        count[r] = da > 0 ? da : 0;
+      }
+      continue;
+    }
+    const bool staged = db <= UN_STAGE;
+    if (staged) {
+      for (int t = lane; t < db; t += OCN_WAVE) sb[t] = B[t];
+      wave_lds_sync();
+    }
+    const int dups = staged ? mn_stream<FILL>(A, da, (const int32_t*)sb, db, lane, out, cap)
+                            : mn_stream<FILL>(A, da, B, db, lane, out, cap);
+    if (!FILL && lane == 0) count[r] = da - dups;
+    if (staged) wave_lds_sync();                          // the next row's staging writes stay behind this one's reads
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the bits of A² that lose their last witness
+// ---------------------------------------------------------------------------------------------
+// Length of the shorter list up to which a candidate is decided by its own lane (a serial walk of that list, one narrowing
+// lower-bound search of the longer list per element); beyond it the whole wave decides the candidate, lanes striding the
+// shorter list.  The lane form makes the wave wait for its longest candidate, the wave form takes the candidates one after
+// the other: 32 is a GUESS at where the second gets cheaper, not a measurement ("Removing edges").
+constexpr int BR_LANE_MAX = 32;
+
+// Do the sorted rows s[0..ns) and l[0..nl) (ns <= nl) share a column?  One lane, early exit on the first witness; every
+// search starts where the last one ended.
+__device__ __forceinline__ bool br_lane_meets(const int32_t* __restrict__ s, int ns, const int32_t* __restrict__ l, int nl) {
+  int base = 0;
+  for (int i = 0; i < ns && base < nl; ++i) {
+    const int32_t key = s[i];
+    base += un_lower_bound(l + base, nl - base, key);
+    if (base < nl && l[base] == key) return true;
+  }
+  return false;
+}
+
+// The schedule of bi_apply_kernel — a wave takes work item w by grid stride, the last k with off[k] <= w names entry
+// e = k / 2 = (u, v) of D and the kind, w - off[k] the chunk — over the rows of the OLD matrix: kind a enumerates the
+// candidates (u, k) for k in row v of A (the walks u -> v -> k), kind b the candidates (r, v) for r in row u of A^T (the walks
+// r -> u -> v).  Every lane holds one candidate per round.  A candidate whose bit is set now is decided on A' = (rowptrA, colA)
+// and its transpose, which nothing writes: the bit stays when row r of A' and row k of A'^T share a column, else it is cleared
+// with atomicAnd, and counts as removed exactly when the word that came back still had it — exact when two items reach the same
+// bit (one of them sees it gone) and when D repeats itself.  The decision never depends on what another item did, so neither
+// do the bits or the counts.  Kind a: all lanes work on bit row u, their votes go through a ballot into one atomic per round.
+__global__ __launch_bounds__(OCN_BLOCK) void br_apply_kernel(const i64* __restrict__ rowptrA0, const int32_t* __restrict__ colA0,
+                                                             const i64* __restrict__ rowptrT0, const int32_t* __restrict__ colT0,
+                                                             const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+                                                             const i64* __restrict__ rowptrT, const int32_t* __restrict__ colT,
+                                                             const int32_t* __restrict__ colD, const int32_t* __restrict__ erow,
+                                                             const i64* __restrict__ off, i64 n_off, i64 n,
+                                                             unsigned* __restrict__ bits, i64 stride, int32_t* __restrict__ removed) {
+  const int lane = threadIdx.x & 63;
+  const i64 total = off[n_off];
+  for (i64 w = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); w < total; w += (i64)gridDim.x * OCN_WPB) {
+    i64 lo = 0, hi = n_off;                                // off[0] = 0 <= w < off[n_off]: the answer is in [0, n_off)
+    while (hi - lo > 1) {
+      const i64 mid = (lo + hi) >> 1;
+      if (off[mid] <= w) lo = mid; else hi = mid;
+    }
+    const i64 e = lo >> 1;
+    const i64 chunk = w - off[lo];
+    const i64 u = erow[e], v = colD[e];
+    if (u < 0 || u >= n || v < 0 || v >= n) continue;      // (such an entry has no items; nothing is indexed with it)
+    const bool kind_a = !(lo & 1);
+    const i64* rp0 = kind_a ? rowptrA0 : rowptrT0;
+    const int32_t* col0 = kind_a ? colA0 : colT0;
+    const i64 row0 = kind_a ? v : u;
+    const i64 p0 = rp0[row0] + chunk * BI_CHUNK;
+    const i64 p1 = (p0 + BI_CHUNK) < rp0[row0 + 1] ? (p0 + BI_CHUNK) : rp0[row0 + 1];
+    for (i64 q0 = p0; q0 < p1; q0 += OCN_WAVE) {           // (wave-uniform bounds: every lane takes every round)
+      const i64 q = q0 + lane;
+      i64 r = -1, k = -1;
+      if (q < p1) {
+        const i64 x = col0[q];
+        r = kind_a ? u : x;
+        k = kind_a ? x : v;
+      }
+      unsigned* word = nullptr;
+      unsigned bit = 0;
+      const int32_t *S = nullptr, *L = nullptr;            // the shorter and the longer of A' row r and A'^T row k
+      int ns = 0, nl = 0;
+      bool clear = false, heavy = false;
+      if (r >= 0 && r < n && k >= 0 && k < n) {
+        word = bits + r * stride + (k >> 5);
+        bit = 1u << (k & 31);
+        if (*word & bit) {                                 // (a bit that is not set now has nothing to decide)
+          const i64 a0 = rowptrA[r], t0 = rowptrT[k];
+          const int la = (int)(rowptrA[r + 1] - a0), lt = (int)(rowptrT[k + 1] - t0);
+          const bool a_short = la <= lt;
+          S = a_short ? colA + a0 : colT + t0;
+          L = a_short ? colT + t0 : colA + a0;
+          ns = a_short ? la : lt;
+          nl = a_short ? lt : la;
+          if (ns <= BR_LANE_MAX) clear = !br_lane_meets(S, ns, L, nl);
+          else heavy = true;
+        }
+      }
+      for (u64 todo = __ballot(heavy); todo; todo &= todo - 1) {   // the whole wave on one candidate at a time
+        const int src = __ffsll((long long)todo) - 1;
+        const int32_t* s = (const int32_t*)__shfl((u64)S, src, OCN_WAVE);
+        const int32_t* l = (const int32_t*)__shfl((u64)L, src, OCN_WAVE);
+        const int cs = __shfl(ns, src, OCN_WAVE), cl = __shfl(nl, src, OCN_WAVE);
+        bool met = false;
+        for (int i0 = 0; i0 < cs && !met; i0 += OCN_WAVE) {
+          const int i = i0 + lane;
+          met = __any(i < cs && sorted_has(l, (i64)cl, s[i]));
+        }
+        if (lane == src) clear = !met;
+      }
+      bool gone = false;
+      if (clear) gone = (atomicAnd(word, ~bit) & bit) != 0;
+      if (kind_a) {
+        const int cnt = __popcll(__ballot(gone));
+        if (lane == 0 && cnt) atomicAdd(removed + u, cnt);
+      } else if (gone) {
+        atomicAdd(removed + r, 1);
+      }
+    }
+  }
+}
+
 extern "C" {
 
 int ocn_csr_union_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
@@ -244,6 +422,64 @@ int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_
   hipLaunchKernelGGL(bi_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0, st,
                      (const i64*)rowptrA, colA, (const i64*)rowptrT, colT, colD, (const int32_t*)erow, (const i64*)off,
                      (i64)(2 * nnzD), (i64)n, (unsigned*)bits, (i64)bm_stride_words, added);
+  return launch_status();
+}
+
+int ocn_csr_minus_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                        int64_t n_rows, int32_t* count, void* stream) {
+  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !count) return OCN_EINVAL;
+  if (n_rows == 0) return 0;
+  hipLaunchKernelGGL((csr_minus_kernel<false>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, count,
+                     (const i64*)nullptr, (int32_t*)nullptr);
+  return launch_status();
+}
+
+int ocn_csr_minus_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                       int64_t n_rows, const int64_t* rowptrC, int32_t* colC, void* stream) {
+  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !rowptrC || !colC) return OCN_EINVAL;
+  if (n_rows == 0) return 0;
+  hipLaunchKernelGGL((csr_minus_kernel<true>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, (int32_t*)nullptr,
+                     (const i64*)rowptrC, colC);
+  return launch_status();
+}
+
+int64_t ocn_bitrows_remove_workspace_bytes(int64_t nnzD) {
+  // the layout of ocn_bitrows_insert: items int32[2 nnzD] | off int64[2 nnzD + 1] | erow int32[nnzD] | scan state
+  return ocn_bitrows_insert_workspace_bytes(nnzD);
+}
+
+int ocn_bitrows_remove(const int64_t* rowptrA0, const int32_t* colA0, const int64_t* rowptrT0, const int32_t* colT0,
+                       const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
+                       const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
+                       int64_t bm_stride_words, int32_t* removed, void* workspace, void* stream) {
+  if (n < 0 || nnzD < 0 || nnzD > 0x3fffffffll || bm_stride_words < 0 || bm_stride_words * 32 < n) return OCN_EINVAL;
+  if (!rowptrA0 || !colA0 || !rowptrT0 || !colT0 || !rowptrA || !colA || !rowptrT || !colT) return OCN_EINVAL;
+  if (!rowptrD || !colD || !bits || !removed || !workspace) return OCN_EINVAL;
+  if (n == 0 || nnzD == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int32_t* items = (int32_t*)ws;
+  i64* off = (i64*)(ws + bi_align(2 * nnzD * 4));
+  int32_t* erow = (int32_t*)((char*)off + bi_align((2 * nnzD + 1) * 8));
+  int32_t* scan_ws = (int32_t*)((char*)erow + bi_align(nnzD * 4));
+  const i64 sw = bi_align(ocn_scan_workspace_bytes(2 * nnzD));
+  // items of entries no row of D reaches (a rowptrD that does not cover colD) stay zero; the scan state starts zero
+  hipLaunchKernelGGL(bi_zero_kernel, dim3(grid_for((2 * nnzD + OCN_BLOCK - 1) / OCN_BLOCK, 1024)), dim3(OCN_BLOCK), 0, st, items,
+                     (i64)(2 * nnzD));
+  hipLaunchKernelGGL(bi_zero_kernel, dim3(grid_for((nnzD + OCN_BLOCK - 1) / OCN_BLOCK, 1024)), dim3(OCN_BLOCK), 0, st, erow, (i64)nnzD);
+  hipLaunchKernelGGL(bi_zero_kernel, dim3(1), dim3(OCN_BLOCK), 0, st, scan_ws, (i64)(sw / 4));
+  // the candidates are enumerated from the OLD rows: the same count of chunks per entry and kind as the insertion's, read
+  // off the old row pointers
+  hipLaunchKernelGGL(bi_items_kernel, dim3(grid_for((n + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0, st,
+                     (const i64*)rowptrA0, (const i64*)rowptrT0, (const i64*)rowptrD, colD, (i64)n, (i64)nnzD, erow, items);
+  const int rc = ocn_scan_i32(items, 2 * nnzD, (int64_t*)off, scan_ws, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(br_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0, st,
+                     (const i64*)rowptrA0, colA0, (const i64*)rowptrT0, colT0, (const i64*)rowptrA, colA, (const i64*)rowptrT, colT,
+                     colD, (const int32_t*)erow, (const i64*)off, (i64)(2 * nnzD), (i64)n, (unsigned*)bits, (i64)bm_stride_words,
+                     removed);
   return launch_status();
 }
 

@@ -1170,6 +1170,66 @@ def bitrows_insert(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor,
 
 
 @_on_device
+def csr_minus_count(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tensor:
+    """count[r] = |A[r,:] \\ B[r,:]| (ocn_hip.h: ocn_csr_minus_count): int32 [n_rows]; ``scan_i32`` of it gives the row pointers
+    ``csr_minus_fill`` writes at."""
+    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
+    count = torch.empty(n, dtype=torch.int32, device=rowptrA.device)
+    if n:
+        check(_lib.lib().ocn_csr_minus_count(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(count), stream_ptr()),
+              "ocn_csr_minus_count")
+    return count
+
+
+@_on_device
+def csr_minus_fill(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor, rowptrC: Tensor, total: Optional[int] = None) -> Tensor:
+    """The columns of every row's difference, ascending, int32 [rowptrC[-1]] (ocn_hip.h: ocn_csr_minus_fill).  ``rowptrC``:
+    ``scan_i32(csr_minus_count(...))`` of the same operands; ``total`` = ``rowptrC[-1]`` where the caller has read it already."""
+    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
+    if _req(rowptrC, torch.int64, "rowptrC", 1).numel() != n + 1:
+        raise ValueError("rowptrC: one entry per row and the total")
+    T = _total(rowptrC[-1]) if total is None else int(total)
+    colC = torch.empty(max(T, 1), dtype=torch.int32, device=rowptrA.device)
+    if n and T:
+        check(_lib.lib().ocn_csr_minus_fill(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(rowptrC), ptr(colC), stream_ptr()),
+              "ocn_csr_minus_fill")
+    return colC[:T]
+
+
+def csr_minus(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tuple[Tensor, Tensor]:
+    """(rowptrC, colC) of the row-wise difference A \\ B: count -> scan -> fill, one host read for the output size."""
+    rowptrC = scan_i32(csr_minus_count(rowptrA, colA, rowptrB, colB))
+    return rowptrC, csr_minus_fill(rowptrA, colA, rowptrB, colB, rowptrC)
+
+
+@_on_device
+def bitrows_remove(rowptrA0: Tensor, colA0: Tensor, rowptrT0: Tensor, colT0: Tensor, rowptrA: Tensor, colA: Tensor,
+                   rowptrT: Tensor, colT: Tensor, rowptrD: Tensor, colD: Tensor, bits: Tensor) -> Tensor:
+    """ocn_hip.h: ocn_bitrows_remove — ``bits`` (the bit rows of A·A, int32 [n, words]) become those of A'·A' IN PLACE, for
+    the old A = (rowptrA0, colA0) and its transpose (rowptrT0, colT0), A' = (rowptrA, colA) = A \\ D and its transpose
+    (rowptrT, colT), and the removed entries D.  Returns ``removed`` int32 [n]: the bits turned off per row."""
+    for t, name in ((rowptrA0, "rowptrA0"), (rowptrT0, "rowptrT0"), (rowptrA, "rowptrA"), (rowptrT, "rowptrT"), (rowptrD, "rowptrD")):
+        _req(t, torch.int64, name, 1)
+    for t, name in ((colA0, "colA0"), (colT0, "colT0"), (colA, "colA"), (colT, "colT"), (colD, "colD")):
+        _req(t, torch.int32, name, 1)
+    _req(bits, torch.int32, "bits", 2)
+    n = rowptrA0.numel() - 1
+    if any(t.numel() != n + 1 for t in (rowptrT0, rowptrA, rowptrT, rowptrD)) or bits.shape[0] != n or bits.shape[1] * 32 < n:
+        raise ValueError("bitrows_remove: A, A', their transposes, D and the bit rows must all be n x n")
+    removed = torch.zeros(n, dtype=torch.int32, device=bits.device)
+    nnzD = colD.numel()
+    if n and nnzD:
+        l = _lib.lib()
+        # a matrix without entries has no column array to point at (A' after every entry has left): a stand-in nothing reads
+        cols = [c if c.numel() else torch.zeros(1, dtype=torch.int32, device=bits.device) for c in (colA0, colT0, colA, colT)]
+        ws = torch.empty(int(l.ocn_bitrows_remove_workspace_bytes(nnzD)), dtype=torch.uint8, device=bits.device)
+        check(l.ocn_bitrows_remove(ptr(rowptrA0), ptr(cols[0]), ptr(rowptrT0), ptr(cols[1]), ptr(rowptrA), ptr(cols[2]), ptr(rowptrT),
+                                   ptr(cols[3]), ptr(rowptrD), ptr(colD), n, nnzD, ptr(bits), bits.shape[1], ptr(removed), ptr(ws),
+                                   stream_ptr()), "ocn_bitrows_remove")
+    return removed
+
+
+@_on_device
 def bitrows_to_cols(bits: Tensor, n_cols: int, rowptr: Tensor) -> Tensor:
     """The column ids of dense bit rows, ascending per row, at the row pointers of their counts (ocn_hip.h: ocn_bitrows_fill).
     One host read for the output size."""
