@@ -14,10 +14,10 @@
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------
-// row-wise union of two CSR patterns
+// row-wise union and difference of two CSR patterns
 // ---------------------------------------------------------------------------------------------
-// Columns of the shorter row a wave stages in LDS (2 KiB per wave, as the row difference of recommend.hip): the searches of
-// the longer row's elements then stay on chip.  A longer "short" row is searched where it lies.
+// Columns of the shorter row (the difference: of B's row) a wave stages in LDS (2 KiB per wave, as the row difference of
+// recommend.hip): the searches of the longer row's elements then stay on chip.  A longer "short" row is searched where it lies.
 constexpr int UN_STAGE = 512;
 
 // first position of the sorted row a[0..n) whose column is not below key; every load is inside the row
@@ -33,13 +33,13 @@ __device__ __forceinline__ int un_lower_bound(Row a, int n, int32_t key) {
 
 // Streams the row x[0..nx) 64 columns at a time against the sorted row y[0..ny).  An element that y holds too is a
 // duplicate; the ballot of the duplicates gives every lane the number of duplicates before its own element, the wave's
-// running count carries it across rounds.  With KEEP_DUP the element x[i] lands at i + (elements of y below it) - (duplicates
-// before it): its own index plus the smaller elements of the other row that are not duplicates.  Without, duplicates are
-// dropped and x[i] lands at (elements of y below it) + i - (duplicates before it).  Both are the same expression; what
-// differs is whether the duplicate itself is written.  Returns the number of duplicates.
-template <bool FILL, bool KEEP_DUP, typename RowY>
-__device__ __forceinline__ int un_stream(const int32_t* __restrict__ x, int nx, RowY y, int ny, int lane,
-                                         int32_t* __restrict__ out, i64 cap) {
+// running count carries it across rounds.  MODE 0 and 1 are the two halves of a union: x[i] lands at i + (elements of y below
+// it) - (duplicates before it), its own index plus the smaller elements of the other row that are not duplicates; MODE 0
+// writes the duplicate itself, MODE 1 leaves it to the other half.  MODE 2 is the difference: the elements of y do not
+// enter the place and a duplicate is dropped.  Returns the number of duplicates.
+template <bool FILL, int MODE, typename RowY>
+__device__ __forceinline__ int set_stream(const int32_t* __restrict__ x, int nx, RowY y, int ny, int lane,
+                                          int32_t* __restrict__ out, i64 cap) {
   int dups = 0;
   for (int i0 = 0; i0 < nx; i0 += OCN_WAVE) {
     const int i = i0 + lane;
@@ -52,22 +52,26 @@ __device__ __forceinline__ int un_stream(const int32_t* __restrict__ x, int nx, 
       dup = lb < ny && y[lb] == v;
     }
     const u64 m = __ballot(dup);
-    if (FILL && i < nx && (KEEP_DUP || !dup)) {
-      const i64 at = (i64)i + lb - (dups + __popcll(m & ((1ull << lane) - 1ull)));
-      if (at < cap) out[at] = v;                          // (at < cap: offsets of another input write nothing past their own segment)
+    if (FILL && i < nx && (MODE == 0 || !dup)) {
+      // (at >= 0: at most i duplicates come before element i; at < cap: offsets of another input write nothing past
+      // their own segment)
+      const i64 at = (i64)i + (MODE == 2 ? 0 : lb) - (dups + __popcll(m & ((1ull << lane) - 1ull)));
+      if (at < cap) out[at] = v;
     }
     dups += __popcll(m);
   }
   return dups;
 }
 
-// One body for both passes, so they cannot disagree: FILL == false leaves the size of every row's union in count[r],
-// FILL == true writes its columns, ascending, from colC[rowptrC[r]] on.  A wave owns a row.  The union is symmetric in its
-// operands: L is the longer row, S the shorter.  S empty (nearly every row: D has few entries) is a coalesced copy of L.
-// Otherwise L is streamed against S (staged in LDS when it fits) and keeps its duplicates, S is streamed against L and drops
-// them: every element computes its own place from binary searches, no sequential merge, no atomics.
-template <bool FILL>
-__global__ __launch_bounds__(OCN_BLOCK) void csr_union_kernel(
+// C[r, :] = A[r, :] U B[r, :], or A[r, :] \ B[r, :] under MINUS.  One body for both passes, so they cannot disagree:
+// FILL == false leaves the size of every row's result in count[r], FILL == true writes its columns, ascending, from
+// colC[rowptrC[r]] on.  A wave owns a row.  The union is symmetric in its operands: L is the longer row, S the shorter.  The
+// difference always has L = A's row and S = B's.  S empty (nearly every row: D has few entries) is a coalesced copy of L.
+// Otherwise S is staged in LDS when it fits.  Union: L is streamed against S and keeps its duplicates, S is streamed against L
+// and drops them.  Difference: L is streamed against S and drops them.  Every element computes its own place from binary
+// searches: no sequential merge, no atomics, nothing written at or past rowptrC[r + 1].
+template <bool FILL, bool MINUS>
+__global__ __launch_bounds__(OCN_BLOCK) void csr_setop_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
     const i64* __restrict__ rowptrB, const int32_t* __restrict__ colB, i64 n_rows,
     int32_t* __restrict__ count, const i64* __restrict__ rowptrC, int32_t* __restrict__ colC) {
@@ -77,13 +81,13 @@ __global__ __launch_bounds__(OCN_BLOCK) void csr_union_kernel(
   for (i64 r = (i64)blockIdx.x * OCN_WPB + wave; r < n_rows; r += (i64)gridDim.x * OCN_WPB) {
     const i64 a0 = rowptrA[r], b0 = rowptrB[r];
     const int da = (int)(rowptrA[r + 1] - a0), db = (int)(rowptrB[r + 1] - b0);   // (distinct int32 columns: fewer than 2^31)
-    const bool a_long = da >= db;
+    const bool a_long = MINUS || da >= db;
     const int32_t* L = a_long ? colA + a0 : colB + b0;
     const int32_t* S = a_long ? colB + b0 : colA + a0;
     const int nl = a_long ? da : db, ns = a_long ? db : da;
     int32_t* out = FILL ? colC + rowptrC[r] : nullptr;
     const i64 cap = FILL ? rowptrC[r + 1] - rowptrC[r] : 0;
-    if (ns <= 0) {
+    if (ns <= 0 || (MINUS && nl <= 0)) {
       if (FILL) {
         for (int i = lane; i < nl && i < cap; i += OCN_WAVE) out[i] = L[i];
       } else if (lane == 0) {
@@ -96,12 +100,16 @@ __global__ __launch_bounds__(OCN_BLOCK) void csr_union_kernel(
       for (int t = lane; t < ns; t += OCN_WAVE) ss[t] = S[t];
       wave_lds_sync();
     }
-    if (FILL) {
-      if (staged) un_stream<true, true>(L, nl, (const int32_t*)ss, ns, lane, out, cap);
-      else un_stream<true, true>(L, nl, S, ns, lane, out, cap);
-      un_stream<true, false>(S, ns, L, nl, lane, out, cap);
+    if (MINUS) {
+      const int dups = staged ? set_stream<FILL, 2>(L, nl, (const int32_t*)ss, ns, lane, out, cap)
+                              : set_stream<FILL, 2>(L, nl, S, ns, lane, out, cap);
+      if (!FILL && lane == 0) count[r] = nl - dups;
+    } else if (FILL) {
+      if (staged) set_stream<true, 0>(L, nl, (const int32_t*)ss, ns, lane, out, cap);
+      else set_stream<true, 0>(L, nl, S, ns, lane, out, cap);
+      set_stream<true, 1>(S, ns, L, nl, lane, out, cap);
     } else {
-      const int dups = un_stream<false, false>(S, ns, L, nl, lane, (int32_t*)nullptr, 0);
+      const int dups = set_stream<false, 1>(S, ns, L, nl, lane, (int32_t*)nullptr, 0);
       if (lane == 0) count[r] = nl + ns - dups;
     }
     if (staged) wave_lds_sync();                          // the next row's staging writes stay behind this one's reads
@@ -144,6 +152,25 @@ __global__ __launch_bounds__(OCN_BLOCK) void bi_items_kernel(const i64* __restri
   }
 }
 
+// Work item w of the bit-row schedule: the last k with off[k] <= w names entry e = k / 2 of D and the kind (k even: a, odd:
+// b), w - off[k] the chunk of that item's row.  Returns k.
+__device__ __forceinline__ i64 bi_item(const i64* off, i64 n_off, i64 w, i64& chunk) {
+  i64 lo = 0, hi = n_off;                                  // off[0] = 0 <= w < off[n_off]: the answer is in [0, n_off)
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (off[mid] <= w) lo = mid; else hi = mid;
+  }
+  chunk = w - off[lo];
+  return lo;
+}
+
+// [p0, p1): the positions of that chunk of row `row`, clipped to the row's end.  Returns p0.
+__device__ __forceinline__ i64 bi_chunk(const i64* rowptr, i64 row, i64 chunk, i64& p1) {
+  const i64 p0 = rowptr[row] + chunk * BI_CHUNK;
+  p1 = (p0 + BI_CHUNK) < rowptr[row + 1] ? (p0 + BI_CHUNK) : rowptr[row + 1];
+  return p0;
+}
+
 // A wave takes work item w (grid stride): the last k with off[k] <= w names entry e = k / 2 and its kind, w - off[k] the
 // chunk.  Bits are set with atomicOr on the 32-bit word; a bit is new exactly when the word that came back did not have it —
 // exact when two items set the same bit (one of them sees it set) and when it was set before.  Kind a: all lanes work on bit
@@ -157,17 +184,13 @@ __global__ __launch_bounds__(OCN_BLOCK) void bi_apply_kernel(const i64* __restri
   const int lane = threadIdx.x & 63;
   const i64 total = off[n_off];
   for (i64 w = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); w < total; w += (i64)gridDim.x * OCN_WPB) {
-    i64 lo = 0, hi = n_off;                                // off[0] = 0 <= w < off[n_off]: the answer is in [0, n_off)
-    while (hi - lo > 1) {
-      const i64 mid = (lo + hi) >> 1;
-      if (off[mid] <= w) lo = mid; else hi = mid;
-    }
+    i64 chunk;
+    const i64 lo = bi_item(off, n_off, w, chunk);
     const i64 e = lo >> 1;
-    const i64 chunk = w - off[lo];
     const i64 u = erow[e], v = colD[e];
     if (!(lo & 1)) {
-      const i64 p0 = rowptrA[v] + chunk * BI_CHUNK;
-      const i64 p1 = (p0 + BI_CHUNK) < rowptrA[v + 1] ? (p0 + BI_CHUNK) : rowptrA[v + 1];
+      i64 p1;
+      const i64 p0 = bi_chunk(rowptrA, v, chunk, p1);
       unsigned* row = bits + u * stride;
       int fresh = 0;
       for (i64 q0 = p0; q0 < p1; q0 += OCN_WAVE) {
@@ -184,82 +207,14 @@ __global__ __launch_bounds__(OCN_BLOCK) void bi_apply_kernel(const i64* __restri
       }
       if (lane == 0 && fresh) atomicAdd(added + u, fresh);
     } else {
-      const i64 p0 = rowptrT[u] + chunk * BI_CHUNK;
-      const i64 p1 = (p0 + BI_CHUNK) < rowptrT[u + 1] ? (p0 + BI_CHUNK) : rowptrT[u + 1];
+      i64 p1;
+      const i64 p0 = bi_chunk(rowptrT, u, chunk, p1);
       const unsigned bit = 1u << (v & 31);
       for (i64 q = p0 + lane; q < p1; q += OCN_WAVE) {
         const i64 r = colT[q];
         if (r >= 0 && r < n && !(atomicOr(bits + r * stride + (v >> 5), bit) & bit)) atomicAdd(added + r, 1);
       }
     }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// row-wise difference of two CSR patterns
-// ---------------------------------------------------------------------------------------------
-// Streams the row x[0..nx) 64 columns at a time against the sorted row y[0..ny): an element that y holds too is dropped, a
-// kept one lands at its own index minus the dropped ones before it (ballot prefix within the round, the wave's running count
-// across rounds).  Returns the number of dropped elements.
-template <bool FILL, typename RowY>
-__device__ __forceinline__ int mn_stream(const int32_t* __restrict__ x, int nx, RowY y, int ny, int lane,
-                                         int32_t* __restrict__ out, i64 cap) {
-  int dups = 0;
-  for (int i0 = 0; i0 < nx; i0 += OCN_WAVE) {
-    const int i = i0 + lane;
-    bool dup = false;
-    int32_t v = 0;
-    if (i < nx) {
-      v = x[i];
-      const int lb = un_lower_bound(y, ny, v);
-      dup = lb < ny && y[lb] == v;
-    }
-    const u64 m = __ballot(dup);
-    if (FILL && i < nx && !dup) {
-      const i64 at = (i64)i - (dups + __popcll(m & ((1ull << lane) - 1ull)));
-      if (at < cap) out[at] = v;                          // (at >= 0: at most i elements are dropped before element i)
-    }
-    dups += __popcll(m);
-  }
-  return dups;
-}
-
-// C[r, :] = A[r, :] \ B[r, :].  One body for both passes, as csr_union_kernel: FILL == false leaves the size of every row's
-// difference in count[r], FILL == true writes its columns, ascending, from colC[rowptrC[r]] on.  A wave owns a row.  B's row
-// empty (nearly every row: D has few entries) is a coalesced copy of A's; otherwise A's row is streamed against B's, staged in
-// LDS when it fits.  No atomics, nothing written at or past rowptrC[r + 1].
-template <bool FILL>
-__global__ __launch_bounds__(OCN_BLOCK) void csr_minus_kernel(
-    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
-    const i64* __restrict__ rowptrB, const int32_t* __restrict__ colB, i64 n_rows,
-    int32_t* __restrict__ count, const i64* __restrict__ rowptrC, int32_t* __restrict__ colC) {
-  __shared__ int32_t s_b[OCN_WPB][UN_STAGE];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int32_t* sb = s_b[wave];
-  for (i64 r = (i64)blockIdx.x * OCN_WPB + wave; r < n_rows; r += (i64)gridDim.x * OCN_WPB) {
-    const i64 a0 = rowptrA[r], b0 = rowptrB[r];
-    const int da = (int)(rowptrA[r + 1] - a0), db = (int)(rowptrB[r + 1] - b0);   // (distinct int32 columns: fewer than 2^31)
-    const int32_t* A = colA + a0;
-    const int32_t* B = colB + b0;
-    int32_t* out = FILL ? colC + rowptrC[r] : nullptr;
-    const i64 cap = FILL ? rowptrC[r + 1] - rowptrC[r] : 0;
-    if (db <= 0 || da <= 0) {
-      if (FILL) {
-        for (int i = lane; i < da && i < cap; i += OCN_WAVE) out[i] = A[i];
-      } else if (lane == 0) {
-        count[r] = da > 0 ? da : 0;
-      }
-      continue;
-    }
-    const bool staged = db <= UN_STAGE;
-    if (staged) {
-      for (int t = lane; t < db; t += OCN_WAVE) sb[t] = B[t];
-      wave_lds_sync();
-    }
-    const int dups = staged ? mn_stream<FILL>(A, da, (const int32_t*)sb, db, lane, out, cap)
-                            : mn_stream<FILL>(A, da, B, db, lane, out, cap);
-    if (!FILL && lane == 0) count[r] = da - dups;
-    if (staged) wave_lds_sync();                          // the next row's staging writes stay behind this one's reads
   }
 }
 
@@ -302,21 +257,17 @@ __global__ __launch_bounds__(OCN_BLOCK) void br_apply_kernel(const i64* __restri
   const int lane = threadIdx.x & 63;
   const i64 total = off[n_off];
   for (i64 w = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); w < total; w += (i64)gridDim.x * OCN_WPB) {
-    i64 lo = 0, hi = n_off;                                // off[0] = 0 <= w < off[n_off]: the answer is in [0, n_off)
-    while (hi - lo > 1) {
-      const i64 mid = (lo + hi) >> 1;
-      if (off[mid] <= w) lo = mid; else hi = mid;
-    }
+    i64 chunk;
+    const i64 lo = bi_item(off, n_off, w, chunk);
     const i64 e = lo >> 1;
-    const i64 chunk = w - off[lo];
     const i64 u = erow[e], v = colD[e];
     if (u < 0 || u >= n || v < 0 || v >= n) continue;      // (such an entry has no items; nothing is indexed with it)
     const bool kind_a = !(lo & 1);
     const i64* rp0 = kind_a ? rowptrA0 : rowptrT0;
     const int32_t* col0 = kind_a ? colA0 : colT0;
     const i64 row0 = kind_a ? v : u;
-    const i64 p0 = rp0[row0] + chunk * BI_CHUNK;
-    const i64 p1 = (p0 + BI_CHUNK) < rp0[row0 + 1] ? (p0 + BI_CHUNK) : rp0[row0 + 1];
+    i64 p1;
+    const i64 p0 = bi_chunk(rp0, row0, chunk, p1);
     for (i64 q0 = p0; q0 < p1; q0 += OCN_WAVE) {           // (wave-uniform bounds: every lane takes every round)
       const i64 q = q0 + lane;
       i64 r = -1, k = -1;
@@ -369,39 +320,30 @@ __global__ __launch_bounds__(OCN_BLOCK) void br_apply_kernel(const i64* __restri
   }
 }
 
-extern "C" {
-
-int ocn_csr_union_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
-                        int64_t n_rows, int32_t* count, void* stream) {
-  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !count) return OCN_EINVAL;
+// One launch for the four set-operation entries: which kernel, and which of its outputs must be there.
+static int csr_setop_launch(bool minus, bool fill, const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB,
+                            const int32_t* colB, int64_t n_rows, int32_t* count, const int64_t* rowptrC, int32_t* colC,
+                            void* stream) {
+  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB) return OCN_EINVAL;
+  if (fill ? (!rowptrC || !colC) : !count) return OCN_EINVAL;
   if (n_rows == 0) return 0;
-  hipLaunchKernelGGL((csr_union_kernel<false>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
+  static constexpr decltype(&csr_setop_kernel<false, false>) kernels[] = {   // [2 * minus + fill]
+      csr_setop_kernel<false, false>, csr_setop_kernel<true, false>, csr_setop_kernel<false, true>, csr_setop_kernel<true, true>};
+  hipLaunchKernelGGL(kernels[2 * minus + fill], dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
                      (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, count,
-                     (const i64*)nullptr, (int32_t*)nullptr);
-  return launch_status();
-}
-
-int ocn_csr_union_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
-                       int64_t n_rows, const int64_t* rowptrC, int32_t* colC, void* stream) {
-  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !rowptrC || !colC) return OCN_EINVAL;
-  if (n_rows == 0) return 0;
-  hipLaunchKernelGGL((csr_union_kernel<true>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
-                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, (int32_t*)nullptr,
                      (const i64*)rowptrC, colC);
   return launch_status();
 }
 
-int64_t ocn_bitrows_insert_workspace_bytes(int64_t nnzD) {
-  // items int32[2 nnzD] | off int64[2 nnzD + 1] | erow int32[nnzD] | scan state
-  if (nnzD < 0) return 0;
-  return bi_align(2 * nnzD * 4) + bi_align((2 * nnzD + 1) * 8) + bi_align(nnzD * 4) + bi_align(ocn_scan_workspace_bytes(2 * nnzD)) + 64;
-}
-
-int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
-                       const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
-                       int64_t bm_stride_words, int32_t* added, void* workspace, void* stream) {
+// What both bit-row updates do first: check the arguments they share, carve the workspace (items int32[2 nnzD] |
+// off int64[2 nnzD + 1] | erow int32[nnzD] | scan state), leave every entry's row in erow and the running item count in off —
+// the chunks per entry and kind counted on the rows (rowptrA, rowptrT) the caller's apply kernel enumerates, then scanned.
+// off stays null where there is nothing to apply (no rows, or no entries of D).
+static int bi_schedule(const int64_t* rowptrA, const int64_t* rowptrT, const int64_t* rowptrD, const int32_t* colD, int64_t n,
+                       int64_t nnzD, const uint32_t* bits, int64_t bm_stride_words, const int32_t* changed, void* workspace,
+                       void* stream, const int32_t*& erow_out, const i64*& off_out) {
   if (n < 0 || nnzD < 0 || nnzD > 0x3fffffffll || bm_stride_words < 0 || bm_stride_words * 32 < n) return OCN_EINVAL;
-  if (!rowptrA || !colA || !rowptrT || !colT || !rowptrD || !colD || !bits || !added || !workspace) return OCN_EINVAL;
+  if (!rowptrA || !rowptrT || !rowptrD || !colD || !bits || !changed || !workspace) return OCN_EINVAL;
   if (n == 0 || nnzD == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -419,30 +361,51 @@ int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_
                      (const i64*)rowptrA, (const i64*)rowptrT, (const i64*)rowptrD, colD, (i64)n, (i64)nnzD, erow, items);
   const int rc = ocn_scan_i32(items, 2 * nnzD, (int64_t*)off, scan_ws, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(bi_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0, st,
-                     (const i64*)rowptrA, colA, (const i64*)rowptrT, colT, colD, (const int32_t*)erow, (const i64*)off,
+  erow_out = erow;
+  off_out = off;
+  return 0;
+}
+
+extern "C" {
+
+int ocn_csr_union_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                        int64_t n_rows, int32_t* count, void* stream) {
+  return csr_setop_launch(false, false, rowptrA, colA, rowptrB, colB, n_rows, count, nullptr, nullptr, stream);
+}
+
+int ocn_csr_union_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
+                       int64_t n_rows, const int64_t* rowptrC, int32_t* colC, void* stream) {
+  return csr_setop_launch(false, true, rowptrA, colA, rowptrB, colB, n_rows, nullptr, rowptrC, colC, stream);
+}
+
+int64_t ocn_bitrows_insert_workspace_bytes(int64_t nnzD) {
+  // items int32[2 nnzD] | off int64[2 nnzD + 1] | erow int32[nnzD] | scan state
+  if (nnzD < 0) return 0;
+  return bi_align(2 * nnzD * 4) + bi_align((2 * nnzD + 1) * 8) + bi_align(nnzD * 4) + bi_align(ocn_scan_workspace_bytes(2 * nnzD)) + 64;
+}
+
+int ocn_bitrows_insert(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
+                       const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
+                       int64_t bm_stride_words, int32_t* added, void* workspace, void* stream) {
+  if (!colA || !colT) return OCN_EINVAL;
+  const int32_t* erow = nullptr;
+  const i64* off = nullptr;
+  const int rc = bi_schedule(rowptrA, rowptrT, rowptrD, colD, n, nnzD, bits, bm_stride_words, added, workspace, stream, erow, off);
+  if (rc || !off) return rc;
+  hipLaunchKernelGGL(bi_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrT, colT, colD, erow, off,
                      (i64)(2 * nnzD), (i64)n, (unsigned*)bits, (i64)bm_stride_words, added);
   return launch_status();
 }
 
 int ocn_csr_minus_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
                         int64_t n_rows, int32_t* count, void* stream) {
-  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !count) return OCN_EINVAL;
-  if (n_rows == 0) return 0;
-  hipLaunchKernelGGL((csr_minus_kernel<false>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
-                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, count,
-                     (const i64*)nullptr, (int32_t*)nullptr);
-  return launch_status();
+  return csr_setop_launch(true, false, rowptrA, colA, rowptrB, colB, n_rows, count, nullptr, nullptr, stream);
 }
 
 int ocn_csr_minus_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB, const int32_t* colB,
                        int64_t n_rows, const int64_t* rowptrC, int32_t* colC, void* stream) {
-  if (n_rows < 0 || !rowptrA || !colA || !rowptrB || !colB || !rowptrC || !colC) return OCN_EINVAL;
-  if (n_rows == 0) return 0;
-  hipLaunchKernelGGL((csr_minus_kernel<true>), dim3(grid_for((n_rows + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0,
-                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrB, colB, (i64)n_rows, (int32_t*)nullptr,
-                     (const i64*)rowptrC, colC);
-  return launch_status();
+  return csr_setop_launch(true, true, rowptrA, colA, rowptrB, colB, n_rows, nullptr, rowptrC, colC, stream);
 }
 
 int64_t ocn_bitrows_remove_workspace_bytes(int64_t nnzD) {
@@ -454,32 +417,17 @@ int ocn_bitrows_remove(const int64_t* rowptrA0, const int32_t* colA0, const int6
                        const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
                        const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
                        int64_t bm_stride_words, int32_t* removed, void* workspace, void* stream) {
-  if (n < 0 || nnzD < 0 || nnzD > 0x3fffffffll || bm_stride_words < 0 || bm_stride_words * 32 < n) return OCN_EINVAL;
-  if (!rowptrA0 || !colA0 || !rowptrT0 || !colT0 || !rowptrA || !colA || !rowptrT || !colT) return OCN_EINVAL;
-  if (!rowptrD || !colD || !bits || !removed || !workspace) return OCN_EINVAL;
-  if (n == 0 || nnzD == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  int32_t* items = (int32_t*)ws;
-  i64* off = (i64*)(ws + bi_align(2 * nnzD * 4));
-  int32_t* erow = (int32_t*)((char*)off + bi_align((2 * nnzD + 1) * 8));
-  int32_t* scan_ws = (int32_t*)((char*)erow + bi_align(nnzD * 4));
-  const i64 sw = bi_align(ocn_scan_workspace_bytes(2 * nnzD));
-  // items of entries no row of D reaches (a rowptrD that does not cover colD) stay zero; the scan state starts zero
-  hipLaunchKernelGGL(bi_zero_kernel, dim3(grid_for((2 * nnzD + OCN_BLOCK - 1) / OCN_BLOCK, 1024)), dim3(OCN_BLOCK), 0, st, items,
-                     (i64)(2 * nnzD));
-  hipLaunchKernelGGL(bi_zero_kernel, dim3(grid_for((nnzD + OCN_BLOCK - 1) / OCN_BLOCK, 1024)), dim3(OCN_BLOCK), 0, st, erow, (i64)nnzD);
-  hipLaunchKernelGGL(bi_zero_kernel, dim3(1), dim3(OCN_BLOCK), 0, st, scan_ws, (i64)(sw / 4));
+  if (!colA0 || !colT0 || !rowptrA || !colA || !rowptrT || !colT) return OCN_EINVAL;
   // the candidates are enumerated from the OLD rows: the same count of chunks per entry and kind as the insertion's, read
   // off the old row pointers
-  hipLaunchKernelGGL(bi_items_kernel, dim3(grid_for((n + OCN_WPB - 1) / OCN_WPB, 1 << 16)), dim3(OCN_BLOCK), 0, st,
-                     (const i64*)rowptrA0, (const i64*)rowptrT0, (const i64*)rowptrD, colD, (i64)n, (i64)nnzD, erow, items);
-  const int rc = ocn_scan_i32(items, 2 * nnzD, (int64_t*)off, scan_ws, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(br_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0, st,
-                     (const i64*)rowptrA0, colA0, (const i64*)rowptrT0, colT0, (const i64*)rowptrA, colA, (const i64*)rowptrT, colT,
-                     colD, (const int32_t*)erow, (const i64*)off, (i64)(2 * nnzD), (i64)n, (unsigned*)bits, (i64)bm_stride_words,
-                     removed);
+  const int32_t* erow = nullptr;
+  const i64* off = nullptr;
+  const int rc = bi_schedule(rowptrA0, rowptrT0, rowptrD, colD, n, nnzD, bits, bm_stride_words, removed, workspace, stream, erow, off);
+  if (rc || !off) return rc;
+  hipLaunchKernelGGL(br_apply_kernel, dim3(grid_for((2 * nnzD + OCN_WPB - 1) / OCN_WPB, 2048)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const i64*)rowptrA0, colA0, (const i64*)rowptrT0, colT0, (const i64*)rowptrA, colA,
+                     (const i64*)rowptrT, colT, colD, erow, off, (i64)(2 * nnzD), (i64)n, (unsigned*)bits,
+                     (i64)bm_stride_words, removed);
   return launch_status();
 }
 

@@ -120,6 +120,14 @@ def _total(t: Tensor) -> int:
     return v
 
 
+def _scan_total(ptrs: Tensor, n: int, total: Optional[int], name: str, what: str) -> int:
+    """``ptrs`` is a scan over ``n`` segments — one entry each and the total, else ValueError(``what``).  Returns the total:
+    ``total`` where the caller has read it already, else read here (one host sync for an output size)."""
+    if _req(ptrs, torch.int64, name, 1).numel() != n + 1:
+        raise ValueError(what)
+    return _total(ptrs[-1]) if total is None else int(total)
+
+
 def status_message(bits: int) -> str:
     return "; ".join(m for b, m in ((ST_CAP, "CN flag buffer capacity exceeded"),
                                     (ST_SCAN, "a scan workspace was not zero on entry: the batch's offsets are void")) if bits & b)
@@ -689,9 +697,7 @@ def row_diff_fill(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, 
     ocn_row_diff_fill).  ``off``: ``scan_i32(row_diff_count(...))`` of the same operands; ``total`` = ``off[-1]`` where the
     caller has read it already (else it is read here: one host sync for the output size)."""
     Q = _row_diff_args(rowptrP, colP, rowptrM, colM, rows)
-    if _req(off, torch.int64, "off", 1).numel() != Q + 1:
-        raise ValueError("off: one entry per query and the total")
-    T = _total(off[-1]) if total is None else int(total)
+    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
     edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
     if Q and T:
         check(_lib.lib().ocn_row_diff_fill(ptr(rowptrP), ptr(colP), ptr(rowptrM), ptr(colM), ptr(rows), Q, int(bool(drop_self)),
@@ -740,9 +746,7 @@ def two_hop_diff_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tens
     """The pairs (s, c) of every query's set, ascending in c, row-major in int64 [T, 2] from ``off[q]`` on (ocn_hip.h:
     ocn_two_hop_diff_fill).  ``off``, ``total``: as for ``row_diff_fill``."""
     Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols)
-    if _req(off, torch.int64, "off", 1).numel() != Q + 1:
-        raise ValueError("off: one entry per query and the total")
-    T = _total(off[-1]) if total is None else int(total)
+    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
     edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
     if Q and T:
         check(_lib.lib().ocn_two_hop_diff_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
@@ -1099,9 +1103,10 @@ def bitrows_from_csr(rowptr: Tensor, col: Tensor, n_cols: int) -> Tensor:
     return bits
 
 
-def _csr_union_args(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor):
-    """The operand checks of both union passes.  Columns sorted and duplicate-free in every row, as every ``SparseTensor`` of the
-    project stores them.  An empty column array has no address: the library gets a one-element stand-in it never reads."""
+def _csr_setop_args(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor):
+    """The operand checks of both passes of the union and of the difference.  Columns sorted and duplicate-free in every row,
+    as every ``SparseTensor`` of the project stores them.  An empty column array has no address: the library gets a one-element
+    stand-in it never reads."""
     _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
     _req(rowptrB, torch.int64, "rowptrB", 1); _req(colB, torch.int32, "colB", 1)
     if rowptrA.numel() < 1 or rowptrA.numel() != rowptrB.numel():
@@ -1113,31 +1118,37 @@ def _csr_union_args(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor
     return rowptrA.numel() - 1, colA, colB
 
 
+def _csr_setop_count(entry: str, rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tensor:
+    n, colA, colB = _csr_setop_args(rowptrA, colA, rowptrB, colB)
+    count = torch.empty(n, dtype=torch.int32, device=rowptrA.device)
+    if n:
+        check(getattr(_lib.lib(), entry)(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(count), stream_ptr()), entry)
+    return count
+
+
+def _csr_setop_fill(entry: str, rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor, rowptrC: Tensor,
+                    total: Optional[int]) -> Tensor:
+    n, colA, colB = _csr_setop_args(rowptrA, colA, rowptrB, colB)
+    T = _scan_total(rowptrC, n, total, "rowptrC", "rowptrC: one entry per row and the total")
+    colC = torch.empty(max(T, 1), dtype=torch.int32, device=rowptrA.device)
+    if n and T:
+        check(getattr(_lib.lib(), entry)(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(rowptrC), ptr(colC),
+                                         stream_ptr()), entry)
+    return colC[:T]
+
+
 @_on_device
 def csr_union_count(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tensor:
     """count[r] = |A[r,:] U B[r,:]| (ocn_hip.h: ocn_csr_union_count): int32 [n_rows]; ``scan_i32`` of it gives the row pointers
     ``csr_union_fill`` writes at."""
-    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
-    count = torch.empty(n, dtype=torch.int32, device=rowptrA.device)
-    if n:
-        check(_lib.lib().ocn_csr_union_count(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(count), stream_ptr()),
-              "ocn_csr_union_count")
-    return count
+    return _csr_setop_count("ocn_csr_union_count", rowptrA, colA, rowptrB, colB)
 
 
 @_on_device
 def csr_union_fill(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor, rowptrC: Tensor, total: Optional[int] = None) -> Tensor:
     """The columns of every row's union, ascending, int32 [rowptrC[-1]] (ocn_hip.h: ocn_csr_union_fill).  ``rowptrC``:
     ``scan_i32(csr_union_count(...))`` of the same operands; ``total`` = ``rowptrC[-1]`` where the caller has read it already."""
-    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
-    if _req(rowptrC, torch.int64, "rowptrC", 1).numel() != n + 1:
-        raise ValueError("rowptrC: one entry per row and the total")
-    T = _total(rowptrC[-1]) if total is None else int(total)
-    colC = torch.empty(max(T, 1), dtype=torch.int32, device=rowptrA.device)
-    if n and T:
-        check(_lib.lib().ocn_csr_union_fill(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(rowptrC), ptr(colC), stream_ptr()),
-              "ocn_csr_union_fill")
-    return colC[:T]
+    return _csr_setop_fill("ocn_csr_union_fill", rowptrA, colA, rowptrB, colB, rowptrC, total)
 
 
 def csr_union(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tuple[Tensor, Tensor]:
@@ -1147,53 +1158,17 @@ def csr_union(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> T
 
 
 @_on_device
-def bitrows_insert(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor, rowptrD: Tensor, colD: Tensor, bits: Tensor) -> Tensor:
-    """ocn_hip.h: ocn_bitrows_insert — ``bits`` (the bit rows of A·A, int32 [n, words]) become those of A'·A' IN PLACE, for
-    A' = (rowptrA, colA) = A U D, its transpose (rowptrT, colT) and the new entries D.  Returns ``added`` int32 [n]: the bits
-    turned on per row."""
-    for t, name in ((rowptrA, "rowptrA"), (rowptrT, "rowptrT"), (rowptrD, "rowptrD")):
-        _req(t, torch.int64, name, 1)
-    for t, name in ((colA, "colA"), (colT, "colT"), (colD, "colD")):
-        _req(t, torch.int32, name, 1)
-    _req(bits, torch.int32, "bits", 2)
-    n = rowptrA.numel() - 1
-    if rowptrT.numel() != n + 1 or rowptrD.numel() != n + 1 or bits.shape[0] != n or bits.shape[1] * 32 < n:
-        raise ValueError("bitrows_insert: A', its transpose, D and the bit rows must all be n x n")
-    added = torch.zeros(n, dtype=torch.int32, device=bits.device)
-    nnzD = colD.numel()
-    if n and nnzD:
-        l = _lib.lib()
-        ws = torch.empty(int(l.ocn_bitrows_insert_workspace_bytes(nnzD)), dtype=torch.uint8, device=bits.device)
-        check(l.ocn_bitrows_insert(ptr(rowptrA), ptr(colA), ptr(rowptrT), ptr(colT), ptr(rowptrD), ptr(colD), n, nnzD, ptr(bits),
-                                   bits.shape[1], ptr(added), ptr(ws), stream_ptr()), "ocn_bitrows_insert")
-    return added
-
-
-@_on_device
 def csr_minus_count(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tensor:
     """count[r] = |A[r,:] \\ B[r,:]| (ocn_hip.h: ocn_csr_minus_count): int32 [n_rows]; ``scan_i32`` of it gives the row pointers
     ``csr_minus_fill`` writes at."""
-    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
-    count = torch.empty(n, dtype=torch.int32, device=rowptrA.device)
-    if n:
-        check(_lib.lib().ocn_csr_minus_count(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(count), stream_ptr()),
-              "ocn_csr_minus_count")
-    return count
+    return _csr_setop_count("ocn_csr_minus_count", rowptrA, colA, rowptrB, colB)
 
 
 @_on_device
 def csr_minus_fill(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor, rowptrC: Tensor, total: Optional[int] = None) -> Tensor:
     """The columns of every row's difference, ascending, int32 [rowptrC[-1]] (ocn_hip.h: ocn_csr_minus_fill).  ``rowptrC``:
     ``scan_i32(csr_minus_count(...))`` of the same operands; ``total`` = ``rowptrC[-1]`` where the caller has read it already."""
-    n, colA, colB = _csr_union_args(rowptrA, colA, rowptrB, colB)
-    if _req(rowptrC, torch.int64, "rowptrC", 1).numel() != n + 1:
-        raise ValueError("rowptrC: one entry per row and the total")
-    T = _total(rowptrC[-1]) if total is None else int(total)
-    colC = torch.empty(max(T, 1), dtype=torch.int32, device=rowptrA.device)
-    if n and T:
-        check(_lib.lib().ocn_csr_minus_fill(ptr(rowptrA), ptr(colA), ptr(rowptrB), ptr(colB), n, ptr(rowptrC), ptr(colC), stream_ptr()),
-              "ocn_csr_minus_fill")
-    return colC[:T]
+    return _csr_setop_fill("ocn_csr_minus_fill", rowptrA, colA, rowptrB, colB, rowptrC, total)
 
 
 def csr_minus(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> Tuple[Tensor, Tensor]:
@@ -1202,42 +1177,55 @@ def csr_minus(rowptrA: Tensor, colA: Tensor, rowptrB: Tensor, colB: Tensor) -> T
     return rowptrC, csr_minus_fill(rowptrA, colA, rowptrB, colB, rowptrC)
 
 
+def _bitrows_update(fn: str, what: str, operands, bits: Tensor) -> Tensor:
+    """The body of ``bitrows_insert`` / ``bitrows_remove`` = ``fn``: ``operands`` = (rowptr, col, name suffix) of the square
+    matrices the entry ``ocn_<fn>`` takes, in its order and with D last; ``what`` names them in the shape error.  Returns the
+    bits changed per row, int32 [n].  A matrix without entries has no column array to point at (A' after every entry has
+    left): the library gets a stand-in nothing reads."""
+    for rp, c, sfx in operands:
+        _req(rp, torch.int64, "rowptr" + sfx, 1); _req(c, torch.int32, "col" + sfx, 1)
+    _req(bits, torch.int32, "bits", 2)
+    n = operands[0][0].numel() - 1
+    if any(rp.numel() != n + 1 for rp, _, _ in operands) or bits.shape[0] != n or bits.shape[1] * 32 < n:
+        raise ValueError(f"{fn}: {what}, D and the bit rows must all be n x n")
+    changed = torch.zeros(n, dtype=torch.int32, device=bits.device)
+    nnzD = operands[-1][1].numel()
+    if n and nnzD:
+        l = _lib.lib()
+        cols = [c if c.numel() else torch.zeros(1, dtype=torch.int32, device=bits.device) for _, c, _ in operands]
+        csr = [p for (rp, _, _), c in zip(operands, cols) for p in (ptr(rp), ptr(c))]
+        ws = torch.empty(int(getattr(l, f"ocn_{fn}_workspace_bytes")(nnzD)), dtype=torch.uint8, device=bits.device)
+        check(getattr(l, f"ocn_{fn}")(*csr, n, nnzD, ptr(bits), bits.shape[1], ptr(changed), ptr(ws), stream_ptr()), f"ocn_{fn}")
+    return changed
+
+
+@_on_device
+def bitrows_insert(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor, rowptrD: Tensor, colD: Tensor, bits: Tensor) -> Tensor:
+    """ocn_hip.h: ocn_bitrows_insert — ``bits`` (the bit rows of A·A, int32 [n, words]) become those of A'·A' IN PLACE, for
+    A' = (rowptrA, colA) = A U D, its transpose (rowptrT, colT) and the new entries D.  Returns ``added`` int32 [n]: the bits
+    turned on per row."""
+    return _bitrows_update("bitrows_insert", "A', its transpose",
+                           [(rowptrA, colA, "A"), (rowptrT, colT, "T"), (rowptrD, colD, "D")], bits)
+
+
 @_on_device
 def bitrows_remove(rowptrA0: Tensor, colA0: Tensor, rowptrT0: Tensor, colT0: Tensor, rowptrA: Tensor, colA: Tensor,
                    rowptrT: Tensor, colT: Tensor, rowptrD: Tensor, colD: Tensor, bits: Tensor) -> Tensor:
     """ocn_hip.h: ocn_bitrows_remove — ``bits`` (the bit rows of A·A, int32 [n, words]) become those of A'·A' IN PLACE, for
     the old A = (rowptrA0, colA0) and its transpose (rowptrT0, colT0), A' = (rowptrA, colA) = A \\ D and its transpose
     (rowptrT, colT), and the removed entries D.  Returns ``removed`` int32 [n]: the bits turned off per row."""
-    for t, name in ((rowptrA0, "rowptrA0"), (rowptrT0, "rowptrT0"), (rowptrA, "rowptrA"), (rowptrT, "rowptrT"), (rowptrD, "rowptrD")):
-        _req(t, torch.int64, name, 1)
-    for t, name in ((colA0, "colA0"), (colT0, "colT0"), (colA, "colA"), (colT, "colT"), (colD, "colD")):
-        _req(t, torch.int32, name, 1)
-    _req(bits, torch.int32, "bits", 2)
-    n = rowptrA0.numel() - 1
-    if any(t.numel() != n + 1 for t in (rowptrT0, rowptrA, rowptrT, rowptrD)) or bits.shape[0] != n or bits.shape[1] * 32 < n:
-        raise ValueError("bitrows_remove: A, A', their transposes, D and the bit rows must all be n x n")
-    removed = torch.zeros(n, dtype=torch.int32, device=bits.device)
-    nnzD = colD.numel()
-    if n and nnzD:
-        l = _lib.lib()
-        # a matrix without entries has no column array to point at (A' after every entry has left): a stand-in nothing reads
-        cols = [c if c.numel() else torch.zeros(1, dtype=torch.int32, device=bits.device) for c in (colA0, colT0, colA, colT)]
-        ws = torch.empty(int(l.ocn_bitrows_remove_workspace_bytes(nnzD)), dtype=torch.uint8, device=bits.device)
-        check(l.ocn_bitrows_remove(ptr(rowptrA0), ptr(cols[0]), ptr(rowptrT0), ptr(cols[1]), ptr(rowptrA), ptr(cols[2]), ptr(rowptrT),
-                                   ptr(cols[3]), ptr(rowptrD), ptr(colD), n, nnzD, ptr(bits), bits.shape[1], ptr(removed), ptr(ws),
-                                   stream_ptr()), "ocn_bitrows_remove")
-    return removed
+    return _bitrows_update("bitrows_remove", "A, A', their transposes",
+                           [(rowptrA0, colA0, "A0"), (rowptrT0, colT0, "T0"), (rowptrA, colA, "A"), (rowptrT, colT, "T"),
+                            (rowptrD, colD, "D")], bits)
 
 
 @_on_device
 def bitrows_to_cols(bits: Tensor, n_cols: int, rowptr: Tensor) -> Tensor:
     """The column ids of dense bit rows, ascending per row, at the row pointers of their counts (ocn_hip.h: ocn_bitrows_fill).
     One host read for the output size."""
-    _req(bits, torch.int32, "bits", 2); _req(rowptr, torch.int64, "rowptr", 1)
+    _req(bits, torch.int32, "bits", 2)
     n = bits.shape[0]
-    if rowptr.numel() != n + 1:
-        raise ValueError("rowptr: one entry per bit row and the total")
-    nnz = _total(rowptr[-1])
+    nnz = _scan_total(rowptr, n, None, "rowptr", "rowptr: one entry per bit row and the total")
     col = torch.empty(max(nnz, 1), dtype=torch.int32, device=bits.device)
     if nnz:
         check(_lib.lib().ocn_bitrows_fill(ptr(bits), bits.shape[1], n, int(n_cols), ptr(rowptr), ptr(col), stream_ptr()), "ocn_bitrows_fill")

@@ -30,8 +30,12 @@ from . import ops
 from .sparse import SparseTensor
 
 
-def _check_args(adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor], fn: str = "insert_edges",
-                arg: str = "new_edges", verb: str = "take new entries") -> int:
+# function -> (the name of its edge argument, what a valued adjacency cannot do), for its error messages
+_WORDS = {"insert_edges": ("new_edges", "take new entries"), "remove_edges": ("edges", "give up entries")}
+
+
+def _check_args(fn: str, adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor]) -> int:
+    arg, verb = _WORDS[fn]
     if not isinstance(adj, SparseTensor) or (adj2 is not None and not isinstance(adj2, SparseTensor)):
         raise ValueError(f"{fn}: adj (and adj2) must be SparseTensor objects")
     if adj.has_value() or (adj2 is not None and not adj2.rows_on_demand() and adj2.has_value()):
@@ -43,6 +47,8 @@ def _check_args(adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor], 
         raise ValueError(f"{fn}: adj2 is {tuple(adj2.sparse_sizes())}, adj {(n, n)}")
     if not isinstance(edges, Tensor) or edges.dtype != torch.int64 or edges.dim() != 2 or edges.shape[0] != 2:
         raise ValueError(f"{fn}: {arg} must be an int64 tensor of shape [2, E]")
+    if edges.device != adj.device():
+        raise ValueError(f"{fn}: {arg} on {edges.device}, adj on {adj.device()}")
     return n
 
 
@@ -67,6 +73,32 @@ def _cpu_pair(row: Tensor, col: Tensor, n: int, with_product: bool):
         p = torch.sparse.mm(a, a).coalesce()                 # walk counts (<= n: exact), every stored entry positive
     pr, pc = p.indices()
     return adj_new, SparseTensor(row=pr, col=pc, sparse_sizes=(n, n), is_sorted=True, trust_data=True)
+
+
+def _delta_csr(fn: str, edges: Tensor, n: int, undirected: bool) -> Tuple[Tensor, Tensor]:
+    """D: the entries ``edges`` names, alone, as a CSR (with their transposes when ``undirected``) — A is never sorted again."""
+    try:
+        return ops.coo_to_csr(edges[0], edges[1], n, n, symmetrize=undirected, dedupe=True)
+    except IndexError as e:
+        raise ValueError(f"{fn}: {_WORDS[fn][0]} holds an index out of range for the adjacency") from e
+
+
+def _bit_row_product(adj2: SparseTensor, bits: Tensor, changed: Tensor, sign: int, n: int) -> SparseTensor:
+    """The product whose bit rows are ``bits`` (those of ``adj2``, updated): its row lengths are ``adj2``'s plus ``sign`` times
+    ``changed`` (int32 [n], the bits turned on or off per row), its columns are read off the bits when somebody asks."""
+    rp2 = adj2._rowptr
+    rowptr2 = ops.scan_i32(torch.add((rp2[1:] - rp2[:-1]).to(torch.int32), changed, alpha=sign))
+    adj2_new = SparseTensor._deferred_product(rowptr2, lambda: ops.bitrows_to_cols(bits, n, rowptr2), bits, (n, n))
+    adj2_new._published("bitmap")
+    return adj2_new
+
+
+def _cpu_route(route, adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor], n: int, undirected: bool, donate: bool):
+    """CPU tensors: the whole job in plain torch by ``route``; a donated ``adj2`` is retired as on the device."""
+    out = route(adj, edges, adj2, n, undirected)
+    if donate and adj2 is not None:
+        _retire(adj2)
+    return out
 
 
 def _insert_cpu(adj: SparseTensor, new_edges: Tensor, adj2: Optional[SparseTensor], n: int, undirected: bool):
@@ -101,18 +133,10 @@ def insert_edges(adj: SparseTensor, new_edges: Tensor, adj2: Optional[SparseTens
     Raises ``ValueError`` for a valued adjacency, for ``new_edges`` of another type or shape and for an index outside the
     matrix (one host read of the device flag of ``ocn_coo_to_csr``).  CPU tensors take a plain torch route of the same
     meaning (concatenate and coalesce; ``torch.sparse.mm``)."""
-    n = _check_args(adj, new_edges, adj2)
-    if new_edges.device != adj.device():
-        raise ValueError(f"insert_edges: new_edges on {new_edges.device}, adj on {adj.device()}")
+    n = _check_args("insert_edges", adj, new_edges, adj2)
     if not new_edges.is_cuda:
-        out = _insert_cpu(adj, new_edges, adj2, n, undirected)
-        if donate and adj2 is not None:
-            _retire(adj2)
-        return out
-    try:                                                     # D: the new entries alone as a CSR — A is never sorted again
-        rowptrD, colD = ops.coo_to_csr(new_edges[0], new_edges[1], n, n, symmetrize=undirected, dedupe=True)
-    except IndexError as e:
-        raise ValueError("insert_edges: new_edges holds an index out of range for the adjacency") from e
+        return _cpu_route(_insert_cpu, adj, new_edges, adj2, n, undirected, donate)
+    rowptrD, colD = _delta_csr("insert_edges", new_edges, n, undirected)
     rowptrN, colN = ops.csr_union(adj._rowptr, adj._col, rowptrD, colD)
     adj_new = SparseTensor(rowptr=rowptrN, col=colN, sparse_sizes=(n, n))
     if adj2 is None:
@@ -124,10 +148,7 @@ def insert_edges(adj: SparseTensor, new_edges: Tensor, adj2: Optional[SparseTens
             bits = bits.clone()
         at = adj_new if undirected else adj_new.t()
         added = ops.bitrows_insert(rowptrN, colN, at._rowptr, at._col, rowptrD, colD, bits)
-        rp2 = adj2._rowptr
-        rowptr2 = ops.scan_i32((rp2[1:] - rp2[:-1]).to(torch.int32) + added)
-        adj2_new = SparseTensor._deferred_product(rowptr2, lambda: ops.bitrows_to_cols(bits, n, rowptr2), bits, (n, n))
-        adj2_new._published("bitmap")
+        adj2_new = _bit_row_product(adj2, bits, added, 1, n)
     else:
         # CSR only: D·A' and A'·D are products with few non-empty rows / few columns — the existing pattern kernels, no bit rows
         p1 = ops.spgemm_pattern(rowptrD, colD, rowptrN, colN, n, want_bitmap=False)
@@ -170,18 +191,10 @@ def remove_edges(adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor] 
     Raises ``ValueError`` for a valued adjacency, for ``edges`` of another type or shape and for an index outside the matrix
     (one host read of the device flag of ``ocn_coo_to_csr``).  CPU tensors take a plain torch route of the same meaning
     (``torch.isin`` on the entry keys; ``torch.sparse.mm``)."""
-    n = _check_args(adj, edges, adj2, "remove_edges", "edges", "give up entries")
-    if edges.device != adj.device():
-        raise ValueError(f"remove_edges: edges on {edges.device}, adj on {adj.device()}")
+    n = _check_args("remove_edges", adj, edges, adj2)
     if not edges.is_cuda:
-        out = _remove_cpu(adj, edges, adj2, n, undirected)
-        if donate and adj2 is not None:
-            _retire(adj2)
-        return out
-    try:                                                     # D: the named entries alone as a CSR — A is never sorted again
-        rowptrD, colD = ops.coo_to_csr(edges[0], edges[1], n, n, symmetrize=undirected, dedupe=True)
-    except IndexError as e:
-        raise ValueError("remove_edges: edges holds an index out of range for the adjacency") from e
+        return _cpu_route(_remove_cpu, adj, edges, adj2, n, undirected, donate)
+    rowptrD, colD = _delta_csr("remove_edges", edges, n, undirected)
     rowptrN, colN = ops.csr_minus(adj._rowptr, adj._col, rowptrD, colD)
     adj_new = SparseTensor(rowptr=rowptrN, col=colN, sparse_sizes=(n, n))
     if adj2 is None:
@@ -195,10 +208,7 @@ def remove_edges(adj: SparseTensor, edges: Tensor, adj2: Optional[SparseTensor] 
         at0, at = (adj, adj_new) if undirected else (adj.t(), adj_new.t())
         removed = ops.bitrows_remove(adj._rowptr, adj._col, at0._rowptr, at0._col, rowptrN, colN, at._rowptr, at._col,
                                      rowptrD, colD, bits)
-        rp2 = adj2._rowptr
-        rowptr2 = ops.scan_i32((rp2[1:] - rp2[:-1]).to(torch.int32) - removed)
-        adj2_new = SparseTensor._deferred_product(rowptr2, lambda: ops.bitrows_to_cols(bits, n, rowptr2), bits, (n, n))
-        adj2_new._published("bitmap")
+        adj2_new = _bit_row_product(adj2, bits, removed, -1, n)
     else:                                                    # CSR only: formed again from A' (a rebuild of the product)
         rp, col, _ = ops.spgemm_pattern(rowptrN, colN, rowptrN, colN, n, want_bitmap=False)
         adj2_new = SparseTensor(rowptr=rp, col=col, sparse_sizes=(n, n))

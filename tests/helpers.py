@@ -1,5 +1,6 @@
 """Shared builders for the parity tests: the same seeded graph as an oracle SpM and as the product
-SparseTensor on the GPU."""
+SparseTensor on the GPU; the builders and bit-exact comparisons of the graph-update tests."""
+import numpy as np
 import torch
 
 from oracle import ocn_oracle as O
@@ -37,3 +38,46 @@ def spm_equal(prod, spm):
 
 def close(a, b, atol=1e-5, rtol=1e-5):
     return torch.allclose(a.detach().cpu(), b.detach().cpu(), atol=atol, rtol=rtol)
+
+
+# ---- graph updates (test_graph_update_gpu.py, test_graph_remove_gpu.py): everything bit-exact ------------------------------------
+def st():
+    from ocn_amd.sparse import SparseTensor
+    return SparseTensor
+
+
+def edges_of(adj):
+    return torch.stack([adj.storage.row(), adj.storage.col()])
+
+
+def random_graph(n, density, seed, symmetric=True, dev="cuda:0"):
+    rng = np.random.default_rng(seed)
+    a = rng.random((n, n)) < density
+    if symmetric:
+        a = a | a.T
+    r, c = np.nonzero(a)
+    ei = torch.from_numpy(np.stack([r, c]).astype(np.int64)).to(dev)
+    return st().from_edge_index(ei, sparse_sizes=(n, n))
+
+
+def same_adj(got, want):
+    assert got._rowptr.dtype == torch.int64 and got._col.dtype == torch.int32
+    assert torch.equal(got._rowptr, want._rowptr)
+    assert torch.equal(got._col, want._col)
+
+
+def same_product(got, want, bits=True):
+    """Indistinguishable from the product formed from scratch: bit rows, row pointers, nnz and the ids behind the thunk."""
+    if bits:
+        assert got.product_bit_rows() is not None and want.product_bit_rows() is not None
+        assert torch.equal(got.product_bit_rows(), want.product_bit_rows())
+    assert torch.equal(got._rowptr, want._rowptr)
+    assert got.nnz() == want.nnz()
+    assert got._col.dtype == torch.int32 and torch.equal(got._col, want._col)
+
+
+def csr_of_rows(rows, dev="cuda:0"):
+    """(rowptr int64, col int32) on the device from one list of column ids per row."""
+    rp = torch.tensor([0] + list(np.cumsum([len(r) for r in rows])), dtype=torch.int64, device=dev)
+    col = torch.tensor([c for r in rows for c in r], dtype=torch.int32, device=dev)
+    return rp, col

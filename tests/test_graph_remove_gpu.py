@@ -7,23 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import csr_of_rows as _csr, edges_of as _edges_of, product_adj2 as _product, random_graph as _graph, \
+    same_adj as _same_adj, same_product as _same_product, st as _st
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _st():
-    from ocn_amd.sparse import SparseTensor
-    return SparseTensor
-
-
-def _product(adj):
-    sp = adj.to_torch_sparse_coo_tensor()
-    return _st().from_torch_sparse_coo_tensor(sp @ sp, False)
-
-
-def _edges_of(adj):
-    return torch.stack([adj.storage.row(), adj.storage.col()])
 
 
 def _dev(a):
@@ -39,31 +28,6 @@ def _scratch(adj, gone, undirected=True):
         key = torch.cat([key, gone[1] * n + gone[0]])
     out = _st().from_edge_index(ei[:, ~torch.isin(ei[0] * n + ei[1], key)], sparse_sizes=(n, n))
     return out, _product(out)
-
-
-def _graph(n, density, seed, symmetric=True):
-    rng = np.random.default_rng(seed)
-    a = rng.random((n, n)) < density
-    if symmetric:
-        a = a | a.T
-    r, c = np.nonzero(a)
-    return _st().from_edge_index(_dev(np.stack([r, c])), sparse_sizes=(n, n))
-
-
-def _same_adj(got, want):
-    assert got._rowptr.dtype == torch.int64 and got._col.dtype == torch.int32
-    assert torch.equal(got._rowptr, want._rowptr)
-    assert torch.equal(got._col, want._col)
-
-
-def _same_product(got, want, bits=True):
-    """Indistinguishable from the product formed from scratch: bit rows, row pointers, nnz and the ids behind the thunk."""
-    if bits:
-        assert got.product_bit_rows() is not None and want.product_bit_rows() is not None
-        assert torch.equal(got.product_bit_rows(), want.product_bit_rows())
-    assert torch.equal(got._rowptr, want._rowptr)
-    assert got.nnz() == want.nnz()
-    assert got._col.dtype == torch.int32 and torch.equal(got._col, want._col)
 
 
 def _check(adj, gone, undirected=True, donate=False):
@@ -399,12 +363,6 @@ def test_updated_pair_feeds_the_scoring_and_recommendation_loops(hiplib):
 
 
 # ---- the difference entries directly --------------------------------------------------------------------------------------------
-def _csr(rows):
-    rp = torch.tensor([0] + list(np.cumsum([len(r) for r in rows])), dtype=torch.int64, device=DEV)
-    col = torch.tensor([c for r in rows for c in r], dtype=torch.int32, device=DEV)
-    return rp, col
-
-
 def _keys(rows, n_cols):
     return torch.tensor([r * n_cols + c for r, row in enumerate(rows) for c in row], dtype=torch.int64)
 

@@ -7,23 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import csr_of_rows as _csr, edges_of as _edges_of, product_adj2 as _product, random_graph as _graph, \
+    same_adj as _same_adj, same_product as _same_product, st as _st
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _st():
-    from ocn_amd.sparse import SparseTensor
-    return SparseTensor
-
-
-def _product(adj):
-    sp = adj.to_torch_sparse_coo_tensor()
-    return _st().from_torch_sparse_coo_tensor(sp @ sp, False)
-
-
-def _edges_of(adj):
-    return torch.stack([adj.storage.row(), adj.storage.col()])
 
 
 def _scratch(adj, new, undirected=True):
@@ -32,32 +21,6 @@ def _scratch(adj, new, undirected=True):
     out = _st().from_edge_index(torch.cat([_edges_of(adj), new], dim=1), sparse_sizes=(n, n))
     out = out.to_symmetric() if undirected else out.coalesce()
     return out, _product(out)
-
-
-def _graph(n, density, seed, symmetric=True):
-    rng = np.random.default_rng(seed)
-    a = rng.random((n, n)) < density
-    if symmetric:
-        a = a | a.T
-    r, c = np.nonzero(a)
-    ei = torch.from_numpy(np.stack([r, c]).astype(np.int64)).to(DEV)
-    return _st().from_edge_index(ei, sparse_sizes=(n, n))
-
-
-def _same_adj(got, want):
-    assert got._rowptr.dtype == torch.int64 and got._col.dtype == torch.int32
-    assert torch.equal(got._rowptr, want._rowptr)
-    assert torch.equal(got._col, want._col)
-
-
-def _same_product(got, want, bits=True):
-    """Indistinguishable from the product formed from scratch: bit rows, row pointers, nnz and the ids behind the thunk."""
-    if bits:
-        assert got.product_bit_rows() is not None and want.product_bit_rows() is not None
-        assert torch.equal(got.product_bit_rows(), want.product_bit_rows())
-    assert torch.equal(got._rowptr, want._rowptr)
-    assert got.nnz() == want.nnz()
-    assert got._col.dtype == torch.int32 and torch.equal(got._col, want._col)
 
 
 def _check(adj, new, undirected=True, donate=False):
@@ -280,12 +243,6 @@ def test_updated_pair_feeds_the_scoring_and_recommendation_loops(hiplib):
 
 
 # ---- the union entries directly ------------------------------------------------------------------------------------------------
-def _csr(rows, n_cols):
-    rp = torch.tensor([0] + list(np.cumsum([len(r) for r in rows])), dtype=torch.int64, device=DEV)
-    col = torch.tensor([c for r in rows for c in r], dtype=torch.int32, device=DEV)
-    return rp, col
-
-
 def _union_reference(rows_a, rows_b, n_cols):
     """torch.unique of the concatenated (row, column) keys."""
     key = torch.tensor([r * n_cols + c for rows in (rows_a, rows_b) for r, row in enumerate(rows) for c in row], dtype=torch.int64)
@@ -298,7 +255,7 @@ def _union_reference(rows_a, rows_b, n_cols):
 
 def _check_union(rows_a, rows_b, n_cols):
     from ocn_amd import ops
-    a, b = _csr(rows_a, n_cols), _csr(rows_b, n_cols)
+    a, b = _csr(rows_a), _csr(rows_b)
     want_rp, want_col = _union_reference(rows_a, rows_b, n_cols)
     for x, y in ((a, b), (b, a)):                                # the union is symmetric in its operands
         cnt = ops.csr_union_count(x[0], x[1], y[0], y[1])
