@@ -30,7 +30,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
-from ocn_amd.update import insert_edges, remove_edges                               # noqa: E402
+from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
@@ -151,18 +151,31 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1.
     --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route.
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
-    --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original."""
+    --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original.
+    --recommend-check-refresh: the refreshed node embeddings are compared with a full encoder pass after either update."""
     dev = data.x.device
     adj = data.full_adj_t
     adj2 = None if args.recommend_walk else build_adj2(adj, args)
     sources = split_edge['test']['edge'][:n_sources, 0].to(dev).contiguous()
 
+    state = None
+    if not args.heuristic:
+        model.eval(); predictor.eval()
+        if args.recommend_accept > 0:
+            state = EncoderState(model, data.x, adj)      # h and its per-layer activations stay resident beside A and A²
+
+    def refreshed(adj, edges, tag):
+        rows = state.refresh(adj, edges)                  # only the rows the update can reach are recomputed
+        print(f"refreshed {rows.numel()} of {state.n} embedding rows after {tag} ({state.route} route)", flush=True)
+        if args.recommend_check_refresh and not torch.equal(state.h, model(data.x, adj)):
+            raise SystemExit(f"--recommend-check-refresh: the refreshed embeddings differ from a full pass after {tag}")
+
     def top(adj, adj2, tag):
         if args.heuristic:
             dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
         else:
-            model.eval(); predictor.eval()
-            dst, score = recommend_links(predictor, model(data.x, adj), adj, adj2, sources, k, args.testbs, args)
+            h = state.h if state is not None else model(data.x, adj)
+            dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args)
         for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
             print(f"{tag} source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
                   flush=True)
@@ -171,7 +184,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     dst, score = top(adj, adj2, "recommend")
     if args.recommend_accept > 0:
         # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
-        # updated, not rebuilt; the encoder is simply run again) and the same sources are asked again
+        # updated, not rebuilt; the node embeddings are refreshed row by row, EncoderState) and the same sources are asked again
         pairs = torch.stack([sources.view(-1, 1).expand_as(dst).reshape(-1), dst.reshape(-1)])
         flat = score.reshape(-1).masked_fill(pairs[1] < 0, float("-inf"))
         best = flat.topk(min(args.recommend_accept, flat.numel())).indices
@@ -179,11 +192,15 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         was, was2 = adj, adj2
         adj, adj2 = insert_edges(adj, accepted, adj2, donate=not args.recommend_undo)     # (an undo keeps the old pair to compare with)
         print(f"accepted {accepted.shape[1]} links: " + " ".join(f"{a}-{b}" for a, b in accepted.t().tolist()), flush=True)
+        if state is not None:
+            refreshed(adj, accepted, "accepting")
         dst, score = top(adj, adj2, "recommend after accepting")
         if args.recommend_undo:
             # --recommend-undo: the accepted links leave again (ocn_amd.update.remove_edges: A' = A \ D, the bits of A² that lose
             # their last witness cleared).  Recommended links are non-edges, so the round trip is exact
             adj, adj2 = remove_edges(adj, accepted, adj2, donate=True)
+            if state is not None:
+                refreshed(adj, accepted, "the undo")
             same = torch.equal(adj._rowptr, was._rowptr) and torch.equal(adj._col, was._col)
             if adj2 is not None:
                 same = same and torch.equal(adj2._rowptr, was2._rowptr) and torch.equal(adj2._col, was2._col)
@@ -234,7 +251,12 @@ def main(argv=None):
     ap.add_argument("--recommend-undo", action="store_true",
                     help="with --recommend-accept: remove the accepted links again (ocn_amd.update.remove_edges) and check that the "
                          "adjacency and A² are restored exactly")
+    ap.add_argument("--recommend-check-refresh", action="store_true",
+                    help="with --recommend-accept and a model: assert that the refreshed node embeddings (ocn_amd.update.EncoderState) "
+                         "equal a full encoder pass bit for bit after the insert, and after the undo")
     args = ap.parse_args(argv)
+    if args.recommend_check_refresh and (args.heuristic or not (args.recommend and args.recommend_accept > 0)):
+        ap.error("--recommend-check-refresh: needs a model and --recommend K --recommend-accept M")
     if args.recommend_undo and not (args.recommend and args.recommend_accept > 0):
         ap.error("--recommend-undo: needs --recommend K --recommend-accept M")
     if args.recommend_walk and args.heuristic in TWO_HOP:

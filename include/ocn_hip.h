@@ -42,7 +42,9 @@ extern "C" {
  *    expanded from A, where A² is not stored); ocn_philox4x32, ocn_complement_count, ocn_sample_stage_cols,
  *    ocn_sample_complement_rows, ocn_sample_complement_pairs (structured negative sampling); ocn_csr_union_count / _fill,
  *    ocn_bitrows_insert_workspace_bytes, ocn_bitrows_insert (edge insertion into a resident graph); ocn_csr_minus_count /
- *    _fill, ocn_bitrows_remove_workspace_bytes, ocn_bitrows_remove (edge removal from a resident graph). */
+ *    _fill, ocn_bitrows_remove_workspace_bytes, ocn_bitrows_remove (edge removal from a resident graph); ocn_spmm_csr_rows,
+ *    ocn_rows_neighbourhood_workspace_bytes, ocn_rows_neighbourhood, ocn_bitlist_count / _fill (refreshing the node embeddings
+ *    after an edge update: only the rows that can have changed). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -525,6 +527,20 @@ int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, in
                  int32_t mode, int32_t edge_scale, int32_t self_mode,
                  float* y, void* stream);
 
+/* ocn_spmm_csr restricted to a list of output rows (refreshing the encoder output after an edge update, ocn_amd.update):
+ * rows = int64 [n_list], ascending, duplicate-free, each in [0, n_rows); y is COMPACT, [n_list][F], and row i of it holds
+ * what ocn_spmm_csr writes to row rows[i] of its y, bit for bit — the two entries launch one kernel body, which differs in where
+ * a lane group takes its row id from (the list instead of the launch coordinates) and in nothing else: the terms of a row are
+ * added in the same (column) order.  Every other operand means what it means above: pre is indexed by the GLOBAL column id,
+ * post and the self term by the GLOBAL row id rows[i]; x has a row per column of the operator.  y must not overlap x (rows are
+ * gathered from x while others are written).  A listed id outside [0, n_rows) gives a zero row; nothing is indexed with it.
+ * F in {16, 32, 64, 128, 256, 512}.  NULL rowptr / col / x / rows / y, n_rows < 0, n_list < 0, another F, a mode or self_mode
+ * out of range: OCN_EINVAL before any launch.  n_list == 0 returns 0. */
+int ocn_spmm_csr_rows(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows,
+                      const float* x, int32_t F, const float* pre, const float* post,
+                      int32_t mode, int32_t edge_scale, int32_t self_mode,
+                      const int64_t* rows, int64_t n_list, float* y, void* stream);
+
 /* Max aggregation under autograd (model.py:42-55 aggr "max", pygho spmm aggr "amax", model.py:101-102).
  * ocn_spmm_csr_max_arg: y[i,f] = max over row i of fl(val_ik * x[k,f]) (val NULL: x[k,f]) and arg[i,f] = the column id
  *   k of the winner, the first maximum in the row's (ascending column) order; an empty row gives y = 0, arg = -1.
@@ -659,6 +675,28 @@ int ocn_bitrows_remove(const int64_t* rowptrA0, const int32_t* colA0, const int6
                        const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
                        const int64_t* rowptrD, const int32_t* colD, int64_t n, int64_t nnzD, uint32_t* bits,
                        int64_t bm_stride_words, int32_t* removed, void* workspace, void* stream);
+
+/* Which rows an edge update can reach (ocn_amd.update.EncoderState): the closed neighbourhood of a row list, as bits.
+ *
+ * ocn_rows_neighbourhood: (rowptrT, colT) = the n x n CSR whose row k lists the rows that READ column k — the transpose of the
+ * adjacency, the adjacency itself where it is symmetric.  rows = int64 [n_list] (any order, duplicates allowed; an id outside
+ * [0, n) is skipped).  bits = ONE bit row, uint32 [ceil(n / 32)], owned by the caller and OR-ed into, never cleared: on return
+ * the bit of every listed row and of every column of those rows is set (32-bit atomicOr, as ocn_bitrows_insert sets its bits).
+ * Work items are chunks of at most 256 row elements, scheduled by a scan of ceil(len / 256) as in ocn_bitrows_insert: a hub row
+ * is spread over many waves.  workspace: ocn_rows_neighbourhood_workspace_bytes(n_list) bytes, any content (16-byte aligned).
+ * NULL pointers, n < 0, n_list < 0 or >= 2^30: OCN_EINVAL before any HIP call.  n == 0 or n_list == 0 returns 0.
+ *
+ * ocn_bitlist_count / ocn_bitlist_fill: one bit row of n_bits bits as the ascending list of its set bits' ids, a thread per
+ * word (ocn_bitrows_count / _fill walk a row on one wave: right for many rows, serial for one long one).  count (int32
+ * [ceil(n_bits / 32)], the population of each word, bits at or past n_bits ignored) -> ocn_scan_i32 -> fill (out int64 [total],
+ * word w's ids from out[off[w]] on; nothing is written at or past off[w + 1]).  NULL pointers or n_bits < 0: OCN_EINVAL before
+ * any HIP call.  n_bits == 0 returns 0. */
+int64_t ocn_rows_neighbourhood_workspace_bytes(int64_t n_list);
+int ocn_rows_neighbourhood(const int64_t* rowptrT, const int32_t* colT, int64_t n, const int64_t* rows, int64_t n_list,
+                           uint32_t* bits, void* workspace, void* stream);
+int ocn_bitlist_count(const uint32_t* bits, int64_t n_bits, int32_t* count, void* stream);
+int ocn_bitlist_fill(const uint32_t* bits, int64_t n_bits, const int64_t* off /* [words + 1], from ocn_scan_i32 */, int64_t* out,
+                     void* stream);
 
 /* Glue for head layouts the fused Linear kernel below does not cover (widths outside 32..256, training
  * mode; model.py:2203-2235, 2429-2437): y = LayerNorm(x) (eps, affine gamma/beta) followed by ReLU when `relu` != 0,

@@ -92,6 +92,7 @@ SIGNATURES = {
     "ocn_mix3_workspace_bytes": (c_int64, []),
     "ocn_mix3_backward": (c_int32, [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     "ocn_spmm_csr": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "ocn_spmm_csr_rows": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
     "ocn_spmm_csr_max_arg": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, _P, _P, _P]),
     "ocn_spmm_max_backward": (c_int32, [_P, _P, _P, c_int64, _P, _P, c_int32, _P, _P]),
     "ocn_deg_rsqrt": (c_int32, [_P, _P, c_int64, c_float, _P, _P]),
@@ -112,6 +113,10 @@ SIGNATURES = {
     "ocn_csr_minus_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P]),
     "ocn_bitrows_remove_workspace_bytes": (c_int64, [c_int64]),
     "ocn_bitrows_remove": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P]),
+    "ocn_rows_neighbourhood_workspace_bytes": (c_int64, [c_int64]),
+    "ocn_rows_neighbourhood": (c_int32, [_P, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "ocn_bitlist_count": (c_int32, [_P, c_int64, _P, _P]),
+    "ocn_bitlist_fill": (c_int32, [_P, c_int64, _P, _P, _P]),
     "ocn_rows_ln_relu": (c_int32, [_P, _P, _P, c_float, c_int32, c_int64, c_int32, _P, _P]),
     "ocn_fill_rows": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "ocn_combine3": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P]),

@@ -11,6 +11,9 @@
 // Edge removal, further down: A' = A \ D as a row-wise difference, and the bit rows of A² turned into those of A'·A' by
 // deciding again every bit that had a witness walk through a removed entry — bit (r, k) stays exactly when row r of A' and
 // row k of A'^T share a column (ocn_csr_minus_count / ocn_csr_minus_fill, ocn_bitrows_remove).
+//
+// Which rows of the encoder output an update can reach, last: the closed neighbourhood of a row list as one bit row, on the
+// same chunked schedule, and a bit row as an ascending id list (ocn_rows_neighbourhood, ocn_bitlist_count / _fill).
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -320,6 +323,69 @@ __global__ __launch_bounds__(OCN_BLOCK) void br_apply_kernel(const i64* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// the closed neighbourhood of a row list, as bits; bits as an ascending id list
+// ---------------------------------------------------------------------------------------------
+// Listed row i learns the number of its items, the chunks of its row of (rowptrT, colT), and sets its own bit.  An id outside
+// [0, n) has no items and no bit.
+__global__ __launch_bounds__(OCN_BLOCK) void rn_items_kernel(const i64* __restrict__ rowptrT, const i64* __restrict__ rows, i64 n_list,
+                                                             i64 n, int32_t* __restrict__ items, unsigned* __restrict__ bits) {
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += (i64)gridDim.x * blockDim.x) {
+    const i64 r = rows[i];
+    int32_t c = 0;
+    if (r >= 0 && r < n) {
+      c = (int32_t)((rowptrT[r + 1] - rowptrT[r] + BI_CHUNK - 1) / BI_CHUNK);
+      atomicOr(bits + (r >> 5), 1u << (r & 31));
+    }
+    items[i] = c;
+  }
+}
+
+// The schedule of bi_apply_kernel over a row list: a wave takes work item w by grid stride, the last i with off[i] <= w names
+// the listed row, w - off[i] the chunk of at most BI_CHUNK of its elements; every lane sets the bit of one column per round.
+__global__ __launch_bounds__(OCN_BLOCK) void rn_apply_kernel(const i64* __restrict__ rowptrT, const int32_t* __restrict__ colT,
+                                                             const i64* __restrict__ rows, const i64* __restrict__ off, i64 n_list,
+                                                             i64 n, unsigned* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const i64 total = off[n_list];
+  for (i64 w = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); w < total; w += (i64)gridDim.x * OCN_WPB) {
+    i64 chunk;
+    const i64 i = bi_item(off, n_list, w, chunk);
+    const i64 r = rows[i];
+    if (r < 0 || r >= n) continue;                         // (such a row has no items; nothing is indexed with it)
+    i64 p1;
+    const i64 p0 = bi_chunk(rowptrT, r, chunk, p1);
+    for (i64 q = p0 + lane; q < p1; q += OCN_WAVE) {
+      const i64 k = colT[q];
+      if (k >= 0 && k < n) atomicOr(bits + (k >> 5), 1u << (k & 31));
+    }
+  }
+}
+
+// One thread per 32-bit word of a bit vector of n_bits bits: FILL == false leaves the word's population in count[w] (bits at
+// or past n_bits do not count), FILL == true writes the ids of its bits, ascending, from out[off[w]] on.
+template <bool FILL>
+__global__ __launch_bounds__(OCN_BLOCK) void bitlist_kernel(const unsigned* __restrict__ bits, i64 n_bits, int32_t* __restrict__ count,
+                                                            const i64* __restrict__ off, i64* __restrict__ out) {
+  const i64 words = (n_bits + 31) >> 5;
+  for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (i64)gridDim.x * blockDim.x) {
+    unsigned b = bits[w];
+    const i64 left = n_bits - (w << 5);
+    if (left < 32) b &= (1u << left) - 1u;
+    if (!FILL) {
+      count[w] = __popc(b);
+    } else {
+      i64* o = out + off[w];
+      const i64 end = off[w + 1];                          // (offsets of another vector write nothing past their own segment)
+      while (b && o < out + end) {
+        const int q = __ffs((int)b) - 1;
+        b &= b - 1;
+        *o++ = (w << 5) + q;
+      }
+    }
+  }
+}
+
 // One launch for the four set-operation entries: which kernel, and which of its outputs must be there.
 static int csr_setop_launch(bool minus, bool fill, const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrB,
                             const int32_t* colB, int64_t n_rows, int32_t* count, const int64_t* rowptrC, int32_t* colC,
@@ -428,6 +494,53 @@ int ocn_bitrows_remove(const int64_t* rowptrA0, const int32_t* colA0, const int6
                      (hipStream_t)stream, (const i64*)rowptrA0, colA0, (const i64*)rowptrT0, colT0, (const i64*)rowptrA, colA,
                      (const i64*)rowptrT, colT, colD, erow, off, (i64)(2 * nnzD), (i64)n, (unsigned*)bits,
                      (i64)bm_stride_words, removed);
+  return launch_status();
+}
+
+int64_t ocn_rows_neighbourhood_workspace_bytes(int64_t n_list) {
+  // items int32[n_list] | off int64[n_list + 1] | scan state
+  if (n_list < 0) return 0;
+  return bi_align(n_list * 4) + bi_align((n_list + 1) * 8) + bi_align(ocn_scan_workspace_bytes(n_list)) + 64;
+}
+
+int ocn_rows_neighbourhood(const int64_t* rowptrT, const int32_t* colT, int64_t n, const int64_t* rows, int64_t n_list,
+                           uint32_t* bits, void* workspace, void* stream) {
+  if (n < 0 || n_list < 0 || n_list > 0x3fffffffll) return OCN_EINVAL;
+  if (!rowptrT || !colT || !rows || !bits || !workspace) return OCN_EINVAL;
+  if (n == 0 || n_list == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int32_t* items = (int32_t*)ws;
+  i64* off = (i64*)(ws + bi_align(n_list * 4));
+  int32_t* scan_ws = (int32_t*)((char*)off + bi_align((n_list + 1) * 8));
+  const i64 sw = bi_align(ocn_scan_workspace_bytes(n_list));
+  hipLaunchKernelGGL(bi_zero_kernel, dim3(1), dim3(OCN_BLOCK), 0, st, scan_ws, (i64)(sw / 4));   // the scan state starts zero
+  hipLaunchKernelGGL(rn_items_kernel, dim3(grid_for((n_list + OCN_BLOCK - 1) / OCN_BLOCK, 1024)), dim3(OCN_BLOCK), 0, st,
+                     (const i64*)rowptrT, (const i64*)rows, (i64)n_list, (i64)n, items, (unsigned*)bits);
+  const int rc = ocn_scan_i32(items, n_list, (int64_t*)off, scan_ws, stream);
+  if (rc) return rc;
+  // (the item count is known on the device only: at least 256 workgroups, so that one listed hub row is not four waves' work)
+  const i64 blocks = (n_list + OCN_WPB - 1) / OCN_WPB;
+  hipLaunchKernelGGL(rn_apply_kernel, dim3(grid_for(blocks < 256 ? 256 : blocks, 2048)), dim3(OCN_BLOCK), 0, st,
+                     (const i64*)rowptrT, colT, (const i64*)rows, (const i64*)off, (i64)n_list, (i64)n, (unsigned*)bits);
+  return launch_status();
+}
+
+int ocn_bitlist_count(const uint32_t* bits, int64_t n_bits, int32_t* count, void* stream) {
+  if (n_bits < 0 || !bits || !count) return OCN_EINVAL;
+  if (n_bits == 0) return 0;
+  const i64 words = (n_bits + 31) / 32;
+  hipLaunchKernelGGL((bitlist_kernel<false>), dim3(grid_for((words + OCN_BLOCK - 1) / OCN_BLOCK, 4096)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const unsigned*)bits, (i64)n_bits, count, (const i64*)nullptr, (i64*)nullptr);
+  return launch_status();
+}
+
+int ocn_bitlist_fill(const uint32_t* bits, int64_t n_bits, const int64_t* off, int64_t* out, void* stream) {
+  if (n_bits < 0 || !bits || !off || !out) return OCN_EINVAL;
+  if (n_bits == 0) return 0;
+  const i64 words = (n_bits + 31) / 32;
+  hipLaunchKernelGGL((bitlist_kernel<true>), dim3(grid_for((words + OCN_BLOCK - 1) / OCN_BLOCK, 4096)), dim3(OCN_BLOCK), 0,
+                     (hipStream_t)stream, (const unsigned*)bits, (i64)n_bits, (int32_t*)nullptr, (const i64*)off, (i64*)out);
   return launch_status();
 }
 

@@ -38,18 +38,30 @@ __device__ __forceinline__ void red4(float4& acc, float w, bool weighted, const 
   }
 }
 
-template <int LPE, int NV, int MODE>
+// LIST == false: lane group g of the launch owns output row g.  LIST == true (ocn_spmm_csr_rows): it owns the row rows[g]
+// of the operator and writes row g of a compact y [n_list][F] — pre, post and the self term keep the GLOBAL row id.  The row
+// id is all that differs: one body, so the two entries add a row's terms in the same order and give the same bits.  A listed
+// id outside [0, n_rows) gives a zero row (nothing is indexed with it).
+template <int LPE, int NV, int MODE, bool LIST>
 __global__ __launch_bounds__(OCN_BLOCK) void spmm_csr_kernel(
     const i64* __restrict__ rowptr, const int32_t* __restrict__ col, i64 n_rows,
     const float* __restrict__ val, const float* __restrict__ x, int F, const float* __restrict__ pre,
-    const float* __restrict__ post, int edge_scale, int self_mode, float* __restrict__ y) {
+    const float* __restrict__ post, int edge_scale, int self_mode, float* __restrict__ y,
+    const i64* __restrict__ rows, i64 n_list) {
   constexpr int GPW = OCN_WAVE / LPE;
   constexpr int UNR = 4;
   const int lane = threadIdx.x & 63;
   const int gl = lane % LPE;
   const int gbase = lane - gl;
-  const i64 r = ((i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
-  if (r >= n_rows) return;
+  const i64 slot = ((i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  if (slot >= (LIST ? n_list : n_rows)) return;
+  const i64 r = LIST ? rows[slot] : slot;
+  if (LIST && (r < 0 || r >= n_rows)) {
+    float4* z = reinterpret_cast<float4*>(y) + slot * (F >> 2) + gl;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) z[v * LPE] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   const i64 a0 = rowptr[r], da = rowptr[r + 1] - a0;
   const float4* x4 = reinterpret_cast<const float4*>(x);
   const i64 rowq = F >> 2;
@@ -118,7 +130,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void spmm_csr_kernel(
     ++seen;
   }
   const float po = post ? post[r] : 1.0f;
-  float4* o = reinterpret_cast<float4*>(y) + r * rowq + gl;
+  float4* o = reinterpret_cast<float4*>(y) + slot * rowq + gl;
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     float4 a = acc[v];
@@ -280,11 +292,15 @@ extern "C" {
 
 #define SPMM_ARGS (const i64*)rowptr, col, (i64)n_rows, val, x, (int)F, pre, post, (int)edge_scale, \
                   (int)self_mode, y
+// n_out lane groups: the operator's rows, or (LIST) the listed ones
 #define LAUNCH_SPMM(LPE, NV, MODE)                                                                  \
   do {                                                                                              \
     const i64 rpb = (i64)OCN_WPB * (OCN_WAVE / (LPE));                                              \
-    hipLaunchKernelGGL((spmm_csr_kernel<LPE, NV, MODE>), dim3((unsigned)((n_rows + rpb - 1) / rpb)),\
-                       dim3(OCN_BLOCK), 0, st, SPMM_ARGS);                                          \
+    const dim3 grid((unsigned)((n_out + rpb - 1) / rpb));                                           \
+    if (rows) hipLaunchKernelGGL((spmm_csr_kernel<LPE, NV, MODE, true>), grid, dim3(OCN_BLOCK), 0, st, SPMM_ARGS, \
+                                 (const i64*)rows, (i64)n_out);                                     \
+    else hipLaunchKernelGGL((spmm_csr_kernel<LPE, NV, MODE, false>), grid, dim3(OCN_BLOCK), 0, st, SPMM_ARGS, \
+                            (const i64*)nullptr, (i64)0);                                           \
   } while (0)
 #define DISPATCH_SPMM(MODE)                                                                         \
   do {                                                                                              \
@@ -297,17 +313,24 @@ extern "C" {
     else return OCN_EINVAL; /* feature widths of the reference configs only (16..512, pow2) */      \
   } while (0)
 
+// rows == NULL: every row of the operator (n_out = n_rows); else the n_out listed ones into a compact y
+static int spmm_launch(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, const float* x,
+                       int32_t F, const float* pre, const float* post, int32_t mode, int32_t edge_scale,
+                       int32_t self_mode, float* y, const int64_t* rows, int64_t n_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == SPMM_SUM) DISPATCH_SPMM(SPMM_SUM);
+  else if (mode == SPMM_MEAN) DISPATCH_SPMM(SPMM_MEAN);
+  else DISPATCH_SPMM(SPMM_MAX);
+  return launch_status();
+}
+
 int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, const float* x,
                  int32_t F, const float* pre, const float* post, int32_t mode, int32_t edge_scale,
                  int32_t self_mode, float* y, void* stream) {
   if (n_rows < 0 || F <= 0 || mode < 0 || mode > 2 || self_mode < 0 || self_mode > 2) return OCN_EINVAL;
   if (n_rows == 0) return 0;
   if (!rowptr || !x || !y) return OCN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == SPMM_SUM) DISPATCH_SPMM(SPMM_SUM);
-  else if (mode == SPMM_MEAN) DISPATCH_SPMM(SPMM_MEAN);
-  else DISPATCH_SPMM(SPMM_MAX);
-  return launch_status();
+  return spmm_launch(rowptr, col, val, n_rows, x, F, pre, post, mode, edge_scale, self_mode, y, nullptr, n_rows, stream);
 }
 
 // F -> (lanes per row, float4 per lane) of the lane-group kernels above: the widths of DISPATCH_SPMM
@@ -323,6 +346,15 @@ int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, in
 
 static inline bool spmm_width_ok(int32_t F) {
   return F == 16 || F == 32 || F == 64 || F == 128 || F == 256 || F == 512;
+}
+
+int ocn_spmm_csr_rows(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, const float* x,
+                      int32_t F, const float* pre, const float* post, int32_t mode, int32_t edge_scale,
+                      int32_t self_mode, const int64_t* rows, int64_t n_list, float* y, void* stream) {
+  if (n_rows < 0 || n_list < 0 || !spmm_width_ok(F) || mode < 0 || mode > 2 || self_mode < 0 || self_mode > 2) return OCN_EINVAL;
+  if (!rowptr || !col || !x || !rows || !y) return OCN_EINVAL;
+  if (n_list == 0 || n_rows == 0) return 0;
+  return spmm_launch(rowptr, col, val, n_rows, x, F, pre, post, mode, edge_scale, self_mode, y, rows, n_list, stream);
 }
 
 int ocn_spmm_csr_max_arg(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, const float* x,

@@ -1039,6 +1039,37 @@ def spmm_csr(rowptr: Tensor, col: Tensor, x: Tensor, pre: Optional[Tensor] = Non
 
 
 @_on_device
+def spmm_csr_rows(rowptr: Tensor, col: Tensor, x: Tensor, rows: Tensor, pre: Optional[Tensor] = None,
+                  post: Optional[Tensor] = None, mode: str = "sum", edge_scale: bool = False,
+                  self_mode: int = 0, val: Optional[Tensor] = None) -> Tensor:
+    """``spmm_csr(...)[rows]`` without forming the other rows (ocn_hip.h: ocn_spmm_csr_rows): a compact ``[len(rows), F]``
+    matrix, bit for bit the listed rows of the full product — both entries run one kernel body.  ``rows``: int64, ascending,
+    duplicate-free, each in ``[0, n)``; ``pre`` / ``post`` stay indexed by global ids.  The result is a new tensor: the launch
+    never writes into ``x``."""
+    _req(rowptr, torch.int64, "rowptr", 1); _req(col, torch.int32, "col", 1)
+    _req(x, torch.float32, "x", 2); _req(rows, torch.int64, "rows", 1)
+    n = rowptr.numel() - 1
+    if x.shape[1] not in LN_WIDTHS:
+        raise ValueError(f"spmm_csr_rows: unsupported width {x.shape[1]}")
+    if pre is not None and (_req(pre, torch.float32, "pre", 1).numel() != x.shape[0]):
+        raise ValueError("pre must have one entry per row of x")
+    if post is not None and (_req(post, torch.float32, "post", 1).numel() != n):
+        raise ValueError("post must have one entry per output row")
+    if self_mode and x.shape[0] != n:
+        raise ValueError("self term needs a square operator")
+    if val is not None and _req(val, torch.float32, "val", 1).numel() != col.numel():
+        raise ValueError("val must have one entry per stored column")
+    y = torch.empty(rows.numel(), x.shape[1], dtype=torch.float32, device=x.device)
+    if rows.numel():
+        if not col.numel():                               # no entries: no column array to point at; nothing reads the stand-in
+            col = torch.zeros(1, dtype=torch.int32, device=x.device)
+        check(_lib.lib().ocn_spmm_csr_rows(ptr(rowptr), ptr(col), ptr(val), n, ptr(x), x.shape[1], ptr(pre), ptr(post),
+                                           SPMM_MODES[mode], int(edge_scale), int(self_mode), ptr(rows), rows.numel(), ptr(y),
+                                           stream_ptr()), "ocn_spmm_csr_rows")
+    return y
+
+
+@_on_device
 def spmm_max_arg(rowptr: Tensor, col: Tensor, x: Tensor, val: Optional[Tensor] = None,
                  n_cols: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """(y, arg): y = the max aggregation of ``spmm_csr(mode="max")`` (valued: max_k val_ik * x_k), arg [n, F] int32 = the
@@ -1217,6 +1248,55 @@ def bitrows_remove(rowptrA0: Tensor, colA0: Tensor, rowptrT0: Tensor, colT0: Ten
     return _bitrows_update("bitrows_remove", "A, A', their transposes",
                            [(rowptrA0, colA0, "A0"), (rowptrT0, colT0, "T0"), (rowptrA, colA, "A"), (rowptrT, colT, "T"),
                             (rowptrD, colD, "D")], bits)
+
+
+# EncoderState.refresh (ocn_amd/update.py) walks the full encoder instead of the listed rows once the listed rows hold more than
+# this share of the adjacency entries the full walk reads (sum over the layers of the entries in the layer's rows, against
+# layers x nnz).  Measured on one MI355X ("Refreshing h"): the row walk was level with the full pass at a
+# share of 0.41 (collab shape, 3 layers, 1 000 edges) and slower at 0.59 (citation2 shape, 5 layers, ONE edge) and 0.60 (collab,
+# 1 layer, 100 000 edges); nothing was measured in between.  0.4 = the largest share at which it did not lose, rounded down.
+refresh_full_share = 0.4
+
+
+@_on_device
+def rows_neighbourhood(rowptrT: Tensor, colT: Tensor, rows: Tensor, bits: Tensor) -> Tensor:
+    """ocn_hip.h: ocn_rows_neighbourhood — ORs into ``bits`` (ONE bit row, int32 [ceil(n / 32)], the caller's, never cleared
+    here) the bit of every id in ``rows`` (int64) and of every column of those rows of (rowptrT, colT): the CSR whose row k
+    lists the rows that read column k, the adjacency itself where it is symmetric.  Returns ``bits``."""
+    _req(rowptrT, torch.int64, "rowptrT", 1); _req(colT, torch.int32, "colT", 1)
+    _req(rows, torch.int64, "rows", 1); _req(bits, torch.int32, "bits", 1)
+    n = rowptrT.numel() - 1
+    if n < 0 or bits.numel() != (n + 31) // 32:
+        raise ValueError(f"rows_neighbourhood: {bits.numel()} words of bits for {n} rows")
+    if n and rows.numel():
+        l = _lib.lib()
+        if not colT.numel():
+            colT = torch.zeros(1, dtype=torch.int32, device=bits.device)
+        ws = torch.empty(int(l.ocn_rows_neighbourhood_workspace_bytes(rows.numel())), dtype=torch.uint8, device=bits.device)
+        check(l.ocn_rows_neighbourhood(ptr(rowptrT), ptr(colT), n, ptr(rows), rows.numel(), ptr(bits), ptr(ws), stream_ptr()),
+              "ocn_rows_neighbourhood")
+    return bits
+
+
+@_on_device
+def bits_to_list(bits: Tensor, n_bits: int) -> Tensor:
+    """The ids of the set bits of ONE bit row (int32 [ceil(n_bits / 32)]), ascending, int64 (ocn_hip.h: ocn_bitlist_count ->
+    scan -> ocn_bitlist_fill).  One host read for the output size."""
+    _req(bits, torch.int32, "bits", 1)
+    n_bits = int(n_bits)
+    if n_bits < 0 or bits.numel() != (n_bits + 31) // 32:
+        raise ValueError(f"bits_to_list: {bits.numel()} words for {n_bits} bits")
+    if not n_bits:
+        return torch.empty(0, dtype=torch.int64, device=bits.device)
+    l = _lib.lib()
+    cnt = torch.empty(bits.numel(), dtype=torch.int32, device=bits.device)
+    check(l.ocn_bitlist_count(ptr(bits), n_bits, ptr(cnt), stream_ptr()), "ocn_bitlist_count")
+    off = scan_i32(cnt)
+    total = _total(off[-1])
+    out = torch.empty(max(total, 1), dtype=torch.int64, device=bits.device)
+    if total:
+        check(l.ocn_bitlist_fill(ptr(bits), n_bits, ptr(off), ptr(out), stream_ptr()), "ocn_bitlist_fill")
+    return out[:total]
 
 
 @_on_device
