@@ -44,7 +44,8 @@ extern "C" {
  *    ocn_bitrows_insert_workspace_bytes, ocn_bitrows_insert (edge insertion into a resident graph); ocn_csr_minus_count /
  *    _fill, ocn_bitrows_remove_workspace_bytes, ocn_bitrows_remove (edge removal from a resident graph); ocn_spmm_csr_rows,
  *    ocn_rows_neighbourhood_workspace_bytes, ocn_rows_neighbourhood, ocn_bitlist_count / _fill (refreshing the node embeddings
- *    after an edge update: only the rows that can have changed). */
+ *    after an edge update: only the rows that can have changed); ocn_cn3_flags (the (A, A³) pass of cn6 from A and the bit rows
+ *    of A², without a stored A³). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -470,6 +471,33 @@ int ocn_cn_gather3(const int64_t* rowptrA, const int32_t* colA, const int64_t* s
                    const int64_t* order, int64_t B, const int64_t* off, const uint8_t* flagsA,
                    const uint8_t* flagsB, const float* weightsA, const float* weightsB, const float* nip,
                    const float* h, int32_t H, float* xcn1, float* xcn2, float* xcn3, float* xij, void* stream);
+
+/* The (A, A³) pass of cn6 WITHOUT a stored A³.  For e = (i, j) the p-th neighbour k of i is a cn3 entry exactly when
+ * A³[j, k] != 0: when some m with A[m, k] != 0 has A²[j, m] != 0, i.e. when row k of Aᵀ shares a column with row j of A².
+ * The pass walks the neighbours of the neighbours of the source and probes bit row j of A² (one probe per membership test);
+ * its outputs are byte for byte what ocn_cn_flags leaves when called with T1 = the pattern of A·A·A and no T2 on the same
+ * src / dst / off:
+ *   flags[off[e] + p] = OCN_F_CN1 where neighbour p of src[e] is a cn3 entry, else 0 — every position of every row is written;
+ *   cnt3[e] = the number of entries; hist[k] word 0 += 1 | 1 << 42 per entry of column k (n1 and n_union, what
+ *   ocn_cn_weights_cn6 reads for its B histogram), word 1 is untouched.  hist and cnt3 must be ZERO on entry (entries add
+ *   into them with integer atomics: the result does not depend on the schedule).
+ * rowptrT / colT: the CSR of Aᵀ — row k = the m with A[m, k] != 0; pass A's own arrays for a symmetric A.
+ * bitmapP: dense bit rows of the pattern of A·A (row j at bitmapP + j * bm_stride_words, bit m = column m;
+ * bm_stride_words * 32 >= n_cols).  off: as ocn_edge_offsets / ocn_batch_prep leave it for (rowptrA, src).
+ * chunk_off: ocn_chunk_offsets(rowptrA, nds, src, order, B) — the work items: a candidate with a run of consecutive
+ * neighbours of its source, the run length adapted by nds so that an item sweeps a bounded number of elements.  nds (or NULL:
+ * runs of ocn_walk_chunk() neighbours) must be the array chunk_off was formed with; nds[i] = sum over k in N(i) of the length
+ * of row k of Aᵀ (ocn_neighbor_degree_sum for a symmetric A).  order: as for ocn_cn_flags, it changes the processing order only.
+ * status: int32[4] as for ocn_cn_flags: OCN_ST_CAP if off[B] > flags_cap (rows that do not fit are not written: nothing past
+ * the cap), OCN_ST_SCAN if off[B] or chunk_off[B] is OCN_SCAN_POISON (the batch is then treated as empty); both also ORed into
+ * the sticky word status[3].  No allocation, no global state, no host synchronisation.
+ * NULL required pointers, negative sizes, bit rows narrower than n_cols, B >= 2^21: OCN_EINVAL before any HIP call.  B == 0
+ * returns 0. */
+int ocn_cn3_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT, const int32_t* colT,
+                  const uint32_t* bitmapP, int64_t bm_stride_words, const int64_t* src, const int64_t* dst,
+                  const int64_t* order /* or NULL */, int64_t B, int64_t n_cols, const int64_t* off, uint8_t* flags,
+                  int64_t flags_cap, uint64_t* hist /* [n_cols][2] */, int32_t* cnt3, int32_t* status,
+                  const int64_t* nds /* or NULL */, const int64_t* chunk_off /* [B + 1] */, void* stream);
 
 /* Backward of the pooling with respect to h (training drop-in): for upstream
  * gradients g1, g2, g3 of xcn1, xcn2, xij ([B][H] each),

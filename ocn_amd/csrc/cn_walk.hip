@@ -56,22 +56,6 @@ __device__ __forceinline__ i64 walk_set_find(const int32_t* s_set, const int32_t
   return sorted_find(set_g, ds, key);
 }
 
-// batch slot of a work item: last slot with item_off[slot] <= item (item_off[0] = 0 <= item <
-// item_off[B]).  Called by one whole wave: 64 probes per round instead of a dependent chain of
-// log2(B) single loads (2 rounds for B = 2048, 3 for 65 536).
-__device__ __forceinline__ i64 walk_item_slot(const i64* __restrict__ item_off, i64 B, i64 item, int lane) {
-  i64 lo = 0, hi = B;                        // item_off[lo] <= item < item_off[hi]
-  while (hi - lo > 1) {
-    const i64 step = (hi - lo + OCN_WAVE - 1) / OCN_WAVE;
-    const i64 idx = lo + (i64)(lane + 1) * step;
-    const bool le = idx < hi && item_off[idx] <= item;
-    const int c = __popcll(__ballot(le));
-    lo += (i64)c * step;
-    hi = lo + step < hi ? lo + step : hi;
-  }
-  return lo;
-}
-
 constexpr int WALK_THREADS = 512;   /* threads per walk work item */
 #define WALK_WAVES (WALK_THREADS / OCN_WAVE)
 #define WALK_ROWS (WALK_WAVES * WALK_CHUNK)   /* rows a forward item can take: one 64-row chunk per wave */

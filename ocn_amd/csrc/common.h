@@ -169,6 +169,22 @@ __device__ __forceinline__ i64 walk_group(const i64* __restrict__ nds, i64 i, i6
   return cg < 1 ? 1 : (cg > chunks ? chunks : cg);
 }
 
+// batch slot of a work item: last slot with item_off[slot] <= item (item_off[0] = 0 <= item <
+// item_off[B]).  Called by one whole wave: 64 probes per round instead of a dependent chain of
+// log2(B) single loads (2 rounds for B = 2048, 3 for 65 536).  (cn_walk.hip, cn3_flags.hip: the items of ocn_chunk_offsets)
+__device__ __forceinline__ i64 walk_item_slot(const i64* __restrict__ item_off, i64 B, i64 item, int lane) {
+  i64 lo = 0, hi = B;                        // item_off[lo] <= item < item_off[hi]
+  while (hi - lo > 1) {
+    const i64 step = (hi - lo + OCN_WAVE - 1) / OCN_WAVE;
+    const i64 idx = lo + (i64)(lane + 1) * step;
+    const bool le = idx < hi && item_off[idx] <= item;
+    const int c = __popcll(__ballot(le));
+    lo += (i64)c * step;
+    hi = lo + step < hi ? lo + step : hi;
+  }
+  return lo;
+}
+
 __device__ __forceinline__ bool walk_reverse(const i64* __restrict__ nds, i64 i, i64 j, i64 di, i64 dj) {
   if (!nds || dj == 0 || di == 0) return false;
   const i64 chunks_j = (dj + WALK_REV_CHUNK - 1) / WALK_REV_CHUNK;

@@ -398,6 +398,61 @@ def _cn_flags_walk_small(rowptrA, colA, src, dst, n_cols, max_deg_a, wsd, nds):
 
 
 @_on_device
+def cn3_flags(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor, bits: Tensor, src: Tensor, dst: Tensor, n_cols: int,
+              off: Tensor, order: Optional[Tensor], max_deg_a: int, wsd=None, nds: Optional[Tensor] = None,
+              flags: Optional[Tensor] = None):
+    """The (A, A³) pass of cn6 without a stored A³ (ocn_hip.h: ocn_cn3_flags): neighbour p of ``src[e]`` is a cn3 entry when
+    its row of Aᵀ (``rowptrT`` / ``colT``; A's own arrays for a symmetric A) shares a column with bit row ``dst[e]`` of A²
+    (``bits``, int32 [n, words]).  ``off`` / ``order``: the flag offsets and the processing order of the batch's (A, A, A²)
+    pass (``cn_flags``), or ``edge_offsets`` / None.  ``nds`` (or None): Σ_{k∈N(i)} |Aᵀ row k| per source — the work items then
+    sweep a bounded number of elements (``neighbor_degree_sum`` for a symmetric A).  ``flags`` (or None): a caller's uint8
+    buffer, whose length is then the capacity; by default the capacity is the one ``cn_flags`` derives.
+    Returns (flags, hist [n_cols, 2] int64 packed, cnt3 int32 [B], status int32 [4])."""
+    dev = src.device
+    B = src.numel()
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    _req(rowptrT, torch.int64, "rowptrT", 1); _req(colT, torch.int32, "colT", 1)
+    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
+    _req(bits, torch.int32, "bits", 2)
+    n = rowptrA.numel() - 1
+    if dst.numel() != B:
+        raise ValueError("src/dst length mismatch")
+    if B > MAX_BATCH:
+        raise ValueError(f"candidate batch of {B} edges exceeds the histogram field width ({MAX_BATCH})")
+    if rowptrT.numel() != int(n_cols) + 1:
+        raise ValueError("rowptrT: the transpose has one row per column of the adjacency")
+    if bits.shape[0] != n or bits.shape[1] * 32 < n_cols:
+        raise ValueError(f"bits ({tuple(bits.shape)}) does not match the adjacency: {n} bit rows of at least {n_cols} bits")
+    if _req(off, torch.int64, "off", 1).numel() != B + 1:
+        raise ValueError("off: int64 [B + 1]")
+    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
+        raise ValueError("order: a permutation of the batch rows")
+    if nds is not None and _req(nds, torch.int64, "nds", 1).numel() != n:
+        raise ValueError("nds does not match the adjacency")
+    _mark("begin")
+    hist = buf(wsd, "hist3", (n_cols, 2), torch.int64, dev)
+    cnt3 = buf(wsd, "cnt3", B, torch.int32, dev)
+    status = buf(wsd, "status3", 4, torch.int32, dev, zero_init=True)      # ([3]: the sticky error word)
+    zero_regions([hist, cnt3, status[:3]])
+    chunk_off = buf(wsd, "chunk_off3", B + 1, torch.int64, dev)
+    cws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, dev, zero_init=True)
+    check(_lib.lib().ocn_chunk_offsets(ptr(rowptrA), ptr(nds), ptr(src), ptr(order), B, ptr(chunk_off), ptr(cws), stream_ptr()),
+          "ocn_chunk_offsets")
+    if flags is None:
+        bound = B * max(int(max_deg_a), 0)
+        cap = bound if bound <= FLAGS_NOSYNC_LIMIT else _total(off[-1])
+        flags = buf(wsd, "flags3", max(cap, 1), torch.uint8, dev)
+    else:
+        cap = _req(flags, torch.uint8, "flags", 1).numel()
+    _mark("cn3_prep")
+    check(_lib.lib().ocn_cn3_flags(ptr(rowptrA), ptr(colA), ptr(rowptrT), ptr(colT), ptr(bits), bits.shape[1], ptr(src), ptr(dst),
+                                   ptr(order), B, int(n_cols), ptr(off), ptr(flags), cap, ptr(hist), ptr(cnt3), ptr(status),
+                                   ptr(nds), ptr(chunk_off), stream_ptr()), "ocn_cn3_flags")
+    _mark("cn3_flags")
+    return flags, hist, cnt3, status
+
+
+@_on_device
 def neighbor_degree_sum(rowptr: Tensor, col: Tensor) -> Tensor:
     """nds[v] = Σ_{u∈N(v)} deg(u) (int64): the elements a sweep of v's neighbour rows touches."""
     _req(rowptr, torch.int64, "rowptr", 1); _req(col, torch.int32, "col", 1)

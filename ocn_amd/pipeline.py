@@ -55,10 +55,16 @@ def score_edges(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     ``group`` (a process group, or True for the default one): the ``PermIterator`` batches are DEALT round robin to the
     ranks — every batch stays whole on one GPU, so its batch-coupled normalisation is the single-device one and no
     histogram travels; ONE all-gather of the scores closes the split (``dist.gather_dealt``).  Every rank returns all n
-    scores, bit-equal to the single-process call."""
+    scores, bit-equal to the single-process call.
+
+    A cn6 predictor (``CNLinkPredictor3hopCNs``) takes a loop of its own (``_score_3hop``): its third handle is
+    ``adjoverlap_3hop(adj, adj2, e)``, the batches run one after the other, and ``group`` raises ValueError."""
     from .utils import adjoverlap
     if predictor.training:
         raise RuntimeError("score_edges is the eval path; call predictor.eval() first")
+    from .model import CNLinkPredictor3hopCNs
+    if isinstance(predictor, CNLinkPredictor3hopCNs):
+        return _score_3hop(predictor, h, adj, adj2, edges, batch_size, args, run_ahead, group)
     h = h.contiguous()
     outs, done = [], []
     if edges.shape[0] == 0:
@@ -95,6 +101,42 @@ def score_edges(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     else:
         scores = torch.cat(outs, dim=0)
     predictor.check_errors()       # the batches' sticky status words, read once per split (flag capacity, scan state)
+    return scores
+
+
+def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int, args, run_ahead, group) -> Tensor:
+    """``score_edges`` for the 3-hop predictor cn6, which takes a third handle and does not speak ``begin`` / ``finish``: the
+    ``PermIterator(training=False)`` batches one after the other on the current stream, each
+    ``predictor(h, adj, adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e), adjoverlap_3hop(adj, adj2, e), e, args)`` — cn3 from
+    ``adj`` and the bit rows of ``adj2``, no A³ — so the scores are exactly those of per-batch ``forward`` calls at this batch
+    size.  No side streams, no graph replay; the batches' status words are ORed on the device and read once at the end."""
+    from .utils import adjoverlap, adjoverlap_3hop
+    if group is not None:
+        raise ValueError("cn6 is scored on one GPU: score_edges deals batches over a group for the two-handle predictors only")
+    if adj2 is None:
+        raise ValueError("cn6 needs adj2 = adj @ adj: its cn2 and cn3 are read from the rows of A²")
+    h = h.contiguous()
+    if edges.shape[0] == 0:
+        return h.new_zeros(0)
+    adj.warm(walk=False)
+    adj.neighbor_degree_sum()                               # (sizes the work items of the cn3 pass)
+    if adj2.rows_on_demand():                               # (a product formed under autograd: completed first)
+        adj2.product_bit_rows()
+    outs, done, bits = [], [], None
+    with ops.prevalidated(edges[:, 0], edges[:, 1], adj.size(0), adj.size(0)):
+        for perm in PermIterator(edges.device, edges.shape[0], batch_size, training=False):
+            if len(done) >= max(run_ahead, 1):
+                done.pop(0).synchronize()
+            e = edges[perm].t().contiguous()
+            cn3 = adjoverlap_3hop(adj, adj2, e)
+            outs.append(predictor(h, adj, adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e), cn3, e, args).reshape(-1))
+            word = cn3.fused.a.status[0] | cn3.fused.b.status[0]
+            bits = word if bits is None else bits | word
+            done.append(torch.cuda.current_stream(h.device).record_event())
+    scores = torch.cat(outs, dim=0)
+    bits = int(bits.item())
+    if bits:
+        raise RuntimeError(ops.status_message(bits))
     return scores
 
 

@@ -106,11 +106,18 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     ``pipeline.score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)``; the contract is the same sentence
     with that call in it.  The candidate LIST is the one a materialised A² gives; the SCORES are not those of the pattern
     route: on the walk route cn2 carries walk counts (``utils.get_cn1_cn2``, the route of the ppa and citation2 drivers), by
-    design, so the two routes may rank a source's candidates differently."""
+    design, so the two routes may rank a source's candidates differently.
+
+    The 3-hop predictor cn6 is served with ``adj2`` given: ``score_edges`` forms its third handle from ``adj`` and the bit rows
+    of ``adj2`` (``utils.adjoverlap_3hop``), no A³ is stored.  With ``adj2=None`` it raises ValueError: the walk route has no
+    3-hop form."""
     from .pipeline import score_edges, score_edges_walk
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
+    from .model import CNLinkPredictor3hopCNs
+    if adj2 is None and isinstance(predictor, CNLinkPredictor3hopCNs):
+        raise ValueError("cn6 needs adj2 = adj @ adj: the walk route has no 3-hop form")
     ptr, edges = two_hop_candidates(adj, adj2, sources, known)
     if adj2 is None:
         scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)

@@ -21,6 +21,10 @@ can change only the rows inside the L-hop ball of the updated rows, and every ev
 time in a fixed order.  ``EncoderState.refresh`` recomputes those rows alone, layer by layer (``ocn_spmm_csr_rows`` over the
 row lists of ``ocn_rows_neighbourhood``), and ends with ``h`` bit-equal to a full pass over the new adjacency.
 
+The 3-hop predictor cn6 needs nothing more: the pair ``(adj, adj2)`` these functions return is all it reads — its cn3 pass
+(``utils.adjoverlap_3hop``, ``ocn_cn3_flags``) decides A³[j, k] from the rows of A and the bit rows of A², so no third matrix
+is kept beside them that could go stale on the first accepted link.
+
 Valued adjacencies, changed node features, training-mode refresh and more than one GPU are out of scope.
 """
 from __future__ import annotations

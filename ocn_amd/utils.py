@@ -42,6 +42,42 @@ class PermIterator:
         return ret
 
 
+def _check_hop3(adj: SparseTensor, adj2: SparseTensor, tarei: Tensor) -> None:
+    if tarei.dim() != 2 or tarei.shape[0] != 2:
+        raise ValueError("tarei must be [2, B]")
+    if adj.size(0) != adj.size(1):
+        raise ValueError("the 3-hop common neighbours need a square adjacency")
+    if tuple(adj2.sparse_sizes()) != tuple(adj.sparse_sizes()):
+        raise ValueError("adjoverlap_3hop: adj2 must be adj @ adj, of adj's size")
+
+
+def _a2_bit_rows(adj2: SparseTensor, dst: Tensor) -> Tensor:
+    """Bit rows of A² for the A³-free cn3 pass: the ones the product arrived with; of a product with rows on demand the rows
+    this batch probes (on one stream only, as ``CNState``); else built from the CSR where they fit."""
+    if adj2.rows_on_demand() and not getattr(ops, "_overlap_active", False) and adj2.size(1) > ops.small_graph_cols():
+        return adj2.product_bit_rows(dst)
+    bits = adj2.product_bit_rows()
+    if bits is None:
+        bits = adj2.bit_rows()
+    if bits is None:
+        raise ValueError("the A³-free cn6 route needs dense bit rows of A², and this adj2 has none (it exceeds "
+                         "ops.a1_bitmap_max_bytes and did not arrive with them); a materialised adj3 is still accepted")
+    return bits
+
+
+def _transposed(adj: SparseTensor, undirected: bool):
+    """(rowptr, col) of Aᵀ and Σ_{k∈N(i)} |Aᵀ row k| per source i, the probe bound that sizes the work items of the cn3
+    pass.  ``undirected``: A is symmetric — its own CSR and its cached ``neighbor_degree_sum``."""
+    if undirected:
+        return adj._rowptr, adj._col, adj.neighbor_degree_sum()
+    at = adj.t()
+    if getattr(adj, "_nds_t", None) is None:
+        deg_t = at._rowptr[1:] - at._rowptr[:-1]
+        adj._nds_t = torch.zeros(adj.size(0), dtype=torch.int64, device=deg_t.device).index_add_(
+            0, adj._row64(), deg_t[adj._col.to(torch.int64)])
+    return at._rowptr, at._col, adj._nds_t
+
+
 class CNState:
     """Device state of one candidate batch after the intersection kernel: where each batch row
     starts (``off``), one flag byte per neighbour of the source node (bit 0: cn1 entry, bit 1: cn2
@@ -71,7 +107,9 @@ class CNState:
                       if (self.rec is not None and ops.heavy_first and self.B >= ops.sort_edges_min_batch) else None)
         # a product whose rows are built on demand (a training step's A²): the rows this batch probes, and no row pointers — on
         # one stream only (a loop with several phase-A streams completes the product before it forks them: pipeline.score_edges)
-        t2_rows = (t2 is not None and not walk and t2.rows_on_demand() and not getattr(ops, "_overlap_active", False))
+        # (a small graph's pass reads the row lengths of T2 beside its bit rows: there the product is completed)
+        t2_rows = (t2 is not None and not walk and t2.rows_on_demand() and not getattr(ops, "_overlap_active", False)
+                   and self.N > ops.small_graph_cols())
         (self.order, self.off, self.flags, self.wc, self.hist, self.cnt1, self.cnt2, self.status, self.scal) = ops.cn_flags(
             adj._rowptr, adj._col, None if walk else (t1._rowptr, t1._col),
             None if (walk or t2 is None) else ((None, None) if t2_rows else
@@ -133,6 +171,32 @@ class CNState:
         st.hist = torch.stack([n1 | (n2 << ops.HIST_FIELD_BITS) | (nu << (2 * ops.HIST_FIELD_BITS)), walks], dim=1).contiguous()
         st.status = torch.zeros(4, dtype=torch.int32, device=dev)
         st.scal = torch.zeros(4, dtype=torch.int32, device=dev)
+        st._hist_live = True
+        return st
+
+    @classmethod
+    def hop3(cls, adj: SparseTensor, adj2: SparseTensor, tarei: Tensor, undirected: bool = True, off: Optional[Tensor] = None,
+             order: Optional[Tensor] = None) -> "CNState":
+        """The (A, A³) pass without a stored A³: the state ``CNState(adj, adj3, None, tarei)`` leaves for adj3 = the pattern
+        of A·A·A, from ``adj`` and the bit rows of ``adj2 = adj @ adj`` (``ops.cn3_flags``).  ``off`` / ``order``: those of
+        the batch's (A, A, A²) pass, which has then checked the edges; standing alone the state forms its own."""
+        _check_hop3(adj, adj2, tarei)
+        st = cls.__new__(cls)
+        st.adj, st.walk, st.t2, st.ws = adj, False, None, None
+        st.src = tarei[0].to(torch.int64).contiguous()
+        st.dst = tarei[1].to(torch.int64).contiguous()
+        st.B, st.N = st.src.numel(), adj.size(1)
+        st.rec = st.sched = st.wc = st.cnt2 = None
+        if off is None:
+            ops.check_edges(st.src, st.dst, adj.size(0), adj.size(0))
+            off = ops.edge_offsets(adj._rowptr, st.src)
+            order = ops.order_by_node(st.src, adj.size(0)) if st.B >= ops.sort_edges_min_batch else None
+        st.off, st.order = off, order
+        bits = _a2_bit_rows(adj2, st.dst)
+        rowptr_t, col_t, nds = _transposed(adj, undirected)
+        st.flags, st.hist, st.cnt1, st.status = ops.cn3_flags(adj._rowptr, adj._col, rowptr_t, col_t, bits, st.src, st.dst, st.N,
+                                                              off, order, adj.max_rowcount(), nds=nds)
+        st.scal = torch.zeros(4, dtype=torch.int32, device=st.src.device)
         st._hist_live = True
         return st
 
@@ -229,11 +293,14 @@ class CNState:
 
 class CNBatch:
     """Lazy ``adjoverlap(adj1, adj2, tarei)``: rows N_adj1(tarei[0][e]) ∩ N_adj2(tarei[1][e]); or one
-    half of ``get_cn1_cn2(adj, tedge)`` (``mode`` "walk1" / "walk2")."""
+    half of ``get_cn1_cn2(adj, tedge)`` (``mode`` "walk1" / "walk2"); or ``adjoverlap_3hop(adj, adj2, tarei)`` (``mode``
+    "hop3": rows N_adj(tarei[0][e]) ∩ N³(tarei[1][e]) from ``adj`` and ``adj2 = adj @ adj``)."""
 
-    def __init__(self, adj1: SparseTensor, adj2: Optional[SparseTensor], tarei: Tensor, mode: str = "pattern"):
-        self.adj1, self.adj2, self.tarei, self.mode = adj1, adj2, tarei, mode
+    def __init__(self, adj1: SparseTensor, adj2: Optional[SparseTensor], tarei: Tensor, mode: str = "pattern",
+                 undirected: bool = True):
+        self.adj1, self.adj2, self.tarei, self.mode, self.undirected = adj1, adj2, tarei, mode, undirected
         self._state: Optional[CNState] = None
+        self.fused: Optional["CNState3"] = None      # hop3: the batch state ``fuse3`` built with this handle (its status words)
 
     def sizes(self):
         return [self.tarei.shape[1], self.adj1.size(1)]
@@ -248,6 +315,8 @@ class CNBatch:
         if self._state is None:
             if self.mode == "pattern":
                 self._state = CNState(self.adj1, self.adj2, None, self.tarei)
+            elif self.mode == "hop3":
+                self._state = CNState.hop3(self.adj1, self.adj2, self.tarei, self.undirected)
             else:
                 self._state = CNState(self.adj1, None, None, self.tarei, walk=True)
         return self._state
@@ -263,11 +332,17 @@ class CNBatch:
 
 class CNState3:
     """The 3-hop predictor's batch state: two intersection passes over the same candidates — (A, A, A²) and
-    (A, A³) — sharing the row offsets (both walk the source rows of A)."""
+    (A, A³) — sharing the row offsets (both walk the source rows of A).  ``adj3=None``: the second pass runs without a
+    stored A³, from ``adj`` and the bit rows of ``adj2`` (``CNState.hop3``; ``undirected=False`` reads ``adj.t()`` for the
+    rows of Aᵀ) and leaves the same state."""
 
-    def __init__(self, adj: SparseTensor, adj2: SparseTensor, adj3: SparseTensor, tarei: Tensor):
+    def __init__(self, adj: SparseTensor, adj2: SparseTensor, adj3: Optional[SparseTensor], tarei: Tensor,
+                 undirected: bool = True):
+        if adj3 is None:
+            _check_hop3(adj, adj2, tarei)
         self.a = CNState(adj, adj, adj2, tarei)
-        self.b = CNState(adj, adj3, None, tarei)
+        self.b = (CNState(adj, adj3, None, tarei) if adj3 is not None
+                  else CNState.hop3(adj, adj2, tarei, undirected, off=self.a.off, order=self.a.order))
         self.adj, self.B, self.N = adj, self.a.B, self.a.N
 
     @property
@@ -304,15 +379,22 @@ def _same_edges(a: Tensor, b: Tensor) -> bool:
 
 
 def fuse3(cn1: "CNBatch", cn2: "CNBatch", cn3: "CNBatch", tar_ei: Tensor) -> CNState3:
-    """(cn1, cn2, cn3) = adjoverlap(adj, adj | adj2 | adj3, e) of one candidate batch."""
+    """(cn1, cn2, cn3) = adjoverlap(adj, adj | adj2 | adj3, e) of one candidate batch; cn3 may be
+    ``adjoverlap_3hop(adj, adj2, e)`` instead, built on the SAME ``adj2`` object as cn2: no A³ is needed then."""
     for c in (cn1, cn2, cn3):
-        if not isinstance(c, CNBatch) or c.mode != "pattern":
-            raise NotImplementedError("cn6 takes the handles returned by ocn_amd.utils.adjoverlap")
+        if not isinstance(c, CNBatch) or (c.mode != "pattern" and not (c is cn3 and c.mode == "hop3")):
+            raise NotImplementedError("cn6 takes the handles returned by ocn_amd.utils.adjoverlap (cn3: or adjoverlap_3hop)")
     if not (cn1.adj1 is cn2.adj1 is cn3.adj1) or cn1.adj2 is not cn1.adj1:
         raise NotImplementedError("cn1/cn2/cn3 must come from adjoverlap(adj, adj|adj2|adj3, e) of one adjacency")
     if ops.validate_indices and not (_same_edges(cn1.tarei, cn2.tarei) and _same_edges(cn1.tarei, cn3.tarei)
                                      and _same_edges(cn1.tarei, tar_ei)):
         raise NotImplementedError("cn1, cn2, cn3 and tar_ei must be built from the same candidate edges")
+    if cn3.mode == "hop3":
+        if cn3.adj2 is not cn2.adj2:
+            raise NotImplementedError("adjoverlap_3hop(adj, adj2, e) must be built on the adj2 object of cn2 = adjoverlap(adj, adj2, e)")
+        st = CNState3(cn1.adj1, cn2.adj2, None, cn1.tarei, undirected=cn3.undirected)
+        cn3.fused = st
+        return st
     return CNState3(cn1.adj1, cn2.adj2, cn3.adj2, cn1.tarei)
 
 
@@ -402,6 +484,19 @@ def adjoverlap(adj1: SparseTensor, adj2: SparseTensor, tarei: Tensor, filled1: b
     if calresadj or cnsampledeg > 0 or ressampledeg > 0:
         raise NotImplementedError("calresadj / neighbour sampling are outside the cn5/cn7 path")
     return CNBatch(adj1, adj2, tarei)
+
+
+def adjoverlap_3hop(adj: SparseTensor, adj2: SparseTensor, tarei: Tensor, undirected: bool = True) -> CNBatch:
+    """The cn3 argument of cn6 without a stored A³: rows N(i) ∩ N³(j) for (i, j) = tarei[:, e], N³ the pattern of A·A·A —
+    what ``adjoverlap(adj, adj3, tarei)`` yields for a materialised adj3 — from ``adj`` and ``adj2 = adj @ adj``.  Neighbour k of
+    i is an entry exactly when row k of Aᵀ shares a column with row j of A² (``ops.cn3_flags``), so ``adj2`` must have dense
+    bit rows: the ones a product arrives with, or built from its CSR where they fit ``ops.a1_bitmap_max_bytes``.
+    ``undirected=True`` assumes a symmetric ``adj`` (as ``update.insert_edges`` does) and reads A's own CSR for the rows of
+    Aᵀ; ``undirected=False`` reads ``adj.t()``.  The handle goes to the cn6 predictor beside
+    ``adjoverlap(adj, adj, e)`` and ``adjoverlap(adj, adj2, e)`` of the same ``adj2`` object; standing alone it answers
+    ``.counts()`` and ``.materialize()``."""
+    _check_hop3(adj, adj2, tarei)
+    return CNBatch(adj, adj2, tarei, "hop3", undirected=bool(undirected))
 
 
 def get_cn1_cn2(adj: SparseTensor, tedge: Tensor) -> Tuple[CNBatch, CNBatch]:
