@@ -16,7 +16,9 @@ import torch
 from torch import Tensor
 
 from . import ops
+from .pipeline import RunAhead
 from .sparse import SparseTensor
+from .utils import PermIterator, _endpoints
 
 KINDS = ("cn", "aa", "ra", "jaccard", "pa", "cn2", "aa2", "ra2")
 TWO_HOP = ("cn2", "aa2", "ra2")
@@ -56,23 +58,18 @@ def node_table(adj: SparseTensor, node_weight: Optional[Tensor] = None) -> Tenso
 
 def _sums(adj: SparseTensor, adj2: Optional[SparseTensor], edges: Tensor, w: Tensor, wsd: Optional[dict]):
     """One ``ops.cn_node_sums`` launch (behind the order launch of a large batch) for ``edges`` [2, B].  T1 = ``adj`` and
-    T2 = ``adj2`` go as bit rows where the adjacency has them, else as CSR — the choices of cn8's fused state
-    (``utils.CN8State.pool``); T1's row pointers always go along: the kernel reads the target's degree from them."""
-    if edges.dim() != 2 or edges.shape[0] != 2:
-        raise ValueError("edges must be [2, B]")
-    src = edges[0].to(torch.int64).contiguous()
-    dst = edges[1].to(torch.int64).contiguous()
+    T2 = ``adj2`` go as bit rows where the adjacency has them (``SparseTensor.bit_rows`` / ``.probed_bit_rows``), else as
+    CSR; T1's row pointers always go along: the kernel reads the target's degree from them."""
+    src, dst = _endpoints(edges, "edges")
     bm2 = csr2 = None
     if adj2 is not None:
         if adj2.sparse_sizes() != adj.sparse_sizes():
             raise ValueError("adj and adj2 differ in size")
-        lazy = adj2.rows_on_demand() and not getattr(ops, "_overlap_active", False)
-        bm2 = adj2.product_bit_rows(dst) if lazy else adj2.product_bit_rows()
+        bm2 = adj2.probed_bit_rows(dst)
         csr2 = None if bm2 is not None else (adj2._rowptr, adj2._col)
     bm1 = adj.bit_rows()
-    order = ops.order_by_node(src, adj.size(0), wsd) if src.numel() >= ops.sort_edges_min_batch else None
     return ops.cn_node_sums(adj._rowptr, adj._col, (adj._rowptr, adj._col), csr2, src, dst, w, t1_bitmap=bm1, t2_bitmap=bm2,
-                            order=order, wsd=wsd, n_cols=adj.size(1))
+                            order=ops.batch_order(src, adj.size(0), wsd), wsd=wsd, n_cols=adj.size(1))
 
 
 def _check_kinds(kinds: Sequence[str], adj2) -> Tuple[str, ...]:
@@ -137,7 +134,6 @@ def score_edges_heuristic(adj: SparseTensor, adj2: Optional[SparseTensor], edges
     ``evaluate.Evaluator.eval`` takes as it is.  The split is bounds-checked once, the caches (bit rows, node table) are
     built before the loop, and the host stays at most ``run_ahead`` batches ahead of the GPU.  One stream; dealing the
     batches over several GPUs is not built for this loop."""
-    from .utils import PermIterator
     (kind,) = _check_kinds((kind,), adj2)
     if edges.dim() != 2 or edges.shape[1] != 2:
         raise ValueError("edges must be [n, 2]")
@@ -146,14 +142,13 @@ def score_edges_heuristic(adj: SparseTensor, adj2: Optional[SparseTensor], edges
     need2 = kind in TWO_HOP
     adj.warm(walk=False)
     node_table(adj)
-    if need2 and adj2.rows_on_demand():
-        adj2.product_bit_rows()
+    if need2:
+        adj2.complete()
     wsd: dict = {}
-    outs, done = [], []
+    outs, window = [], RunAhead(run_ahead, edges.device)
     with ops.prevalidated(edges[:, 0], edges[:, 1], adj.size(0), adj.size(0)):
         for perm in PermIterator(edges.device, edges.shape[0], batch_size, training=False):
-            if len(done) >= max(run_ahead, 1):
-                done.pop(0).synchronize()
+            window.wait()
             outs.append(link_heuristics(adj, adj2 if need2 else None, edges[perm].t(), (kind,), wsd=wsd)[:, 0])
-            done.append(torch.cuda.current_stream(edges.device).record_event())
+            window.mark()
     return torch.cat(outs, dim=0)

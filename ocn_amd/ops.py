@@ -133,8 +133,9 @@ def status_message(bits: int) -> str:
                                     (ST_SCAN, "a scan workspace was not zero on entry: the batch's offsets are void")) if bits & b)
 
 
-def _ws(n: int, device) -> Tensor:
-    return torch.zeros(int(_lib.lib().ocn_scan_workspace_bytes(n)) // 8 + 1, dtype=torch.int64, device=device)
+def _ws(n: int, device, wsd=None) -> Tensor:
+    """The zeroed workspace of a scan over ``n`` items (ocn_hip.h, ocn_scan_workspace_bytes: the library hands it back zero)."""
+    return buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(n)) // 8 + 1, torch.int64, device, zero_init=True)
 
 
 def buf(ws, name: str, shape, dtype, device, zero: bool = False, zero_init: bool = False) -> Tensor:
@@ -176,7 +177,7 @@ def edge_offsets(rowptr: Tensor, src: Tensor, wsd=None) -> Tensor:
     _req(src, torch.int64, "src", 1)
     B = src.numel()
     off = buf(wsd, "off", B + 1, torch.int64, src.device)
-    ws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, src.device, zero_init=True)
+    ws = _ws(B, src.device, wsd)
     check(_lib.lib().ocn_edge_offsets(ptr(rowptr), ptr(src), B, ptr(off), ptr(ws), stream_ptr()),
           "ocn_edge_offsets")
     return off
@@ -246,6 +247,80 @@ def hist_counts(hist: Tensor) -> Tensor:
     return torch.stack([p & m, (p >> HIST_FIELD_BITS) & m, (p >> (2 * HIST_FIELD_BITS)) & m, hist[:, 1]], dim=1)
 
 
+def _batch_ids(src: Tensor, dst: Tensor, hist: bool = False) -> int:
+    """B of a batch's int64 id vectors (the intersection family's operand checks start here); ``hist``: the packed histogram bounds B."""
+    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
+    B = src.numel()
+    if dst.numel() != B:
+        raise ValueError("src/dst length mismatch")
+    if hist and B > MAX_BATCH:
+        raise ValueError(f"candidate batch of {B} edges exceeds the histogram field width ({MAX_BATCH})")
+    return B
+
+
+def _t_tail(rp, col, bm: Optional[Tensor], nm: str, n_cols: int, like: Optional[int]):
+    """What both operand forms end with: the bit rows fit the matrix and the columns, and the row count is that of the pass's
+    other matrix (``like``; ``dst`` indexes both).  Returns (rowptr, col, rows) as they go to the library."""
+    if bm is not None:
+        _req(bm, torch.int32, nm.lower() + "_bitmap", 2)
+        if (rp is not None and bm.shape[0] != rp.numel() - 1) or bm.shape[1] * 32 < n_cols:
+            raise ValueError(f"{nm.lower()}_bitmap does not match the {nm} adjacency")
+    rows = rp.numel() - 1 if rp is not None else bm.shape[0]
+    if like is not None and rows != like:
+        raise ValueError(f"T1 has {like} rows, T2 {rows}")
+    return rp, col, rows
+
+
+def _t_pair_or_bits(t, bm: Optional[Tensor], nm: str, n_cols: int, like: Optional[int] = None, optional: bool = False):
+    """A matrix of ocn_cn8_pool / ocn_cn_node_sums: ``t`` = its whole (rowptr, col) pair — half a pair counts as none — and / or
+    its bit rows ``bm``; with ``optional`` it may be left out altogether (all None)."""
+    rp, col = (None, None) if t is None else t
+    if rp is None or col is None:
+        if bm is None:
+            if optional:
+                return None, None, None
+            raise ValueError(f"{nm}: needs its CSR arrays or its bit rows")
+        rp = col = None
+    else:
+        _req(rp, torch.int64, "rowptr" + nm, 1); _req(col, torch.int32, "col" + nm, 1)
+    return _t_tail(rp, col, bm, nm, n_cols, like)
+
+
+def _t_of_flag_pass(t, bm, nm: str, n_cols: int, like=None, rowptr_optional: bool = False, col_deferred: bool = False):
+    """A matrix of ocn_cn_flags: both CSR arrays, except that beside bit rows the row pointers may be absent with
+    ``rowptr_optional`` and the column ids with ``col_deferred``."""
+    rp, col = t
+    if rp is not None or bm is None or not rowptr_optional:
+        _req(rp, torch.int64, "rowptr" + nm, 1)
+    if col is not None or bm is None or not col_deferred:
+        _req(col, torch.int32, "col" + nm, 1)
+    return _t_tail(rp, col, bm, nm, n_cols, like)
+
+
+def _order_arg(order: Optional[Tensor], B: int) -> None:
+    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
+        raise ValueError("order: one entry per candidate")
+
+
+def _nds_arg(nds: Optional[Tensor], n: int) -> Optional[Tensor]:
+    if nds is not None and _req(nds, torch.int64, "nds", 1).numel() != n:
+        raise ValueError("nds does not match the adjacency")
+    return nds
+
+
+def _flag_capacity(B: int, max_deg_a: int, off: Tensor) -> int:
+    """Entries of a batch's flag buffer: B * (longest row) while over-allocating beats a host sync, else the total read from ``off``."""
+    bound = B * max(int(max_deg_a), 0)
+    return bound if bound <= FLAGS_NOSYNC_LIMIT else _total(off[-1])
+
+
+def _cn_operands(rowptrA, colA, t1, t2, bm1, bm2, src, dst, order, B: int, n_cols: int):
+    """The leading arguments of ocn_cn_flags[_rec], ocn_cn8_pool and ocn_cn_node_sums (``t1`` / ``t2``: the checked (rowptr, col))."""
+    return (ptr(rowptrA), ptr(colA), ptr(t1[0]), ptr(t1[1]), ptr(t2[0]), ptr(t2[1]),
+            ptr(bm1), bm1.shape[1] if bm1 is not None else 0, ptr(bm2), bm2.shape[1] if bm2 is not None else 0,
+            ptr(src), ptr(dst), ptr(order), B, n_cols)
+
+
 @_on_device
 def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
              t2: Optional[Tuple[Tensor, Tensor]], src: Tensor, dst: Tensor, n_cols: int, max_deg_a: int,
@@ -259,20 +334,16 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     Returns (order|None, off, flags, wc|None, hist[N,2] int64 packed, cnt1, cnt2|None, status, scal) — ``scal``
     is the zeroed int32[4] statistics scratch the weights stage of the same batch uses."""
     dev = src.device
-    B = src.numel()
     _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    has_t2 = not walk and t2 is not None
     if not walk:
-        _req(t1[0], torch.int64, "rowptrT1", 1); _req(t1[1], torch.int32, "colT1", 1)
-        if t2 is not None:
-            if t2[0] is not None or t2_bitmap is None or n_cols <= small_graph_cols():      # (a product with rows on demand: bit rows only)
-                _req(t2[0], torch.int64, "rowptrT2", 1)
-            if t2[1] is not None or t2_bitmap is None:           # (with bit rows the kernel never reads T2's column ids: they may be deferred)
-                _req(t2[1], torch.int32, "colT2", 1)
-    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
-    if dst.numel() != B:
-        raise ValueError("src/dst length mismatch")
-    if B > MAX_BATCH:
-        raise ValueError(f"candidate batch of {B} edges exceeds the histogram field width ({MAX_BATCH})")
+        *csr1, rows = _t_of_flag_pass(t1, t1_bitmap, "T1", n_cols)
+        if t2 is None and t2_bitmap is not None:
+            raise ValueError("t2_bitmap does not match the T2 adjacency")
+        # (T2's row pointers: a product with rows on demand has none, and past the small-graph histogram the kernel reads none)
+        *csr2, _ = (None, None, None) if not has_t2 else _t_of_flag_pass(
+            t2, t2_bitmap, "T2", n_cols, like=rows, col_deferred=True, rowptr_optional=t2[0] is None and n_cols > small_graph_cols())
+    B = _batch_ids(src, dst, hist=True)
     _mark("begin")
     if walk and 0 < B <= int(_lib.lib().ocn_walk_prep_max_batch()) and walk_share_min > 0:
         return _cn_flags_walk_small(rowptrA, colA, src, dst, n_cols, max_deg_a, wsd, nds)
@@ -284,10 +355,10 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     ows = (buf(wsd, "order_ws", int(_lib.lib().ocn_order_workspace_bytes(n_src)) // 8 + 1, torch.int64, dev, zero_init=True)
            if want_order else None)
     off = buf(wsd, "off", B + 1, torch.int64, dev)
-    sws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, dev, zero_init=True)
+    sws = _ws(B, dev, wsd)
     hist = buf(wsd, "hist", (n_cols, 2), torch.int64, dev)
     cnt1 = buf(wsd, "cnt1", B, torch.int32, dev)
-    cnt2 = buf(wsd, "cnt2", B, torch.int32, dev) if (walk or t2 is not None) else None
+    cnt2 = buf(wsd, "cnt2", B, torch.int32, dev) if (walk or has_t2) else None
     status = buf(wsd, "status", 4, torch.int32, dev, zero_init=True)     # [0] error bits of this batch; [1], [2] walk-route work tickets; [3] sticky error bits
     scal = buf(wsd, "scal", 4, torch.int32, dev)         # the column statistics word of the weights stage
     # the flag offsets, the counting phase of the order and the batch's resets: ONE launch (ocn_batch_prep)
@@ -309,20 +380,14 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     elif want_order:
         check(_lib.lib().ocn_order_by_node_finish(ptr(src), B, n_src, ptr(order), ptr(ows), stream_ptr()),
               "ocn_order_by_node_finish")
-    bound = B * max(int(max_deg_a), 0)
-    cap = bound if bound <= FLAGS_NOSYNC_LIMIT else _total(off[-1])
+    cap = _flag_capacity(B, max_deg_a, off)
     flags = buf(wsd, "flags", max(cap, 1), torch.uint8, dev)
     wc = buf(wsd, "wc", max(cap, 1), torch.int32, dev) if walk else None
     chunk_off = rev_off = None
     if walk:
-        if nds is not None and walk_two_sided:
-            _req(nds, torch.int64, "nds", 1)
-            if nds.numel() != rowptrA.numel() - 1:
-                raise ValueError("nds does not match the adjacency")
-        else:
-            nds = None
+        nds = _nds_arg(nds if walk_two_sided else None, n_src)
         chunk_off = buf(wsd, "chunk_off", B + 1, torch.int64, dev)
-        cws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, dev, zero_init=True)
+        cws = _ws(B, dev, wsd)
         check(_lib.lib().ocn_chunk_offsets(ptr(rowptrA), ptr(nds), ptr(src), ptr(order), B, ptr(chunk_off), ptr(cws),
                                            stream_ptr()), "ocn_chunk_offsets")
         if nds is not None:
@@ -336,20 +401,9 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
                                            ptr(wc), cap, ptr(hist), ptr(cnt1), ptr(cnt2), ptr(status),
                                            stream_ptr()), "ocn_cn_walk_flags")
     else:
-        if t2_bitmap is not None:
-            _req(t2_bitmap, torch.int32, "t2_bitmap", 2)
-            if t2 is None or (t2[0] is not None and t2_bitmap.shape[0] != t2[0].numel() - 1) or t2_bitmap.shape[1] * 32 < n_cols:
-                raise ValueError("t2_bitmap does not match the T2 adjacency")
-        if t1_bitmap is not None:
-            _req(t1_bitmap, torch.int32, "t1_bitmap", 2)
-            if t1_bitmap.shape[0] != t1[0].numel() - 1 or t1_bitmap.shape[1] * 32 < n_cols:
-                raise ValueError("t1_bitmap does not match the T1 adjacency")
-        check((_lib.lib().ocn_cn_flags_rec if rec_in else _lib.lib().ocn_cn_flags)(ptr(rowptrA), ptr(colA), ptr(t1[0]), ptr(t1[1]),
-                                      ptr(t2[0] if t2 else None), ptr(t2[1] if t2 else None),
-                                      ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
-                                      ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
-                                      ptr(src), ptr(dst), ptr(order), B, n_cols, ptr(off), ptr(flags), cap, ptr(hist),
-                                      ptr(cnt1), ptr(cnt2), ptr(status), ptr(rec), ptr(sched), stream_ptr()), "ocn_cn_flags")
+        check((_lib.lib().ocn_cn_flags_rec if rec_in else _lib.lib().ocn_cn_flags)(
+            *_cn_operands(rowptrA, colA, csr1, csr2, t1_bitmap, t2_bitmap, src, dst, order, B, n_cols), ptr(off), ptr(flags), cap,
+            ptr(hist), ptr(cnt1), ptr(cnt2), ptr(status), ptr(rec), ptr(sched), stream_ptr()), "ocn_cn_flags")
     _mark("cn_flags")
     return order, off, flags, wc, hist, cnt1, cnt2, status, scal
 
@@ -359,12 +413,7 @@ def _cn_flags_walk_small(rowptrA, colA, src, dst, n_cols, max_deg_a, wsd, nds):
     candidates with a source of their own, the shared sweep for candidates that share one (ocn_cn_walk_group)."""
     dev, B = src.device, src.numel()
     l = _lib.lib()
-    if nds is not None and walk_two_sided:
-        _req(nds, torch.int64, "nds", 1)
-        if nds.numel() != rowptrA.numel() - 1:
-            raise ValueError("nds does not match the adjacency")
-    else:
-        nds = None
+    nds = _nds_arg(nds if walk_two_sided else None, rowptrA.numel() - 1)
     order = buf(wsd, "order", B, torch.int64, dev)
     off = buf(wsd, "off", B + 1, torch.int64, dev)
     chunk_off = buf(wsd, "chunk_off", B + 1, torch.int64, dev)
@@ -382,8 +431,7 @@ def _cn_flags_walk_small(rowptrA, colA, src, dst, n_cols, max_deg_a, wsd, nds):
                           ptr(chunk_off), ptr(rev_off), ptr(g_head), ptr(g_item_off), ptr(g_active), ptr(meta), ptr(cnt1),
                           ptr(cnt2), ptr(status), ptr(scal), stream_ptr()), "ocn_walk_prep")
     zero_regions([hist])
-    bound = B * max(int(max_deg_a), 0)
-    cap = bound if bound <= FLAGS_NOSYNC_LIMIT else _total(off[-1])
+    cap = _flag_capacity(B, max_deg_a, off)
     flags = buf(wsd, "flags", max(cap, 1), torch.uint8, dev)
     wc = buf(wsd, "wc", max(cap, 1), torch.int32, dev)
     _mark("cn_prep")
@@ -409,38 +457,30 @@ def cn3_flags(rowptrA: Tensor, colA: Tensor, rowptrT: Tensor, colT: Tensor, bits
     buffer, whose length is then the capacity; by default the capacity is the one ``cn_flags`` derives.
     Returns (flags, hist [n_cols, 2] int64 packed, cnt3 int32 [B], status int32 [4])."""
     dev = src.device
-    B = src.numel()
     _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
     _req(rowptrT, torch.int64, "rowptrT", 1); _req(colT, torch.int32, "colT", 1)
-    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
+    B = _batch_ids(src, dst, hist=True)
     _req(bits, torch.int32, "bits", 2)
     n = rowptrA.numel() - 1
-    if dst.numel() != B:
-        raise ValueError("src/dst length mismatch")
-    if B > MAX_BATCH:
-        raise ValueError(f"candidate batch of {B} edges exceeds the histogram field width ({MAX_BATCH})")
     if rowptrT.numel() != int(n_cols) + 1:
         raise ValueError("rowptrT: the transpose has one row per column of the adjacency")
     if bits.shape[0] != n or bits.shape[1] * 32 < n_cols:
         raise ValueError(f"bits ({tuple(bits.shape)}) does not match the adjacency: {n} bit rows of at least {n_cols} bits")
     if _req(off, torch.int64, "off", 1).numel() != B + 1:
         raise ValueError("off: int64 [B + 1]")
-    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
-        raise ValueError("order: a permutation of the batch rows")
-    if nds is not None and _req(nds, torch.int64, "nds", 1).numel() != n:
-        raise ValueError("nds does not match the adjacency")
+    _order_arg(order, B)
+    _nds_arg(nds, n)
     _mark("begin")
     hist = buf(wsd, "hist3", (n_cols, 2), torch.int64, dev)
     cnt3 = buf(wsd, "cnt3", B, torch.int32, dev)
     status = buf(wsd, "status3", 4, torch.int32, dev, zero_init=True)      # ([3]: the sticky error word)
     zero_regions([hist, cnt3, status[:3]])
     chunk_off = buf(wsd, "chunk_off3", B + 1, torch.int64, dev)
-    cws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, dev, zero_init=True)
+    cws = _ws(B, dev, wsd)
     check(_lib.lib().ocn_chunk_offsets(ptr(rowptrA), ptr(nds), ptr(src), ptr(order), B, ptr(chunk_off), ptr(cws), stream_ptr()),
           "ocn_chunk_offsets")
     if flags is None:
-        bound = B * max(int(max_deg_a), 0)
-        cap = bound if bound <= FLAGS_NOSYNC_LIMIT else _total(off[-1])
+        cap = _flag_capacity(B, max_deg_a, off)
         flags = buf(wsd, "flags3", max(cap, 1), torch.uint8, dev)
     else:
         cap = _req(flags, torch.uint8, "flags", 1).numel()
@@ -600,6 +640,11 @@ def order_by_node(node: Tensor, n_nodes: int, wsd=None) -> Tensor:
     return order
 
 
+def batch_order(src: Tensor, n_nodes: int, wsd=None) -> Optional[Tensor]:
+    """Outside ``cn_flags`` (which forms its own by this rule): by source from ``sort_edges_min_batch`` candidates on, else None."""
+    return order_by_node(src, n_nodes, wsd) if src.numel() >= sort_edges_min_batch else None
+
+
 # cn8 in eval on adjoverlap handles: ocn_cn8_pool when on, else flags -> unit weights -> the pooling of cn5 / cn7.  OFF by default:
 # the one pass is built and tested bit-equal, but it gives up the chain's longest-first schedule and class-major head rows, and the
 # default goes to it only on a measurement that shows its range below the chain's (DESIGN.md section 4, cn8; tools/cn8bench.py).
@@ -617,45 +662,24 @@ def cn8_pool(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor],
     ``h``, which it must equal — every column id indexes a row of h).  T1 and T2 must have the same number of rows, whichever
     form they come in: ``dst`` is bounds-checked against it.  Returns (xcn1, xcn2, xij [B, H], cnt1, cnt2 int32 [B])."""
     _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
-    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
-    _req(h, torch.float32, "h", 2)
-    B, (N, H) = src.numel(), h.shape
-    if dst.numel() != B:
-        raise ValueError("src/dst length mismatch")
+    B = _batch_ids(src, dst)
+    N, H = _req(h, torch.float32, "h", 2).shape
     if H not in LN_WIDTHS:
         raise NotImplementedError(f"cn8 pooling supports hidden widths {LN_WIDTHS}, got {H}")
     if n_cols is not None and int(n_cols) != N:
         raise ValueError(f"h has {N} rows, the adjacency {int(n_cols)} columns")
-    csr, n_rows = [], []
-    for t, bm, nm in ((t1, t1_bitmap, "T1"), (t2, t2_bitmap, "T2")):
-        rp, col = (None, None) if t is None else t
-        if rp is None or col is None:
-            if bm is None:
-                raise ValueError(f"{nm}: needs its CSR arrays or its bit rows")
-            rp = col = None
-        else:
-            _req(rp, torch.int64, "rowptr" + nm, 1); _req(col, torch.int32, "col" + nm, 1)
-        if bm is not None:
-            _req(bm, torch.int32, nm.lower() + "_bitmap", 2)
-            if (rp is not None and bm.shape[0] != rp.numel() - 1) or bm.shape[1] * 32 < N:
-                raise ValueError(f"{nm.lower()}_bitmap does not match the {nm} adjacency")
-        csr.append((rp, col))
-        n_rows.append(rp.numel() - 1 if rp is not None else bm.shape[0])
-    if n_rows[0] != n_rows[1]:                     # (the kernel indexes both with dst: one bound must hold for both)
-        raise ValueError(f"T1 has {n_rows[0]} rows, T2 {n_rows[1]}")
-    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
-        raise ValueError("order: one entry per candidate")
-    check_edges(src, dst, rowptrA.numel() - 1, n_rows[0])
+    *csr1, rows = _t_pair_or_bits(t1, t1_bitmap, "T1", N)
+    *csr2, _ = _t_pair_or_bits(t2, t2_bitmap, "T2", N, like=rows)
+    _order_arg(order, B)
+    check_edges(src, dst, rowptrA.numel() - 1, rows)
     out = buf(wsd, "pooled", (3, B, H), torch.float32, h.device)
     cnt = buf(wsd, "cn8_cnt", (2, B), torch.int32, h.device)
     if B == 0:
         return out[0], out[1], out[2], cnt[0], cnt[1]
     _mark("cn_prep")
-    check(_lib.lib().ocn_cn8_pool(ptr(rowptrA), ptr(colA), ptr(csr[0][0]), ptr(csr[0][1]), ptr(csr[1][0]), ptr(csr[1][1]),
-                                  ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
-                                  ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
-                                  ptr(src), ptr(dst), ptr(order), B, N, ptr(h), H, ptr(out[0]), ptr(out[1]), ptr(out[2]),
-                                  ptr(cnt[0]), ptr(cnt[1]), stream_ptr()), "ocn_cn8_pool")
+    check(_lib.lib().ocn_cn8_pool(*_cn_operands(rowptrA, colA, csr1, csr2, t1_bitmap, t2_bitmap, src, dst, order, B, N),
+                                  ptr(h), H, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(cnt[0]), ptr(cnt[1]), stream_ptr()),
+          "ocn_cn8_pool")
     _mark("cn8_pool")
     return out[0], out[1], out[2], cnt[0], cnt[1]
 
@@ -671,45 +695,24 @@ def cn_node_sums(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tens
     float32 [N, 4], N = the column count of A, T1 and T2.  Returns (sum1, sum2 float32 [B, 4], cnt1, cnt2 int32 [B],
     deg float32 [B, 2] = {row length of src in A, of dst in T1}, or None where T1 has no CSR form)."""
     _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
-    _req(src, torch.int64, "src", 1); _req(dst, torch.int64, "dst", 1)
-    _req(w, torch.float32, "w", 2)
-    B, N = src.numel(), w.shape[0]
-    if dst.numel() != B:
-        raise ValueError("src/dst length mismatch")
+    B = _batch_ids(src, dst)
+    N = _req(w, torch.float32, "w", 2).shape[0]
     if w.shape[1] != 4:
         raise ValueError(f"w must be [N, 4], got {tuple(w.shape)}")
     if n_cols is not None and int(n_cols) != N:
         raise ValueError(f"w has {N} rows, the adjacency {int(n_cols)} columns")
-    csr, n_rows = [], []
-    for t, bm, nm in ((t1, t1_bitmap, "T1"), (t2, t2_bitmap, "T2")):
-        rp, col = (None, None) if t is None else t
-        if rp is None or col is None:
-            if bm is None and nm == "T1":
-                raise ValueError("T1: needs its CSR arrays or its bit rows")
-            rp = col = None
-        else:
-            _req(rp, torch.int64, "rowptr" + nm, 1); _req(col, torch.int32, "col" + nm, 1)
-        if bm is not None:
-            _req(bm, torch.int32, nm.lower() + "_bitmap", 2)
-            if (rp is not None and bm.shape[0] != rp.numel() - 1) or bm.shape[1] * 32 < N:
-                raise ValueError(f"{nm.lower()}_bitmap does not match the {nm} adjacency")
-        csr.append((rp, col))
-        n_rows.append(rp.numel() - 1 if rp is not None else (bm.shape[0] if bm is not None else None))
-    if n_rows[1] is not None and n_rows[0] != n_rows[1]:       # (the kernel indexes both with dst: one bound must hold for both)
-        raise ValueError(f"T1 has {n_rows[0]} rows, T2 {n_rows[1]}")
-    if order is not None and _req(order, torch.int64, "order", 1).numel() != B:
-        raise ValueError("order: one entry per candidate")
-    check_edges(src, dst, rowptrA.numel() - 1, n_rows[0])
+    *csr1, rows = _t_pair_or_bits(t1, t1_bitmap, "T1", N)
+    *csr2, _ = _t_pair_or_bits(t2, t2_bitmap, "T2", N, like=rows, optional=True)
+    _order_arg(order, B)
+    check_edges(src, dst, rowptrA.numel() - 1, rows)
     sums = buf(wsd, "heur_sums", (2, B, 4), torch.float32, w.device)
     cnt = buf(wsd, "heur_cnt", (2, B), torch.int32, w.device)
-    deg = buf(wsd, "heur_deg", (B, 2), torch.float32, w.device) if csr[0][0] is not None else None
+    deg = buf(wsd, "heur_deg", (B, 2), torch.float32, w.device) if csr1[0] is not None else None
     if B == 0:
         return sums[0], sums[1], cnt[0], cnt[1], deg
-    check(_lib.lib().ocn_cn_node_sums(ptr(rowptrA), ptr(colA), ptr(csr[0][0]), ptr(csr[0][1]), ptr(csr[1][0]), ptr(csr[1][1]),
-                                      ptr(t1_bitmap), t1_bitmap.shape[1] if t1_bitmap is not None else 0,
-                                      ptr(t2_bitmap), t2_bitmap.shape[1] if t2_bitmap is not None else 0,
-                                      ptr(src), ptr(dst), ptr(order), B, N, ptr(w), ptr(sums[0]), ptr(sums[1]),
-                                      ptr(cnt[0]), ptr(cnt[1]), ptr(deg), stream_ptr()), "ocn_cn_node_sums")
+    check(_lib.lib().ocn_cn_node_sums(*_cn_operands(rowptrA, colA, csr1, csr2, t1_bitmap, t2_bitmap, src, dst, order, B, N),
+                                      ptr(w), ptr(sums[0]), ptr(sums[1]), ptr(cnt[0]), ptr(cnt[1]), ptr(deg), stream_ptr()),
+          "ocn_cn_node_sums")
     _mark("cn_node_sums")
     return sums[0], sums[1], cnt[0], cnt[1], deg
 
@@ -961,7 +964,7 @@ def class_order(cnt1: Tensor, cnt2: Optional[Tensor], order: Optional[Tensor], w
     inv = buf(wsd, "cls_inv", B, torch.int64, dev)
     ranges = buf(wsd, "cls_ranges", (CLASS_RANGES, 2), torch.int64, dev)
     prefix = buf(wsd, "cls_prefix", B + 1, torch.int64, dev)
-    ws = buf(wsd, "scan_ws", int(_lib.lib().ocn_scan_workspace_bytes(B)) // 8 + 1, torch.int64, dev, zero_init=True)
+    ws = _ws(B, dev, wsd)
     check(_lib.lib().ocn_class_order(ptr(cnt1), ptr(cnt2), ptr(order), B, ptr(order2), ptr(inv), ptr(ranges),
                                      ptr(prefix), ptr(ws), stream_ptr()), "ocn_class_order")
     _mark("cn_class")

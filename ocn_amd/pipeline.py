@@ -44,13 +44,68 @@ def _dealt(perms, group):
     return deal_batches(len(perms), world, dist.get_rank(group if group is not True else None)), world
 
 
+class RunAhead:
+    """The flow control of a scoring loop: the host stays at most ``n`` batches ahead of the GPU — an unbounded backlog makes
+    the HIP runtime block the host until the queue has drained completely.  ``wait()`` in front of a batch,
+    ``mark()`` behind it (an event on the current stream of ``device``); ``n`` = None: no flow control, both do nothing."""
+
+    def __init__(self, n: Optional[int], device):
+        self.n, self.device, self.done = n, device, []
+
+    def wait(self, it=None) -> None:
+        if self.n is not None and len(self.done) >= max(self.n, 1):
+            self.done.pop(0).synchronize()
+
+    def mark(self) -> None:
+        if self.n is not None:
+            self.done.append(torch.cuda.current_stream(self.device).record_event())
+
+
+def _score_batches(predictor, h: Tensor, adj, src_all: Tensor, dst_all: Tensor, batch_edges, make_handles, warm, batch_size: int,
+                   args, run_ahead, group) -> Tensor:
+    """The loop behind ``score_edges``, ``score_edges_walk`` and both halves of ``score_mrr_split`` over the candidates
+    (src_all[i], dst_all[i]) in ``PermIterator(.., training=False)`` batches.  ``batch_edges(perm)`` -> the batch's ids
+    [2, b] (any strides), ``make_handles(e)`` -> its (cn1, cn2) handles, ``warm()`` builds what the batches share;
+    ``run_ahead``: see ``RunAhead``."""
+    if src_all.numel() == 0:
+        return h.new_zeros(0)
+    # the adjacency's lazy caches (bit rows, longest row, degree sums; a product with rows on demand as a whole) are built HERE,
+    # on the caller's stream, before the loop forks its side streams: two phase-A streams must never race on a half-built
+    # cache (the caches also carry their own events)
+    warm()
+    outs, window = [], RunAhead(run_ahead, h.device)
+    # the ids of the whole split are bounds-checked once; the batches then run without a host sync each
+    with ops.prevalidated(src_all, dst_all, adj.size(0), adj.size(0)):
+        perms = list(PermIterator(src_all.device, src_all.shape[0], batch_size, training=False))
+        mine, world = _dealt(perms, group)
+        graphed = _graphed(predictor, h, adj, make_handles, batch_size, args, len(mine))
+
+        def begin(it):
+            e = batch_edges(perms[mine[it]])
+            if graphed is not None:
+                return graphed.begin(it, e)
+            e = e.contiguous()
+            return predictor.begin(h, adj, *make_handles(e), e, slot=it, args=args)
+
+        fin = graphed.finish if graphed is not None else (lambda tok: predictor.finish(h, tok, args))
+        for out in overlapped_steps(begin, fin, len(mine), before_step=window.wait, batch=batch_size, device=h.device):
+            outs.append(out.reshape(-1).clone() if graphed is not None else out.reshape(-1))     # (a replay's scores live in the graph's pool)
+            window.mark()
+    if world > 1:
+        from .dist import gather_dealt
+        scores = gather_dealt(outs, [int(p.numel()) for p in perms], None if group is True else group)
+    else:
+        scores = torch.cat(outs, dim=0)
+    predictor.check_errors()       # the batches' sticky status words, read once per split (flag capacity, scan state)
+    return scores
+
+
 @torch.no_grad()
 def score_edges(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int, args=None,
                 run_ahead: int = 6, group=None) -> Tensor:
     """Scores for ``edges`` [n, 2] (the layout of ``split_edge[...]['edge']``), batched like
     ``PermIterator(.., training=False)``; returns a [n] fp32 tensor on the device.  The host stays at
-    most ``run_ahead`` batches ahead of the GPU: an unbounded backlog makes the HIP runtime block the
-    host until the queue has drained completely.
+    most ``run_ahead`` batches ahead of the GPU (``RunAhead``).
 
     ``group`` (a process group, or True for the default one): the ``PermIterator`` batches are DEALT round robin to the
     ranks — every batch stays whole on one GPU, so its batch-coupled normalisation is the single-device one and no
@@ -65,43 +120,13 @@ def score_edges(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     from .model import CNLinkPredictor3hopCNs
     if isinstance(predictor, CNLinkPredictor3hopCNs):
         return _score_3hop(predictor, h, adj, adj2, edges, batch_size, args, run_ahead, group)
-    h = h.contiguous()
-    outs, done = [], []
-    if edges.shape[0] == 0:
-        return h.new_zeros(0)
-    # the adjacency's lazy caches (bit rows, longest row) are built HERE, on the caller's stream, before the loop forks its
-    # side streams: two phase-A streams must never race on a half-built cache (the caches also carry their own events)
-    adj.warm(walk=False)
-    if adj2 is not None and adj2.rows_on_demand():          # (a product formed under autograd: its rows are built on ONE stream)
-        adj2.product_bit_rows()
-    # the ids of the whole split are bounds-checked once; the batches then run without a host sync each
-    with ops.prevalidated(edges[:, 0], edges[:, 1], adj.size(0), adj.size(0)):
-        perms = list(PermIterator(edges.device, edges.shape[0], batch_size, training=False))
-        mine, world = _dealt(perms, group)
-        graphed = _graphed(predictor, h, adj, lambda e: (adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e)), batch_size, args, len(mine))
 
-        def begin(it):
-            e = edges[perms[mine[it]]].t()
-            if graphed is not None:
-                return graphed.begin(it, e)
-            e = e.contiguous()
-            return predictor.begin(h, adj, adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e), e, slot=it, args=args)
-
-        def flow(it):
-            if len(done) >= max(run_ahead, 1):
-                done.pop(0).synchronize()
-
-        fin = graphed.finish if graphed is not None else (lambda tok: predictor.finish(h, tok, args))
-        for out in overlapped_steps(begin, fin, len(mine), before_step=flow, batch=batch_size, device=h.device):
-            outs.append(out.reshape(-1).clone() if graphed is not None else out.reshape(-1))     # (a replay's scores live in the graph's pool)
-            done.append(torch.cuda.current_stream(h.device).record_event())
-    if world > 1:
-        from .dist import gather_dealt
-        scores = gather_dealt(outs, [int(p.numel()) for p in perms], None if group is True else group)
-    else:
-        scores = torch.cat(outs, dim=0)
-    predictor.check_errors()       # the batches' sticky status words, read once per split (flag capacity, scan state)
-    return scores
+    def warm():
+        adj.warm(walk=False)
+        if adj2 is not None:
+            adj2.complete()
+    return _score_batches(predictor, h.contiguous(), adj, edges[:, 0], edges[:, 1], lambda perm: edges[perm].t(),
+                          lambda e: (adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e)), warm, batch_size, args, run_ahead, group)
 
 
 def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int, args, run_ahead, group) -> Tensor:
@@ -120,19 +145,17 @@ def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
         return h.new_zeros(0)
     adj.warm(walk=False)
     adj.neighbor_degree_sum()                               # (sizes the work items of the cn3 pass)
-    if adj2.rows_on_demand():                               # (a product formed under autograd: completed first)
-        adj2.product_bit_rows()
-    outs, done, bits = [], [], None
+    adj2.complete()                                         # (a product formed under autograd: as a whole, first)
+    outs, window, bits = [], RunAhead(run_ahead, h.device), None
     with ops.prevalidated(edges[:, 0], edges[:, 1], adj.size(0), adj.size(0)):
         for perm in PermIterator(edges.device, edges.shape[0], batch_size, training=False):
-            if len(done) >= max(run_ahead, 1):
-                done.pop(0).synchronize()
+            window.wait()
             e = edges[perm].t().contiguous()
             cn3 = adjoverlap_3hop(adj, adj2, e)
             outs.append(predictor(h, adj, adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e), cn3, e, args).reshape(-1))
             word = cn3.fused.a.status[0] | cn3.fused.b.status[0]
             bits = word if bits is None else bits | word
-            done.append(torch.cuda.current_stream(h.device).record_event())
+            window.mark()
     scores = torch.cat(outs, dim=0)
     bits = int(bits.item())
     if bits:
@@ -141,42 +164,10 @@ def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
 
 
 def _score_walk(predictor, h: Tensor, adj, src_all: Tensor, dst_all: Tensor, batch_size: int, args, run_ahead, group) -> Tensor:
-    """The walk-route loop over the candidates (src_all[i], dst_all[i]): the body of ``score_edges_walk`` and of both halves of
-    ``score_mrr_split``.  ``run_ahead`` = None: no flow control (the MRR splits' loop, as it always ran)."""
+    """``score_edges_walk`` and both halves of ``score_mrr_split`` (``run_ahead`` = None: no flow control, as it always ran)."""
     from .utils import get_cn1_cn2
-    outs, done = [], []
-    if src_all.numel() == 0:
-        return h.new_zeros(0)
-    adj.warm(walk=True)            # (degree sums of the two-sided sweep: built on the caller's stream, before the side streams fork)
-    with ops.prevalidated(src_all, dst_all, adj.size(0), adj.size(0)):
-        perms = list(PermIterator(src_all.device, src_all.shape[0], batch_size, training=False))
-        mine, world = _dealt(perms, group)
-        graphed = _graphed(predictor, h, adj, lambda e: get_cn1_cn2(adj, e), batch_size, args, len(mine))
-
-        def begin(it):
-            e = torch.stack((src_all[perms[mine[it]]], dst_all[perms[mine[it]]]))
-            if graphed is not None:
-                return graphed.begin(it, e)
-            cn1, cn2 = get_cn1_cn2(adj, e)
-            return predictor.begin(h, adj, cn1, cn2, e, slot=it, args=args)
-
-        def flow(it):
-            if len(done) >= max(run_ahead, 1):
-                done.pop(0).synchronize()
-
-        fin = graphed.finish if graphed is not None else (lambda tok: predictor.finish(h, tok, args))
-        for out in overlapped_steps(begin, fin, len(mine), before_step=None if run_ahead is None else flow, batch=batch_size,
-                                    device=h.device):
-            outs.append(out.reshape(-1).clone() if graphed is not None else out.reshape(-1))
-            if run_ahead is not None:
-                done.append(torch.cuda.current_stream(h.device).record_event())
-    if world > 1:
-        from .dist import gather_dealt
-        scores = gather_dealt(outs, [int(p.numel()) for p in perms], None if group is True else group)
-    else:
-        scores = torch.cat(outs, dim=0)
-    predictor.check_errors()
-    return scores
+    return _score_batches(predictor, h, adj, src_all, dst_all, lambda perm: torch.stack((src_all[perm], dst_all[perm])),
+                          lambda e: get_cn1_cn2(adj, e), lambda: adj.warm(walk=True), batch_size, args, run_ahead, group)
 
 
 @torch.no_grad()

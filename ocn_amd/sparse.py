@@ -118,9 +118,9 @@ class SparseTensor:
 
     # One step further for a product formed while autograd records (a training step's per-batch A²): not even the counting pass
     # runs before somebody needs the row pointers — the intersection pass of a large graph asks for the bit rows of its candidates'
-    # TARGET rows only (``product_bit_rows(rows)``: ocn_hip.h, ocn_spgemm_bit_rows), two fifths of the rows at the collab shape, and
+    # TARGET rows only (``probed_bit_rows(dst)``: ocn_hip.h, ocn_spgemm_bit_rows), two fifths of the rows at the collab shape, and
     # every dense row costs a 29 KiB write.  Anything that treats the product as a matrix (row pointers, ids, nnz, all bit rows)
-    # completes it with the ordinary counting pass.  Single-stream use only (the loops that fork streams warm() first = complete).
+    # completes it with the ordinary counting pass.  Single-stream use only: ``probed_bit_rows`` holds that rule.
     @property
     def _rowptr(self) -> Tensor:
         if self._rowptr_v is None and getattr(self, "_lazy", None) is not None:
@@ -165,6 +165,10 @@ class SparseTensor:
 
     def col_materialized(self) -> bool:
         return self._col_v is not None
+
+    def rowptr_formed(self) -> Optional[Tensor]:
+        """The row pointers, or None for a product with rows on demand — which asking for ``_rowptr`` would complete."""
+        return self._rowptr_v
 
     @classmethod
     def _deferred_product(cls, rowptr: Tensor, col_thunk, bitmap: Tensor, sparse_sizes) -> "SparseTensor":
@@ -275,8 +279,7 @@ class SparseTensor:
         """The pattern as dense bit rows (cached, built once by ocn_bitrows_from_csr) when they fit
         ``ops.a1_bitmap_max_bytes``, else None: what the intersection kernel probes instead of searching a row
         (a product of ``matmul`` arrives with its bit rows already)."""
-        if getattr(self, "_lazy", None) is not None:        # (a product with rows on demand, asked for ALL its rows)
-            self._complete()
+        self.complete()                                     # (a product with rows on demand, asked for ALL its rows)
         if self._bitmap is None and self._rowptr.is_cuda:
             n, m = self._sizes
             if 0 < n * ((m + 31) // 32) * 4 <= ops.a1_bitmap_max_bytes:
@@ -296,25 +299,36 @@ class SparseTensor:
             self._await("nds")
         return self._nds
 
-    def product_bit_rows(self, rows: Optional[Tensor] = None) -> Optional[Tensor]:
-        """The bit rows this matrix ARRIVED with (``A @ A``, the block route), never built on demand: A² of a large graph
-        only has them when they fit ``ops.a2_bitmap_max_bytes`` at construction.  ``rows`` (int64 ids): the caller will probe
-        these rows only — a product whose rows are built on demand (``_lazy_product``) builds the missing ones of them now, on
-        the current stream."""
-        if getattr(self, "_lazy", None) is not None:
-            if rows is None:
-                self._complete()
-            else:
-                a_rp, a_col, b_rp, b_col = self._lazy
-                ops.spgemm_bit_rows(a_rp, a_col, b_rp, b_col, self._sizes[1], rows, self._done, self._bitmap)
-                return self._bitmap
+    def product_bit_rows(self) -> Optional[Tensor]:
+        """The bit rows this matrix ARRIVED with (``A @ A``, the block route), never built from its CSR: A² of a large graph
+        only has them when they fit ``ops.a2_bitmap_max_bytes`` at construction.  All of them: a product with rows on demand
+        is completed."""
+        self.complete()
         if self._bitmap is not None:
             self._await("bitmap")
         return self._bitmap
 
+    def probed_bit_rows(self, dst: Tensor, row_lengths: bool = False) -> Optional[Tensor]:
+        """The bit rows a candidate batch with the targets ``dst`` (int64 ids) may probe, or None: then its kernel searches
+        the CSR rows.  This is ``product_bit_rows()``, except that a product with rows on demand (``_lazy_product``) stays
+        one and builds the missing rows of ``dst`` now, on the current stream.  Rows on demand are built on ONE stream
+        only: while a loop runs phase A on side streams (``ops._overlap_active``) the product is completed instead, as it
+        is by ``complete()`` before such a loop forks.  ``row_lengths``: up to ``ops.small_graph_cols()`` columns the
+        caller's kernel reads the row lengths of this matrix beside its bit rows, so there the product is completed too."""
+        if self.rows_on_demand() and not ops._overlap_active and not (row_lengths and self._sizes[1] <= ops.small_graph_cols()):
+            a_rp, a_col, b_rp, b_col = self._lazy
+            ops.spgemm_bit_rows(a_rp, a_col, b_rp, b_col, self._sizes[1], dst, self._done, self._bitmap)
+            return self._bitmap
+        return self.product_bit_rows()
+
     def rows_on_demand(self) -> bool:
         """A product none of whose matrix-level data exists yet (see ``_lazy_product``)."""
         return getattr(self, "_lazy", None) is not None
+
+    def complete(self) -> None:
+        """Form a product with rows on demand as a whole, on the CURRENT stream: what a loop calls before it forks side streams."""
+        if self.rows_on_demand():
+            self._complete()
 
     def warm(self, walk: bool = False) -> None:
         """Build the lazy caches a candidate batch reads (bit rows, longest row, the walk route's degree sums) on the

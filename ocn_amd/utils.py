@@ -42,9 +42,19 @@ class PermIterator:
         return ret
 
 
-def _check_hop3(adj: SparseTensor, adj2: SparseTensor, tarei: Tensor) -> None:
+def _check_batch(tarei: Tensor, name: str = "tarei") -> None:
     if tarei.dim() != 2 or tarei.shape[0] != 2:
-        raise ValueError("tarei must be [2, B]")
+        raise ValueError(f"{name} must be [2, B]")
+
+
+def _endpoints(tarei: Tensor, name: str = "tarei") -> Tuple[Tensor, Tensor]:
+    """(src, dst) of a candidate batch ``tarei`` [2, B], as the contiguous int64 vectors the kernels read."""
+    _check_batch(tarei, name)
+    return tarei[0].to(torch.int64).contiguous(), tarei[1].to(torch.int64).contiguous()
+
+
+def _check_hop3(adj: SparseTensor, adj2: SparseTensor, tarei: Tensor) -> None:
+    _check_batch(tarei)
     if adj.size(0) != adj.size(1):
         raise ValueError("the 3-hop common neighbours need a square adjacency")
     if tuple(adj2.sparse_sizes()) != tuple(adj.sparse_sizes()):
@@ -52,11 +62,9 @@ def _check_hop3(adj: SparseTensor, adj2: SparseTensor, tarei: Tensor) -> None:
 
 
 def _a2_bit_rows(adj2: SparseTensor, dst: Tensor) -> Tensor:
-    """Bit rows of A² for the A³-free cn3 pass: the ones the product arrived with; of a product with rows on demand the rows
-    this batch probes (on one stream only, as ``CNState``); else built from the CSR where they fit."""
-    if adj2.rows_on_demand() and not getattr(ops, "_overlap_active", False) and adj2.size(1) > ops.small_graph_cols():
-        return adj2.product_bit_rows(dst)
-    bits = adj2.product_bit_rows()
+    """Bit rows of A² for the A³-free cn3 pass: the ones this batch may probe (``SparseTensor.probed_bit_rows``, completing a
+    small graph's product as the batch's flag pass does); else built from the CSR where they fit."""
+    bits = adj2.probed_bit_rows(dst, row_lengths=True)
     if bits is None:
         bits = adj2.bit_rows()
     if bits is None:
@@ -86,8 +94,7 @@ class CNState:
 
     def __init__(self, adj: SparseTensor, t1: Optional[SparseTensor], t2: Optional[SparseTensor],
                  tarei: Tensor, walk: bool = False, ws: Optional[dict] = None):
-        if tarei.dim() != 2 or tarei.shape[0] != 2:
-            raise ValueError("tarei must be [2, B]")
+        self.src, self.dst = _endpoints(tarei)
         for t in (t1, t2):
             if t is not None and t.sparse_sizes() != adj.sparse_sizes():
                 raise ValueError("adjoverlap: adjacency sizes differ")    # utils.py:164 assert
@@ -95,8 +102,6 @@ class CNState:
             raise ValueError("get_cn1_cn2 needs a square adjacency")
         self.adj, self.walk, self.t2 = adj, walk, t2
         self.ws = ws                           # a predictor's scratch cache: this state is then transient
-        self.src = tarei[0].to(torch.int64).contiguous()
-        self.dst = tarei[1].to(torch.int64).contiguous()
         self.B = self.src.numel()
         self.N = adj.size(1)
         ops.check_edges(self.src, self.dst, adj.size(0), adj.size(0) if walk else t1.size(0))
@@ -105,18 +110,14 @@ class CNState:
         # ... and what each group of four slots will cost the pooling, for its longest-first schedule (+ room for the schedule)
         self.sched = (ops.buf(ws, "sched", 2 * ((self.B + 3) // 4), torch.int32, self.src.device)
                       if (self.rec is not None and ops.heavy_first and self.B >= ops.sort_edges_min_batch) else None)
-        # a product whose rows are built on demand (a training step's A²): the rows this batch probes, and no row pointers — on
-        # one stream only (a loop with several phase-A streams completes the product before it forks them: pipeline.score_edges)
-        # (a small graph's pass reads the row lengths of T2 beside its bit rows: there the product is completed)
-        t2_rows = (t2 is not None and not walk and t2.rows_on_demand() and not getattr(ops, "_overlap_active", False)
-                   and self.N > ops.small_graph_cols())
+        # T2: the bit rows this batch may probe, the row pointers it has (rows on demand: none), the column ids unless deferred
+        csr2 = bm2 = None
+        if t2 is not None and not walk:
+            bm2 = t2.probed_bit_rows(self.dst, row_lengths=True)
+            csr2 = (t2.rowptr_formed(), t2._col if (t2.col_materialized() or bm2 is None) else None)
         (self.order, self.off, self.flags, self.wc, self.hist, self.cnt1, self.cnt2, self.status, self.scal) = ops.cn_flags(
-            adj._rowptr, adj._col, None if walk else (t1._rowptr, t1._col),
-            None if (walk or t2 is None) else ((None, None) if t2_rows else
-                                               (t2._rowptr, t2._col if (t2.col_materialized() or t2._bitmap is None) else None)),
-            self.src, self.dst, self.N,
-            adj.max_rowcount(), walk=walk,
-            t2_bitmap=None if (walk or t2 is None) else (t2.product_bit_rows(self.dst) if t2_rows else t2.product_bit_rows()), wsd=ws,
+            adj._rowptr, adj._col, None if walk else (t1._rowptr, t1._col), csr2, self.src, self.dst, self.N,
+            adj.max_rowcount(), walk=walk, t2_bitmap=bm2, wsd=ws,
             nds=adj.neighbor_degree_sum() if (walk and ops.walk_two_sided) else None,
             t1_bitmap=None if walk else t1.bit_rows(), rec=self.rec, sched=self.sched)
         self._hist_live = True
@@ -130,8 +131,7 @@ class CNState:
         ``ocn_amd.utils.adjoverlap`` skip it."""
         st = cls.__new__(cls)
         st.adj, st.ws = adj, ws
-        st.src = tarei[0].to(torch.int64).contiguous()
-        st.dst = tarei[1].to(torch.int64).contiguous()
+        st.src, st.dst = _endpoints(tarei)
         st.B, st.N = st.src.numel(), adj.size(1)
         dev = st.src.device
         if tuple(cn1.sizes()) != (st.B, st.N) or tuple(cn2.sizes()) != (st.B, st.N):
@@ -183,14 +183,13 @@ class CNState:
         _check_hop3(adj, adj2, tarei)
         st = cls.__new__(cls)
         st.adj, st.walk, st.t2, st.ws = adj, False, None, None
-        st.src = tarei[0].to(torch.int64).contiguous()
-        st.dst = tarei[1].to(torch.int64).contiguous()
+        st.src, st.dst = _endpoints(tarei)
         st.B, st.N = st.src.numel(), adj.size(1)
         st.rec = st.sched = st.wc = st.cnt2 = None
         if off is None:
             ops.check_edges(st.src, st.dst, adj.size(0), adj.size(0))
             off = ops.edge_offsets(adj._rowptr, st.src)
-            order = ops.order_by_node(st.src, adj.size(0)) if st.B >= ops.sort_edges_min_batch else None
+            order = ops.batch_order(st.src, adj.size(0))
         st.off, st.order = off, order
         bits = _a2_bit_rows(adj2, st.dst)
         rowptr_t, col_t, nds = _transposed(adj, undirected)
@@ -378,17 +377,29 @@ def _same_edges(a: Tensor, b: Tensor) -> bool:
     return torch.equal(a, b)
 
 
+def _check_one_batch(cns, tar_ei: Tensor, one_adjacency: str, cn1_on_adj: bool = True) -> None:
+    """``cns`` (cn1, cn2[, cn3]) and ``tar_ei`` describe ONE batch: source rows from one adjacency (else, and unless the caller's
+    ``cn1_on_adj`` holds, NotImplementedError(``one_adjacency``)), the same shapes, the same edges."""
+    first = cns[0]
+    if not cn1_on_adj or any(c.adj1 is not first.adj1 for c in cns[1:]):
+        raise NotImplementedError(one_adjacency)
+    exc = why = None
+    if tar_ei.shape != first.tarei.shape or any(c.tarei.shape != first.tarei.shape for c in cns[1:]):
+        exc, why = ValueError, "describe different numbers of candidate edges"
+    elif ops.validate_indices and not (all(_same_edges(first.tarei, c.tarei) for c in cns[1:]) and _same_edges(first.tarei, tar_ei)):
+        exc, why = NotImplementedError, "must be built from the same candidate edges"
+    if exc is not None:
+        raise exc(", ".join(("cn1", "cn2", "cn3")[:len(cns)]) + " and tar_ei " + why)
+
+
 def fuse3(cn1: "CNBatch", cn2: "CNBatch", cn3: "CNBatch", tar_ei: Tensor) -> CNState3:
     """(cn1, cn2, cn3) = adjoverlap(adj, adj | adj2 | adj3, e) of one candidate batch; cn3 may be
     ``adjoverlap_3hop(adj, adj2, e)`` instead, built on the SAME ``adj2`` object as cn2: no A³ is needed then."""
     for c in (cn1, cn2, cn3):
         if not isinstance(c, CNBatch) or (c.mode != "pattern" and not (c is cn3 and c.mode == "hop3")):
             raise NotImplementedError("cn6 takes the handles returned by ocn_amd.utils.adjoverlap (cn3: or adjoverlap_3hop)")
-    if not (cn1.adj1 is cn2.adj1 is cn3.adj1) or cn1.adj2 is not cn1.adj1:
-        raise NotImplementedError("cn1/cn2/cn3 must come from adjoverlap(adj, adj|adj2|adj3, e) of one adjacency")
-    if ops.validate_indices and not (_same_edges(cn1.tarei, cn2.tarei) and _same_edges(cn1.tarei, cn3.tarei)
-                                     and _same_edges(cn1.tarei, tar_ei)):
-        raise NotImplementedError("cn1, cn2, cn3 and tar_ei must be built from the same candidate edges")
+    _check_one_batch((cn1, cn2, cn3), tar_ei, "cn1/cn2/cn3 must come from adjoverlap(adj, adj|adj2|adj3, e) of one adjacency",
+                     cn1_on_adj=cn1.adj2 is cn1.adj1)
     if cn3.mode == "hop3":
         if cn3.adj2 is not cn2.adj2:
             raise NotImplementedError("adjoverlap_3hop(adj, adj2, e) must be built on the adj2 object of cn2 = adjoverlap(adj, adj2, e)")
@@ -414,12 +425,7 @@ def fuse(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None, adj: Optional[Spar
     if not isinstance(cn1, CNBatch) or not isinstance(cn2, CNBatch):
         raise TypeError("ocn_amd predictors take the CNBatch handles returned by ocn_amd.utils.adjoverlap "
                         "/ get_cn1_cn2, or explicit [B, N] SparseTensors")
-    if cn1.adj1 is not cn2.adj1:
-        raise NotImplementedError("cn1 and cn2 must select their source rows from the same adjacency")
-    if cn1.tarei.shape != cn2.tarei.shape or cn1.tarei.shape != tar_ei.shape:
-        raise ValueError("cn1, cn2 and tar_ei describe different numbers of candidate edges")
-    if ops.validate_indices and not (_same_edges(cn1.tarei, cn2.tarei) and _same_edges(cn1.tarei, tar_ei)):
-        raise NotImplementedError("cn1, cn2 and tar_ei must be built from the same candidate edges")
+    _check_one_batch((cn1, cn2), tar_ei, "cn1 and cn2 must select their source rows from the same adjacency")
     if cn1.mode == "walk1" and cn2.mode == "walk2":
         return CNState(cn1.adj1, None, None, cn1.tarei, walk=True, ws=ws)
     if cn1.mode != "pattern" or cn2.mode != "pattern":
@@ -433,14 +439,11 @@ class CN8State:
     the integer CN counts in ``cnt1`` / ``cnt2``."""
 
     def __init__(self, adj: SparseTensor, t1: SparseTensor, t2: SparseTensor, tarei: Tensor, ws: Optional[dict] = None):
-        if tarei.dim() != 2 or tarei.shape[0] != 2:
-            raise ValueError("tarei must be [2, B]")
+        self.src, self.dst = _endpoints(tarei)
         for t in (t1, t2):
             if t.sparse_sizes() != adj.sparse_sizes():
                 raise ValueError("adjoverlap: adjacency sizes differ")    # utils.py:164 assert
         self.adj, self.t1, self.t2, self.ws = adj, t1, t2, ws
-        self.src = tarei[0].to(torch.int64).contiguous()
-        self.dst = tarei[1].to(torch.int64).contiguous()
         self.B, self.N = self.src.numel(), adj.size(1)
         self.walk = False
         self.cnt1 = self.cnt2 = self.order = None
@@ -450,14 +453,12 @@ class CN8State:
         adj, t1, t2 = self.adj, self.t1, self.t2
         if h.dim() != 2 or h.shape[0] != self.N:
             raise ValueError("h must have one row per column of the adjacency")
-        # T2: the bit rows the product arrived with (rows built on demand: the ones this batch probes — on one stream only,
-        # as CNState), else its CSR; T1: bit rows where they fit (small dense graphs), else its CSR
-        lazy = t2.rows_on_demand() and not getattr(ops, "_overlap_active", False)
-        bm2 = t2.product_bit_rows(self.dst) if lazy else t2.product_bit_rows()
+        # T2: the bit rows this batch may probe (``SparseTensor.probed_bit_rows``), else its CSR; T1: bit rows where they fit
+        # (small dense graphs), else its CSR
+        bm2 = t2.probed_bit_rows(self.dst)
         csr2 = None if bm2 is not None else (t2._rowptr, t2._col)
         bm1 = t1.bit_rows()
-        if self.B >= ops.sort_edges_min_batch:
-            self.order = ops.order_by_node(self.src, adj.size(0), self.ws)
+        self.order = ops.batch_order(self.src, adj.size(0), self.ws)
         x1, x2, xij, self.cnt1, self.cnt2 = ops.cn8_pool(adj._rowptr, adj._col, (t1._rowptr, t1._col), csr2, self.src, self.dst, h,
                                                          t1_bitmap=bm1, t2_bitmap=bm2, order=self.order, wsd=self.ws, n_cols=self.N)
         return x1, x2, xij
@@ -468,12 +469,7 @@ def fuse8(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None) -> Optional[CN8St
     ``fuse``), or None for anything else — walk handles and explicit matrices take the flag form (``fuse``)."""
     if not (isinstance(cn1, CNBatch) and isinstance(cn2, CNBatch) and cn1.mode == "pattern" and cn2.mode == "pattern"):
         return None
-    if cn1.adj1 is not cn2.adj1:
-        raise NotImplementedError("cn1 and cn2 must select their source rows from the same adjacency")
-    if cn1.tarei.shape != cn2.tarei.shape or cn1.tarei.shape != tar_ei.shape:
-        raise ValueError("cn1, cn2 and tar_ei describe different numbers of candidate edges")
-    if ops.validate_indices and not (_same_edges(cn1.tarei, cn2.tarei) and _same_edges(cn1.tarei, tar_ei)):
-        raise NotImplementedError("cn1, cn2 and tar_ei must be built from the same candidate edges")
+    _check_one_batch((cn1, cn2), tar_ei, "cn1 and cn2 must select their source rows from the same adjacency")
     return CN8State(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, ws=ws)
 
 

@@ -31,6 +31,34 @@ def test_library_exports_every_declared_symbol(hiplib):
     assert hiplib.ocn_spgemm_max_cols() >= 1_000_000
 
 
+def _declared_signatures():
+    """name -> (restype, argtypes) as include/ocn_hip.h declares them: any pointer is a c_void_p, the scalar types map to the
+    ctypes of the same width (the per-feature host tests compare argument COUNTS, which a swapped pointer and integer pass)."""
+    import ctypes
+    scalar = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "int": ctypes.c_int32, "uint64_t": ctypes.c_uint64,
+              "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
+
+    def ctype(decl):
+        if "*" in decl:
+            return ctypes.c_void_p
+        return scalar[[w for w in re.findall(r"[A-Za-z_]\w*", decl) if w != "const"][0]]
+    txt = open(os.path.join(ROOT, "include", "ocn_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*|^\s*#[^\n]*", " ", txt, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"\b(\w+[\s\*]+)(ocn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        params = params.strip()
+        out[name] = (ctype(ret), [] if params in ("", "void") else [ctype(p) for p in params.split(",")])
+    return out
+
+
+def test_ctypes_table_has_the_types_the_header_declares():
+    want = _declared_signatures()
+    assert sorted(want) == _declared() == sorted(_lib.SIGNATURES) and len(want) >= 100
+    wrong = {n: (want[n], (res, list(args))) for n, (res, args) in _lib.SIGNATURES.items() if want[n] != (res, list(args))}
+    assert not wrong, f"include/ocn_hip.h and _lib.SIGNATURES disagree: {wrong}"
+
+
 def test_entries_reject_bad_arguments_before_any_launch(hiplib):
     """Argument errors come back as OCN_EINVAL (-1) from the C entries themselves — checked here without a GPU, since
     every one of these returns before its first HIP call (ocn_hip.h: error behaviour)."""

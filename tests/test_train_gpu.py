@@ -276,6 +276,76 @@ def test_product_rows_are_built_on_demand_under_autograd(hiplib, monkeypatch):
     assert not SparseTensor.from_torch_sparse_coo_tensor(sp @ sp, False).rows_on_demand()
 
 
+def test_every_consumer_of_a_product_holds_the_one_stream_rule(hiplib, monkeypatch):
+    """Rows on demand are built on one stream only (``SparseTensor.probed_bit_rows``), for all four consumers of a product's
+    bit rows: the flag pass, the A³-free cn3 pass, cn8's one-pass pooling and the 2-hop link heuristics.  On a graph just past
+    the small-graph histogram, 96 candidates with repeated targets: outside a loop with phase-A side streams the product
+    stays one, exactly the batch's target rows exist, and every output is bit-equal to the eager product's; inside such a
+    loop (``ops._overlap_active``) the product is completed, once, with the same outputs."""
+    from ocn_amd.heuristics import link_heuristics
+    from ocn_amd.utils import CN8State, CNState, adjoverlap_3hop
+    from tests.helpers import batch, make_graph, same_product, to_product
+    n = ops.small_graph_cols() + 8
+    oadj = make_graph(n, 6, 60, seed=11, isolated=40)
+    adj = to_product(oadj, DEV)
+    sp = adj.to_torch_sparse_coo_tensor()
+    with torch.no_grad():
+        full = SparseTensor.from_torch_sparse_coo_tensor(sp @ sp, False)
+    assert torch.is_grad_enabled() and not full.rows_on_demand()
+    e = batch(oadj, 96, 3).to(DEV)
+    e[1, 32:64] = e[1, :32]                                     # targets of other candidates again ...
+    e[1, 64:80] = e[1, 0]                                       # ... one target many times ...
+    e[1, 95] = n - 1                                            # ... and an isolated one (an empty row of A²)
+    seen = torch.zeros(n, dtype=torch.bool, device=DEV)
+    seen[e[1]] = True
+    x = torch.randn(n, 16, generator=torch.Generator().manual_seed(4)).to(DEV)
+
+    def flag_pass(a2):
+        st = CNState(adj, adj, a2, e)
+        return st.off, st.flags[: int(st.off[-1])], st.cnt1, st.cnt2, st.hist
+
+    def cn3_pass(a2):
+        cn3 = adjoverlap_3hop(adj, a2, e)
+        cnt, st = cn3.counts(), cn3._state
+        return cnt, st.flags[: int(st.off[-1])], st.hist
+
+    def cn8_pool(a2):
+        st = CN8State(adj, adj, a2, e)
+        return (*st.pool(x), st.cnt1, st.cnt2)
+
+    def heuristics(a2):
+        return (link_heuristics(adj, a2, e, kinds=("cn2", "aa2", "ra2")),)
+
+    completed, complete = [], SparseTensor._complete
+    monkeypatch.setattr(SparseTensor, "_complete", lambda self: (completed.append(self), complete(self))[1])
+    for run in (flag_pass, cn3_pass, cn8_pool, heuristics):
+        want = [t.clone() for t in run(full)]
+        assert any(int(t.ne(0).sum()) for t in want), run.__name__
+        for active in (False, True):
+            lazy = SparseTensor.from_torch_sparse_coo_tensor(sp @ sp, False)
+            assert lazy.rows_on_demand()
+            monkeypatch.setattr(ops, "_overlap_active", active)
+            got = run(lazy)
+            monkeypatch.setattr(ops, "_overlap_active", False)
+            assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want)), (run.__name__, active)
+            if active:
+                assert not lazy.rows_on_demand() and len(completed) == 1 and completed[0] is lazy, run.__name__
+                same_product(lazy, full)
+                completed.clear()
+            else:
+                assert lazy.rows_on_demand() and not completed, run.__name__
+                assert torch.equal(lazy._done.bool(), seen), run.__name__       # exactly the batch's target rows exist ...
+                assert torch.equal(lazy._bitmap[seen], full._bitmap[seen])      # ... and they are the product's
+    # up to small_graph_cols() columns the flag pass reads T2's row lengths, so there (row_lengths=True) the cn3 pass completes too
+    from ocn_amd.utils import _a2_bit_rows
+    small = to_product(make_graph(300, 6, 40, seed=12), DEV)
+    lazy = SparseTensor._lazy_product(small, small)
+    bits = _a2_bit_rows(lazy, torch.arange(10, device=DEV))
+    assert not lazy.rows_on_demand() and len(completed) == 1
+    sp = small.to_torch_sparse_coo_tensor()
+    assert torch.equal(bits, SparseTensor.from_torch_sparse_coo_tensor(sp @ sp, False).product_bit_rows())
+
+
 @pytest.mark.parametrize("H,rows", [(32, 1000), (64, 4097), (256, 20000), (512, 333), (16, 70000)])
 @pytest.mark.parametrize("ln,relu,p", [(True, True, 0.0), (True, True, 0.3), (False, True, 0.05), (True, False, 0.0), (False, False, 0.5)])
 def test_ln_dropout_relu_tail_matches_torch_autograd(hiplib, H, rows, ln, relu, p):
