@@ -6,23 +6,22 @@ CNLinkPredictorbaselearn, model.py:3021-3229; ``cn8`` = CNLinkPredictorbaselearn
 reference's constructor signatures and ``state_dict`` key layout, so checkpoints and the unchanged
 drivers work.  The sparse arithmetic runs in libocn_hip.so (no torch_sparse / pygho / PyG); in eval the
 dense ``Linear`` / ``LayerNorm`` / ``ReLU`` heads run on the bf16x6 MFMA kernel of the same library
-(one fused launch ``ocn_heads_fused`` from H = 128 up, else ``_seq_eval`` / ``_heads_grouped``); under autograd the
+(one fused launch ``ocn_heads_fused`` from H = 128 up, else ``_seq_eval`` / ``_heads_layered``); under autograd the
 heads' Linear layers run through ``_LinearFn`` (forward and input gradient on the same kernel).  The ``nn`` modules hold
 the parameters.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Final, Iterable, Optional
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-import os
-
 from . import ops
 from .sparse import SparseTensor
-from .utils import fuse
+from .utils import fuse, scratch_set_count
 
 
 # ------------------------------------------------------------------------------------------
@@ -602,12 +601,27 @@ def _seq_train(seq: nn.Sequential, x: Tensor) -> Tensor:
     return x
 
 
+def _runner(on_gpu: bool):
+    """How a head's ``nn.Sequential`` runs with autograd on: ``_seq_train`` on the GPU, else the module itself."""
+    return _seq_train if (on_gpu and ops.train_linear) else (lambda seq, t: seq(t))
+
+
+# One parse of a predictor's heads at width H: the stages of xcn1lin / xcn2lin / xijlin and of ``lin`` in front of its
+# Linear(H, 1) ``tail`` (``sl``, ``tail``: None where ``lin`` does not end that way), and which evaluation takes them — ``layered``:
+# 3-layer pooled heads ending in a plain Linear, 1- or 2-layer xijlin (``_heads_layered``); ``skipping``: ... on class-major rows
+# too, ``lin``'s tail scattering to batch order; ``fused``: the drivers' layout, all of it in ocn_heads_fused.
+_HeadLayout = namedtuple("_HeadLayout", "sa sb sx sl tail layered skipping fused")
+_LATE = object()        # token slot 1: the histogram all-reduce is started by finish(), on ITS stream
+
+
 class _CNPredictorBase(nn.Module):
-    """Parameters and MLP heads shared by cn5 and cn7 (model.py:2173-2239 ≡ 3023-3089).  The
-    ``nn.Sequential`` layouts are part of the checkpoint contract (state_dict keys)."""
+    """Parameters, MLP heads and the batch path shared by cn5, cn7 and cn8 (model.py:2173-2239 ≡ 3023-3089).  The
+    ``nn.Sequential`` layouts are part of the checkpoint contract (state_dict keys).  A predictor differs from cn5 through
+    ``_weights``, ``_rowsum``, ``_batch_state`` and the three class attributes below."""
     cndeg: Final[int]
     _xcn2_on_union = True          # pooled xcn2 lives on cn1 ∪ cn2 (cn5); cn7 overrides: raw cn2 only
     _weights_need_args = False     # cn7: its column weights read ``args.sum``
+    _exchanges_hist = True         # edge-sharded, the column histograms are summed over the ranks; cn8 pools without them
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, edrop=0.0,
                  ln=False, cndeg=-1, use_xlin=False, tailact=False, twolayerlin=False, beta=1.0):
@@ -644,6 +658,10 @@ class _CNPredictorBase(nn.Module):
         self.n = 0
         self._shard_group, self._sharded = None, False
         self._ws = {}                          # scratch reused from batch to batch on the no-grad path
+        self._ws_slots = []                    # ... and one set per batch in flight for begin / finish (_scratch_set)
+        self._cache = {}                       # name -> (key, value): derived constants, see _cached / _drop_caches
+        self._rowsum_cache = None              # cn7: A·h of the live embeddings (_rowsum)
+        self._skip_state = None                # per-run state of the zero-row skipping, from the first probe on
 
     def set_edge_sharding(self, group=None, enabled: bool = True) -> None:
         """The candidate batch handed to ``forward`` is one rank's slice of a global batch: sum the
@@ -654,83 +672,92 @@ class _CNPredictorBase(nn.Module):
         """Edge-sharded batches: sum the column histograms over the ranks.  The collective is started, the class
         ordering of the batch rows (which reads the per-row counts only) is enqueued beside it, then the current stream
         waits for the sum."""
-        if self._sharded:
+        if self._sharded and self._exchanges_hist:
             from .dist import allreduce_hist_finish, allreduce_hist_start
             handle = allreduce_hist_start(st.hist, self._shard_group, valued=st.walk, slice_edges=st.B)
-            st.sharded, st.shard_group = True, self._shard_group
+            st.mark_sharded(self._shard_group)
             if x is not None:
                 self._class_order(st, x)
             allreduce_hist_finish(handle)
             ops._mark("allreduce_hist")
         return st
 
+    def _batch_state(self, x, cn1, cn2, tar_ei, ws, adj):
+        """The batch state of (cn1, cn2); a state that pools in its own pass arrives with ``pooled`` set (cn8)."""
+        return fuse(cn1, cn2, tar_ei, ws, adj=adj)
+
+    def _score(self, x, adj, cn1, cn2, tar_ei, args=None):
+        """The one-call batch path: state, exchange, weights, pooling, heads."""
+        st = self._exchange(self._batch_state(x, cn1, cn2, tar_ei, self._scratch(x), adj), x)
+        xcn1, xcn2, xij = st.pooled if st.pooled is not None else self._pool(st, self._weights(st, args), x)
+        return self._heads(x, xcn1, xcn2, xij, st.cls)
+
+    def _scratch_set(self, slot: int) -> dict:
+        n_sets = scratch_set_count()
+        if len(self._ws_slots) != n_sets:
+            self._ws_slots = [dict() for _ in range(n_sets)]
+        return self._ws_slots[slot % n_sets]
+
     # ---- two-phase scoring (eval, no grad) for loops that keep two batches in flight ---------------------------
     # begin(t + 1) is enqueued before finish(t): in the edge-sharded mode the histogram all-reduce of batch t then
     # runs beside the intersection pass of batch t + 1 instead of stalling the stream (ocn_amd/dist.py; bench.py).
     def begin(self, x, adj, cn1, cn2, tar_ei, slot: int = 0, args=None):
-        """Phase A: the intersection pass of one batch (scratch set ``slot`` mod ``ops.overlap_depth`` — a batch in phase A
+        """Phase A: the intersection pass of one batch (scratch set ``slot`` mod ``scratch_set_count()`` — a batch in phase A
         must not share buffers with the ones still in flight) and, sharded, the START of the histogram sum.  Returns a token."""
         if self.training or torch.is_grad_enabled():
             raise RuntimeError("begin / finish is the no-grad scoring path: call .eval() under torch.no_grad()")
-        n_sets = max(2, int(ops.overlap_depth), int(ops.overlap_depth_small))
-        if len(getattr(self, "_ws_slots", ())) != n_sets:
-            self._ws_slots = [dict() for _ in range(n_sets)]
-        st = fuse(cn1, cn2, tar_ei, self._ws_slots[slot % n_sets], adj=adj)
-        handle = None
-        if self._sharded:
+        st = self._batch_state(x, cn1, cn2, tar_ei, self._scratch_set(slot), adj)
+        if st.pooled is not None:              # (cn8's one-pass state: nothing to exchange, weigh or order)
+            return st, None, None
+        if self._sharded and self._exchanges_hist:
             from .dist import allreduce_hist_start
-            st.sharded, st.shard_group = True, self._shard_group
+            st.mark_sharded(self._shard_group)
             if ops.shard_reduce_in_finish if ops.shard_reduce_in_finish is not None else ops._overlap_active:
-                handle = "late"                    # (started by finish(), on ITS stream: see there)
-            else:
-                # the whole interleaved buffer, no copy-out / copy-back of the packed word: the collective is hidden behind the
-                # next batch's intersection pass, its extra bytes are free, the two copies were not
-                handle = allreduce_hist_start(st.hist, self._shard_group, valued=True, slice_edges=st.B)
+                return st, _LATE, None
+            # the whole interleaved buffer, no copy-out / copy-back of the packed word: the collective is hidden behind the
+            # next batch's intersection pass, its extra bytes are free, the two copies were not
+            return st, allreduce_hist_start(st.hist, self._shard_group, valued=True, slice_edges=st.B), None
         # Unsharded, the batch's histogram is complete when the intersection pass ends: the column weights — and, for a
         # trained cn5 / cn6 (innerprod != 0), the order-exact column sums in front of them, 0.2 ms of latency-bound chains at
         # the collab shape — belong to phase A, which the scoring loops run beside the previous batch's pooling and heads.
         # (cn7's weights need ``args.sum``: pass ``args``.)
-        w = None
-        if handle is None and not self._sharded:
-            if args is not None or not self._weights_need_args:
-                w = self._weights(st, args)
-            if ops.phase_a_extras:
-                self._class_order(st, x)           # reads the per-row counts only: off the critical phase too
-                st.prepare_schedule(x.shape[1])    # ... as does the pooling's visiting order (group costs of the intersection pass)
-                if ops.phase_a_pool and w is not None:
-                    # ... and the pooling itself: it needs the weights and the embeddings only.  Phase B is then the heads alone
-                    # (the caller's stream carried pooling + heads, 0.32 ms of kernels back to back, beside side streams with 0.2 ms
-                    # each: the pipeline's stages are better matched this way)
-                    st.pooled = self._pool(st, w, x)
-        return st, handle, w
+        w = self._weights(st, args) if (args is not None or not self._weights_need_args) else None
+        if ops.phase_a_extras:
+            self._class_order(st, x)           # reads the per-row counts only: off the critical phase too
+            st.prepare_schedule(x.shape[1])    # ... as does the pooling's visiting order (group costs of the intersection pass)
+            if ops.phase_a_pool and w is not None:
+                # ... and the pooling itself: it needs the weights and the embeddings only.  Phase B is then the heads alone
+                # (the caller's stream carried pooling + heads, 0.32 ms of kernels back to back, beside side streams with 0.2 ms
+                # each: the pipeline's stages are better matched this way)
+                st.pooled = self._pool(st, w, x)
+        return st, None, w
 
     def finish(self, x, token, args=None):
         """Phase B: class order (beside the collective), wait for the histogram sum, weights (unless phase A had them),
         pooling, heads."""
         st, handle, w_early = token
         ops._mark("begin")                     # (stage timers: this phase may run on another stream than phase A did)
-        if isinstance(handle, str):            # "late": the collective starts here, the class ordering runs beside it, and the
+        if handle is _LATE:                    # the collective starts here, the class ordering runs beside it, and the
             from .dist import allreduce_hist_start      # next batch's phase A (another stream) fills the rest of the wait
             handle = allreduce_hist_start(st.hist, self._shard_group, valued=True, slice_edges=st.B)
-        if not getattr(st, "_cls_decided", False):
+        if not st._cls_decided:
             self._class_order(st, x)
         if handle is not None:
             from .dist import allreduce_hist_finish
             allreduce_hist_finish(handle)
             ops._mark("allreduce_hist")
-        pooled = getattr(st, "pooled", None)
+        pooled = st.pooled
         if pooled is None:
-            w = w_early if w_early is not None else self._weights(st, args)
-            pooled = self._pool(st, w, x)
+            pooled = self._pool(st, w_early if w_early is not None else self._weights(st, args), x)
         xcn1, xcn2, xij = pooled
-        return self._heads(x, xcn1, xcn2, xij, getattr(st, "cls", None))
+        return self._heads(x, xcn1, xcn2, xij, st.cls)
 
     def check_errors(self) -> None:
         """Read the STICKY status words of this predictor's scratch sets (one host sync) and raise for what the batches since
         the last check left there: a flag buffer that was too small, offsets from a scan whose workspace was not zero
         (ocn_hip.h: OCN_ST_CAP / OCN_ST_SCAN).  The scoring loops call it once per split; a driver that calls ``forward`` per
         batch can call it whenever it reads scores anyway."""
-        words = [t for d in ([self._ws] + list(getattr(self, "_ws_slots", ()))) for k, t in d.items() if k[0] == "status"]
+        words = [t for d in [self._ws] + self._ws_slots for k, t in d.items() if k[0] == "status"]
         if not words:
             return
         bits = 0
@@ -747,10 +774,11 @@ class _CNPredictorBase(nn.Module):
         st.cls = None
         st._cls_decided = True
         if (ops.skip_zero_rows and not self.training and not torch.is_grad_enabled() and st.B >= ops.skip_zero_min_batch
-                and st.cnt2 is not None and (self._fused_plan(x.shape[1]) is not None or self._heads_plan(x.shape[1]) is not None)
-                and self._skip_worthwhile()):
-            st.cls = ops.class_order(st.cnt1, st.cnt2, st.order, st.ws)
-            self._skip_probe(st.cls[2], st.B)
+                and st.cnt2 is not None):
+            lay = self._layout(x.shape[1])
+            if (lay.fused or lay.skipping) and self._skip_worthwhile():
+                st.cls = ops.class_order(st.cnt1, st.cnt2, st.order, st.ws)
+                self._skip_probe(st.cls[2], st.B)
 
     def _scratch(self, x):
         """Reuse scratch across batches only where nothing outlives the call: no autograd graph (it
@@ -761,7 +789,7 @@ class _CNPredictorBase(nn.Module):
         x = x.contiguous()
         if torch.is_grad_enabled() and x.requires_grad:
             return _PoolFn.apply(x, st, w)
-        if not getattr(st, "_cls_decided", False):
+        if not st._cls_decided:
             self._class_order(st, x)
         rs = self._rowsum(st, x)
         if st.cls is not None:
@@ -779,7 +807,7 @@ class _CNPredictorBase(nn.Module):
     # host memory WITHOUT waiting; whenever a copy has landed by the time a later batch arrives, its skippable
     # share decides: below ``ops.skip_zero_min_share`` the next ``ops.skip_zero_backoff`` batches run plain.
     def _skip_worthwhile(self) -> bool:
-        pr = getattr(self, "_skip_state", None)
+        pr = self._skip_state
         if pr is None:
             return True
         if torch.cuda.is_current_stream_capturing():                           # no event query while capturing:
@@ -798,7 +826,7 @@ class _CNPredictorBase(nn.Module):
         return True
 
     def _skip_probe(self, ranges: Tensor, B: int) -> None:
-        pr = getattr(self, "_skip_state", None)
+        pr = self._skip_state
         if pr is None:
             pr = self._skip_state = dict(host=torch.empty((ops.CLASS_RANGES, 2), dtype=torch.int64).pin_memory(),
                                          pending=None, B=0, off=0, share=1.0)
@@ -810,24 +838,50 @@ class _CNPredictorBase(nn.Module):
             pr["B"] = B
             pr["pending"] = torch.cuda.current_stream(ranges.device).record_event()
 
+    def _cached(self, name: str, key, make):
+        """``make()`` once per ``key``: every constant derived from the parameters or the module structure lives in
+        ``self._cache`` under a name, beside the key it was made for; ``_drop_caches`` empties the dict."""
+        hit = self._cache.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._cache[name] = (key, make())
+        return hit[1]
+
+    def _layout(self, H: int) -> _HeadLayout:
+        """The heads parsed once per (H, knobs that gate an evaluation): see ``_HeadLayout``.  (``_cached``, written out: this
+        lookup runs twice per batch.)"""
+        key, hit = (H, ops.fast_linear, ops.fused_heads), self._cache.get("layout")
+        if hit is None or hit[0] != key:
+            hit = self._cache["layout"] = (key, self._parse_heads(H))
+        return hit[1]
+
+    def _parse_heads(self, H: int) -> _HeadLayout:
+        sa, sb, sx = _stages(self.xcn1lin, H), _stages(self.xcn2lin, H), _stages(self.xijlin, H)
+        mods = [m for m in self.lin if not isinstance(m, (nn.Dropout, nn.Identity))]
+        tail = mods[-1] if (len(mods) >= 2 and isinstance(mods[-1], nn.Linear) and mods[-1].out_features == 1
+                            and mods[-1].in_features == H) else None
+        sl = _stages(nn.Sequential(*mods[:-1]), H) if tail is not None else None
+        pooled3 = (sa is not None and sb is not None and sx is not None and len(sa) == 3 and len(sb) == 3 and len(sx) in (1, 2)
+                   and sa[2][1] is None and not sa[2][2] and sb[2][1] is None and not sb[2][2])
+        layered = bool(pooled3 and ops.fast_linear and H in ops.LINEAR_WIDTHS)
+        fused = bool(pooled3 and ops.fused_heads and H in ops.HEADS_WIDTHS
+                     and all(st[0][1] is None and st[0][2] and st[1][2] for st in (sa, sb))
+                     and sx[0][2] and (len(sx) == 1 or (sx[1][1] is None and not sx[1][2]))
+                     and sl is not None and len(sl) == 1 and sl[0][2])
+        if fused:                                                   # LayerNorm in all four places or in none, one eps
+            lns = [sa[1][1], sb[1][1], sx[0][1], sl[0][1]]
+            fused = all(l is None for l in lns) or (all(l is not None for l in lns) and len({l.eps for l in lns}) == 1)
+        return _HeadLayout(sa, sb, sx, sl, tail, layered, layered and sl is not None, fused)
+
     def _heads_plan(self, H: int):
-        """Parsed stages of the four heads when the zero-row-skipping evaluation applies (3-layer pooled
-        heads ending in a plain Linear, 1- or 2-layer xijlin, `lin` ending in the fused Linear(H, 1) dot),
-        else None.  Cached per module structure."""
-        key = (H, ops.fast_linear)
-        if getattr(self, "_plan_key", None) != key:
-            plan = None
-            if H in ops.LINEAR_WIDTHS and ops.fast_linear:
-                sa, sb, sx = _stages(self.xcn1lin, H), _stages(self.xcn2lin, H), _stages(self.xijlin, H)
-                mods = [m for m in self.lin if not isinstance(m, (nn.Dropout, nn.Identity))]
-                tail_ok = (len(mods) >= 2 and isinstance(mods[-1], nn.Linear) and mods[-1].out_features == 1
-                           and mods[-1].in_features == H and _stages(nn.Sequential(*mods[:-1]), H) is not None)
-                if (sa is not None and sb is not None and sx is not None and len(sa) == 3 and len(sb) == 3
-                        and len(sx) in (1, 2) and sa[2][1] is None and not sa[2][2] and sb[2][1] is None
-                        and not sb[2][2] and tail_ok):
-                    plan = (sa, sb, sx)
-            self._plan, self._plan_key = plan, key
-        return self._plan
+        """(sa, sb, sx) when the zero-row-skipping layered evaluation applies, else None."""
+        lay = self._layout(H)
+        return (lay.sa, lay.sb, lay.sx) if lay.skipping else None
+
+    def _fused_plan(self, H: int):
+        """(sa, sb, sx, the one stage of lin, its Linear(H, 1) tail) when ocn_heads_fused evaluates the heads (the drivers'
+        layout: 3-layer pooled heads, 1- or 2-layer xijlin, single-layer lin, in_channels == hidden), else None."""
+        lay = self._layout(H)
+        return (lay.sa, lay.sb, lay.sx, lay.sl[0], lay.tail) if lay.fused else None
 
     def innerprod1(self, st):
         """model.py:2241-2250: in training the running mean of Σ(cn2 ⊙ ncn1) is updated and used;
@@ -842,8 +896,8 @@ class _CNPredictorBase(nn.Module):
         return self.innerprod
 
     def _drop_caches(self) -> None:
-        self._coef_key = self._mixw_key = self._zc_key = self._plan_key = self._fplan_key = self._fpack_key = None
-        self._zc_params = self._fp_params = None
+        self._cache.clear()
+        self._rowsum_cache = None
         for p in self.parameters():
             ops._panels.pop(id(p), None)
 
@@ -863,37 +917,37 @@ class _CNPredictorBase(nn.Module):
     def _mix_coef(self) -> Tensor:
         """[σ(α0), σ(α0)σ(α1), β] on the device, recomputed only when alpha / beta change
         (their ``_version`` / storage): three tiny launches less per candidate batch."""
-        key = (self.alpha.data_ptr(), self.alpha._version, self.beta.data_ptr(), self.beta._version)
-        if getattr(self, "_coef_key", None) != key:
+        def make():
             alpha = torch.sigmoid(self.alpha.detach()).cumprod(-1)
-            self._coef = torch.cat([alpha[:2], self.beta.detach()]).contiguous()
-            self._coef_key = key
-        return self._coef
+            return torch.cat([alpha[:2], self.beta.detach()]).contiguous()
+        return self._cached("coef", (self.alpha.data_ptr(), self.alpha._version, self.beta.data_ptr(), self.beta._version), make)
 
     def _mix_weight(self, la: nn.Linear, lb: nn.Linear):
         """[σ(α0)·W3a | σ(α0)σ(α1)·W3b] and the matching bias: the branch mix of model.py:2436 folded
         into one K = 2H Linear over the concatenated second-layer outputs.  Cached like the panels."""
-        key = (self._mix_coef().data_ptr(), self._coef_key, la.weight.data_ptr(), la.weight._version,
-               lb.weight.data_ptr(), lb.weight._version, la.bias._version, lb.bias._version)
-        if getattr(self, "_mixw_key", None) != key:
-            c = self._mix_coef()
+        c = self._mix_coef()
+
+        def make():
             with torch.no_grad():
-                self._mixw = torch.cat([c[0] * la.weight, c[1] * lb.weight], dim=1).contiguous()
-                self._mixb = (c[0] * la.bias + c[1] * lb.bias).contiguous()
-            self._mixw_key = key
-        return self._mixw, self._mixb
+                return (torch.cat([c[0] * la.weight, c[1] * lb.weight], dim=1).contiguous(),
+                        (c[0] * la.bias + c[1] * lb.bias).contiguous())
+        return self._cached("mixw", (c.data_ptr(), self._cache["coef"][0], la.weight.data_ptr(), la.weight._version,
+                                     lb.weight.data_ptr(), lb.weight._version, la.bias._version, lb.bias._version), make)
+
+    def _params_of(self, name: str, *seqs):
+        """The parameters of some heads, walked once (walking the module tree every batch cost 60 us of host time): an entry
+        of ``_cache`` like the others, with no key beside ``_drop_caches``."""
+        hit = self._cache.get(name)
+        if hit is None:
+            hit = self._cache[name] = (None, [p for seq in seqs for p in seq.parameters()])
+        return hit[1]
 
     def _zero_consts(self, sa, sb, H: int, dev):
         """What a candidate with an all-zero pooled xcn1 (xcn2) contributes: the activations after the second
         layer of xcn1lin (xcn2lin) on a zero row, and the mix layer of the two — computed by the SAME
         kernels on a one-row zero input, so a skipped row gets bit for bit what it would have computed.
         Cached on the parameter versions."""
-        plist = getattr(self, "_zc_params", None)
-        if plist is None:             # (walking the module tree every batch cost 60 us of host time)
-            plist = self._zc_params = [p for seq in (self.xcn1lin, self.xcn2lin) for p in seq.parameters()]
-        self._mix_coef()
-        key = (tuple(p._version for p in plist), self._coef_key)
-        if getattr(self, "_zc_key", None) != key:
+        def make():
             z1 = torch.zeros(1, H, device=dev)
             t = torch.empty(2, 1, H, device=dev)
             c2 = torch.empty(1, 2 * H, device=dev)
@@ -902,122 +956,74 @@ class _CNPredictorBase(nn.Module):
             w3, b3 = self._mix_weight(sa[2][0], sb[2][0])
             zc = torch.empty(1, H, device=dev)
             ops.linear_grouped([dict(x=c2, weight=w3, bias=b3, relu=False, y=zc)], 2 * H, H)
-            self._zc = (c2[:, :H].contiguous(), c2[:, H:].contiguous(), zc)
-            self._zc_key = key
-        return self._zc
+            return c2[:, :H].contiguous(), c2[:, H:].contiguous(), zc
+        plist = self._params_of("zc_params", self.xcn1lin, self.xcn2lin)
+        self._mix_coef()
+        return self._cached("zc", (tuple(p._version for p in plist), self._cache["coef"][0]), make)
 
-    def _heads_skipping(self, xcn1, xcn2, xij, cls):
-        """The heads on class-major rows (ops.class_order): layer 1-2 of xcn1lin only where cnt1 > 0, of
-        xcn2lin only where cnt2 > 0, the mix layer only where either is, the constants elsewhere; `lin`
-        scatters the scores back to batch order."""
+    def _heads_layered(self, xcn1, xcn2, xij, cls):
+        """The three branches layer by layer instead of branch by branch: launch 1 = first layers of xcn1lin / xcn2lin /
+        xijlin, launch 2 = their second layers (the two pooled branches write the halves of one [B, 2H] buffer), launch 3 =
+        one K = 2H Linear that is both third layers and the branch mix, with β · xijlin(x_i ⊙ x_j) as its addend; then `lin`.
+        ``cls`` (ops.class_order): the rows are class-major — layers 1-2 of xcn1lin only where cnt1 > 0, of xcn2lin only where
+        cnt2 > 0, the mix layer only where either is, the constants of a zero row elsewhere, and `lin` scatters the scores
+        back to batch order.  ``cls`` = None: every row; None is returned unless the three inputs lie back to back in memory
+        (as the pooling leaves them), and the per-branch walk runs instead."""
         B, H = xij.shape
-        order2, _, r = cls
-        sa, sb, sx = self._heads_plan(H)
-        a2c, b2c, zc = self._zero_consts(sa, sb, H, xij.device)
+        lay = self._layout(H)
+        sa, sb, sx = lay.sa, lay.sb, lay.sx
+        dev, two, R = xij.device, len(sx) == 2, ops
+        if cls is None:
+            rows = B * H * 4
+            if B == 0 or not (xcn1.is_contiguous() and xcn2.data_ptr() == xcn1.data_ptr() + rows
+                              and xij.data_ptr() == xcn2.data_ptr() + rows):
+                return None
+            order2, r = None, [None] * ops.CLASS_RANGES          # (no row range: every row)
+        else:
+            order2, _, r = cls
+            a2c, b2c, zc = self._zero_consts(sa, sb, H, dev)
         coef = self._mix_coef()
-        dev = xij.device
-        two = len(sx) == 2
-        y0 = ops.buf(self._ws, "y0", (B, H), torch.float32, dev)
+        y0 = ops.buf(self._ws, "y0", (B, H), torch.float32, dev)           # β · xijlin(x_i ⊙ x_j)
         z = ops.buf(self._ws, "z", (B, H), torch.float32, dev)
         t1 = ops.buf(self._ws, "t1", (3 if two else 2, B, H), torch.float32, dev)
         cat = ops.buf(self._ws, "cat", (B, 2 * H), torch.float32, dev)
-        R = ops
 
         def xij_last(x, st):         # beta * xijlin(..): into y0 where the mix layer runs, + zc straight into z elsewhere
+            if cls is None:
+                return [_grp(x, st, y0, scale=coef[2:3])]
             return [_grp(x, st, y0, scale=coef[2:3], row_range=r[R.R_ANY]),
                     _grp(x, st, z, scale=coef[2:3], row_range=r[R.R_NONE], addend=zc, add_bcast=True)]
 
         # rows whose pooled xcn2 can be non-zero: cn5 orthogonalises cn2 against cn1 over the UNION pattern
         # (a cn1-only entry carries -t*inv2 when innerprod != 0), cn7 pools the raw cn2
-        b_rows = [R.R_ANY] if self._xcn2_on_union else [R.R_BOTH, R.R_CN2_ONLY]
+        b_rows = [R.R_ANY] if (self._xcn2_on_union or cls is None) else [R.R_BOTH, R.R_CN2_ONLY]
         g1 = [_grp(xcn1, sa[0], t1[0], row_range=r[R.R_CN1])] + [_grp(xcn2, sb[0], t1[1], row_range=r[q]) for q in b_rows]
         g1 += [_grp(xij, sx[0], t1[2])] if two else xij_last(xij, sx[0])
         ops.linear_grouped(g1, H, H)
-        g2 = [_grp(t1[0], sa[1], cat[:, :H], row_range=r[R.R_CN1])] + \
-             [_grp(t1[1], sb[1], cat[:, H:], row_range=r[q]) for q in b_rows]
+        g2 = [_grp(t1[0], sa[1], cat[:, :H], row_range=r[R.R_CN1])] + [_grp(t1[1], sb[1], cat[:, H:], row_range=r[q]) for q in b_rows]
         if two:
             g2 += xij_last(t1[2], sx[1])
         ops.linear_grouped(g2, H, H)
-        if not self._xcn2_on_union:
-            ops.fill_rows(cat[:, H:], b2c, r[R.R_CN1_ONLY])
-        ops.fill_rows(cat[:, :H], a2c, r[R.R_CN2_ONLY])
+        if cls is not None:
+            if not self._xcn2_on_union:
+                ops.fill_rows(cat[:, H:], b2c, r[R.R_CN1_ONLY])
+            ops.fill_rows(cat[:, :H], a2c, r[R.R_CN2_ONLY])
         w3, b3 = self._mix_weight(sa[2][0], sb[2][0])
         ops.linear_grouped([dict(x=cat, weight=w3, bias=b3, relu=False, y=z, addend=y0, row_range=r[R.R_ANY])], 2 * H, H)
         return _seq_eval(self.lin, z, y_row_map=order2)
 
-    def _heads_grouped(self, xcn1, xcn2, xij):
-        """The three branches layer by layer instead of branch by branch: launch 1 = first layers of
-        xcn1lin / xcn2lin / xijlin, launch 2 = their second layers (the two pooled branches write the
-        halves of one [B, 2H] buffer), launch 3 = one K = 2H Linear that is both third layers and the
-        branch mix, with the xij branch as its addend.  Returns None when the heads do not have that
-        shape (then the per-branch walk runs)."""
-        B, H = xij.shape
-        if H not in ops.LINEAR_WIDTHS or not ops.fast_linear or B == 0:
-            return None
-        rows = B * H * 4
-        if not (xcn1.is_contiguous() and xcn2.data_ptr() == xcn1.data_ptr() + rows
-                and xij.data_ptr() == xcn2.data_ptr() + rows):
-            return None
-        sa, sb, sx = _stages(self.xcn1lin, H), _stages(self.xcn2lin, H), _stages(self.xijlin, H)
-        if sa is None or sb is None or sx is None or len(sa) != 3 or len(sb) != 3 or len(sx) not in (1, 2):
-            return None
-        if sa[2][1] is not None or sa[2][2] or sb[2][1] is not None or sb[2][2]:
-            return None
-        coef = self._mix_coef()
-        dev = xij.device
-        y0 = ops.buf(self._ws, "y0", (B, H), torch.float32, dev)           # β · xijlin(x_i ⊙ x_j)
-        t1 = ops.buf(self._ws, "t1", (3 if len(sx) == 2 else 2, B, H), torch.float32, dev)
-        g1 = [_grp(xcn1, sa[0], t1[0]), _grp(xcn2, sb[0], t1[1]),
-              _grp(xij, sx[0], t1[2]) if len(sx) == 2 else _grp(xij, sx[0], y0, scale=coef[2:3])]
-        ops.linear_grouped(g1, H, H)
-        cat = ops.buf(self._ws, "cat", (B, 2 * H), torch.float32, dev)
-        g2 = [_grp(t1[0], sa[1], cat[:, :H]), _grp(t1[1], sb[1], cat[:, H:])]
-        if len(sx) == 2:
-            g2.append(_grp(t1[2], sx[1], y0, scale=coef[2:3]))
-        ops.linear_grouped(g2, H, H)
-        w3, b3 = self._mix_weight(sa[2][0], sb[2][0])
-        z = ops.buf(self._ws, "z", (B, H), torch.float32, dev)
-        ops.linear_grouped([dict(x=cat, weight=w3, bias=b3, relu=False, y=z, addend=y0)], 2 * H, H)
-        return z
-
     # ---- the whole head as one launch (ocn_heads_fused) -------------------------------------------------------------
-    def _fused_plan(self, H: int):
-        """The parsed head when it has the layout ocn_heads_fused evaluates (the drivers': 3-layer pooled heads, 1- or
-        2-layer xijlin, single-layer lin with the Linear(H, 1) tail, in_channels == hidden), else None."""
-        key = (H, ops.fused_heads)
-        if getattr(self, "_fplan_key", None) != key:
-            plan = None
-            if ops.fused_heads and H in ops.HEADS_WIDTHS:
-                sa, sb, sx = _stages(self.xcn1lin, H), _stages(self.xcn2lin, H), _stages(self.xijlin, H)
-                mods = [m for m in self.lin if not isinstance(m, (nn.Dropout, nn.Identity))]
-                sl = _stages(nn.Sequential(*mods[:-1]), H) if len(mods) >= 2 else None
-                tail = mods[-1] if mods else None
-
-                def pooled_ok(st):
-                    return (st is not None and len(st) == 3 and st[0][1] is None and st[0][2] and st[1][2]
-                            and st[2][1] is None and not st[2][2])
-                if (pooled_ok(sa) and pooled_ok(sb) and sx is not None and len(sx) in (1, 2) and sx[0][2]
-                        and (len(sx) == 1 or (sx[1][1] is None and not sx[1][2]))
-                        and sl is not None and len(sl) == 1 and sl[0][2]
-                        and isinstance(tail, nn.Linear) and tail.out_features == 1 and tail.in_features == H):
-                    lns = [sa[1][1], sb[1][1], sx[0][1], sl[0][1]]
-                    if all(l is None for l in lns) or (all(l is not None for l in lns) and len({l.eps for l in lns}) == 1):
-                        plan = (sa, sb, sx, sl[0], tail)
-            self._fplan, self._fplan_key = plan, key
-        return self._fplan
-
     def _fused_pack(self, H: int, dev):
         """Panels, folded output matrices, epilogue vectors and skipped-branch constants of ocn_heads_fused, cached on
         the parameter versions.  Folding (fp64, rounded once): the products of the reference without a non-linearity
         between them — third layers of xcn1lin / xcn2lin, second layer of xijlin, the mix of model.py:2436, lin[0]."""
-        sa, sb, sx, sl, tail = self._fused_plan(H)
-        plist = getattr(self, "_fp_params", None)
-        if plist is None:
-            plist = self._fp_params = [p for seq in (self.xcn1lin, self.xcn2lin, self.xijlin, self.lin) for p in seq.parameters()]
+        plist = self._params_of("fp_params", self.xcn1lin, self.xcn2lin, self.xijlin, self.lin)
         self._mix_coef()
-        key = (tuple(p._version for p in plist), tuple(p.data_ptr() for p in plist), self._coef_key, str(dev))
-        if getattr(self, "_fpack_key", None) == key:
-            return self._fpack
+        return self._cached("fpack", (tuple(p._version for p in plist), tuple(p.data_ptr() for p in plist),
+                                      self._cache["coef"][0], str(dev)), lambda: self._make_fused_pack(H, dev))
+
+    def _make_fused_pack(self, H: int, dev):
+        sa, sb, sx, sl, tail = self._fused_plan(H)
         with torch.no_grad():
             c = self._mix_coef().double()                       # [s(a0), s(a0) s(a1), beta]
             W0l, b0l = sl[0].weight.double(), sl[0].bias.double()
@@ -1056,7 +1062,6 @@ class _CNPredictorBase(nn.Module):
             scratch = ops.buf(self._ws, "heads_scratch", int(ops._lib.lib().ocn_heads_scratch_bytes(H)) // 4, torch.float32, dev)
             ops.heads_fused(z, z, z, pack, None, None, self._xcn2_on_union, scratch, dump=cpark)
             pack["cpark"] = cpark
-        self._fpack, self._fpack_key = pack, key
         return pack
 
     def _heads_fused(self, xcn1, xcn2, xij, cls):
@@ -1070,13 +1075,13 @@ class _CNPredictorBase(nn.Module):
         if (not self.training and not torch.is_grad_enabled() and xij.is_cuda and xij.dim() == 2 and xij.shape[0] > 0
                 and xij.is_contiguous() and xcn1.is_contiguous() and xcn2.is_contiguous()
                 and xcn1.shape == xij.shape and xij.shape[1] >= ops.fused_heads_min_width
-                and self._fused_plan(xij.shape[1]) is not None):
+                and self._layout(xij.shape[1]).fused):
             return self._heads_fused(xcn1, xcn2, xij, cls)
         if cls is not None:
-            return self._heads_skipping(xcn1, xcn2, xij, cls)
+            return self._heads_layered(xcn1, xcn2, xij, cls)
         if self.training or torch.is_grad_enabled() or not xij.is_cuda or xij.shape[-1] % 4:
             alpha = torch.sigmoid(self.alpha).cumprod(-1)
-            run = _seq_train if (xij.is_cuda and ops.train_linear) else (lambda seq, t: seq(t))
+            run = _runner(xij.is_cuda)
             xij = run(self.xijlin, xij)
             xcn1 = run(self.xcn1lin, xcn1)
             xcn2 = run(self.xcn2lin, xcn2)
@@ -1084,9 +1089,10 @@ class _CNPredictorBase(nn.Module):
         # eval under no_grad (the drivers' test()): same modules, same parameters, on the bf16x6 MFMA
         # Linear kernel with fused LayerNorm/ReLU epilogues.  With autograd on, the torch modules
         # above run instead so that the graph is recorded.
-        z = self._heads_grouped(xcn1, xcn2, xij)
-        if z is not None:
-            return _seq_eval(self.lin, z)
+        B, H = xij.shape
+        out = self._heads_layered(xcn1, xcn2, xij, None) if self._layout(H).layered else None
+        if out is not None:
+            return out
         xij = _seq_eval(self.xijlin, xij)
         xcn1 = _seq_eval(self.xcn1lin, xcn1)
         xcn2 = _seq_eval(self.xcn2lin, xcn2)
@@ -1100,10 +1106,7 @@ class CNLinkPredictorOringin(_CNPredictorBase):
 
     def multidomainforward(self, x, adj, cn1, cn2, tar_ei, filled1: bool = False,
                            cndropprobs: Iterable[float] = []):
-        st = self._exchange(fuse(cn1, cn2, tar_ei, self._scratch(x), adj=adj), x)
-        w = self._weights(st, None)
-        xcn1, xcn2, xij = self._pool(st, w, x)
-        return self._heads(x, xcn1, xcn2, xij, getattr(st, "cls", None))
+        return self._score(x, adj, cn1, cn2, tar_ei)
 
     def _weights(self, st, args):
         return st.weights_cn5(self.innerprod1(st))
@@ -1125,10 +1128,7 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
 
     def multidomainforward(self, x, adj, cn1, cn2, tar_ei, args, filled1: bool = False,
                            cndropprobs: Iterable[float] = []):
-        st = self._exchange(fuse(cn1, cn2, tar_ei, self._scratch(x), adj=adj), x)
-        w = self._weights(st, args)
-        xcn1, xcn2, xij = self._pool(st, w, x)
-        return self._heads(x, xcn1, xcn2, xij, getattr(st, "cls", None))
+        return self._score(x, adj, cn1, cn2, tar_ei, args)
 
     def _weights(self, st, args):
         dev = st.hist.device
@@ -1141,7 +1141,7 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
         full — has xcn2 = (A·h)[source], the same additions in the same order; the pooling copies that row instead of
         summing ~500 embedding rows again for each of the source's candidates (ocn_hip.h, ocn_cn_gather `rowsum`).  Only
         where it can pay: pattern route, A² at least half full."""
-        adj, t2 = st.adj, getattr(st, "t2", None)
+        adj, t2 = st.adj, st.t2
         if not ops.share_full_rows or st.walk or t2 is None or not x.is_cuda or x.dim() != 2 or int(self.polysecond) != 0:
             return None                        # (a non-trivial basis weights the cn2 entries: the row sum is not their pool)
         n = adj.size(0)
@@ -1151,7 +1151,7 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
         # computes a fresh h = model(x, adj) per evaluation, and the caching allocator hands the new h the freed one's
         # address (a data_ptr key then matched and the pooling copied the previous epoch's row sums).
         import weakref
-        hit = getattr(self, "_rowsum_cache", None)
+        hit = self._rowsum_cache
         if (hit is None or hit[0]() is not x or hit[1] != x._version or hit[2]() is not adj
                 or hit[3] != (x.data_ptr(), tuple(x.shape))):
             if torch.cuda.is_current_stream_capturing() and hit is not None:
@@ -1176,52 +1176,27 @@ class CNLinkPredictorbaselearnablation(_CNPredictorBase):
     measured against the chain).  An edge-sharded cn8 exchanges nothing."""
     _xcn2_on_union = False
 
-    def _fused_state(self, x, cn1, cn2, tar_ei, ws):
-        """The one-pass batch state where it applies (eval, no grad, pattern handles, a width the kernel has), else None."""
-        if (not ops.cn8_fused_eval or self.training or torch.is_grad_enabled() or not torch.is_tensor(x) or x.dim() != 2
-                or x.dtype != torch.float32 or x.shape[1] not in ops.LN_WIDTHS):
-            return None
-        from .utils import fuse8
-        st = fuse8(cn1, cn2, tar_ei, ws)
-        if st is not None:
-            st.cls, st._cls_decided = None, True       # (the class order needs the counts this pass itself produces: batch order)
-        return st
+    _exchanges_hist = False
+
+    def _batch_state(self, x, cn1, cn2, tar_ei, ws, adj):
+        """The one-pass state, pooled, where it applies (eval, no grad, pattern handles, a width the kernel has); else the
+        flag form of cn5 / cn7."""
+        if (ops.cn8_fused_eval and not self.training and not torch.is_grad_enabled() and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.float32 and x.shape[1] in ops.LN_WIDTHS):
+            from .utils import fuse8
+            st = fuse8(cn1, cn2, tar_ei, ws)
+            if st is not None:
+                st.pooled = st.pool(x.contiguous())
+                return st
+        return fuse(cn1, cn2, tar_ei, ws, adj=adj)
 
     def multidomainforward(self, x, adj, cn1, cn2, tar_ei, args, filled1: bool = False,
                            cndropprobs: Iterable[float] = []):
         getattr(args, "sum", None)                     # model.py:3332, 3388: read, multiplied into a matrix that is then dropped
-        st = self._fused_state(x, cn1, cn2, tar_ei, self._scratch(x))
-        if st is not None:
-            xcn1, xcn2, xij = st.pool(x.contiguous())
-            return self._heads(x, xcn1, xcn2, xij, None)
-        st = fuse(cn1, cn2, tar_ei, self._scratch(x), adj=adj)
-        xcn1, xcn2, xij = self._pool(st, self._weights(st, args), x)
-        return self._heads(x, xcn1, xcn2, xij, getattr(st, "cls", None))
+        return self._score(x, adj, cn1, cn2, tar_ei, args)
 
     def _weights(self, st, args):
         return ops.unit_weights(st.N, st.src.device)
-
-    def begin(self, x, adj, cn1, cn2, tar_ei, slot: int = 0, args=None):
-        """Phase A: the one-pass pooling (pattern handles), or the flag pass, the class order and the pooling with unit
-        weights (walk route).  No collective, sharded or not: there is nothing to exchange."""
-        if self.training or torch.is_grad_enabled():
-            raise RuntimeError("begin / finish is the no-grad scoring path: call .eval() under torch.no_grad()")
-        n_sets = max(2, int(ops.overlap_depth), int(ops.overlap_depth_small))
-        if len(getattr(self, "_ws_slots", ())) != n_sets:
-            self._ws_slots = [dict() for _ in range(n_sets)]
-        ws = self._ws_slots[slot % n_sets]
-        st = self._fused_state(x, cn1, cn2, tar_ei, ws)
-        if st is not None:
-            st.pooled = st.pool(x.contiguous())
-            return st, None, None
-        st = fuse(cn1, cn2, tar_ei, ws, adj=adj)
-        w = self._weights(st, args)
-        if ops.phase_a_extras:
-            self._class_order(st, x)
-            st.prepare_schedule(x.shape[1])
-            if ops.phase_a_pool:
-                st.pooled = self._pool(st, w, x)
-        return st, None, w
 
     def forward(self, x, adj, cn1, cn2, tar_ei, filled1: bool = False):
         return self.multidomainforward(x, adj, cn1, cn2, tar_ei, filled1, [])
@@ -1259,22 +1234,19 @@ class CNLinkPredictor3hopCNs(_CNPredictorBase):
             allreduce_hist(st.a.hist, self._shard_group, valued=False)
             allreduce_hist(st.b.hist, self._shard_group, valued=False)
         wa, wb, nip = st.weights(self.innerprod, sharded=self._sharded)
+        x = x.contiguous()
         if torch.is_grad_enabled():
             # autograd on (row f3): the pooling through _PoolFn3 (its transpose is ocn_cn_gather3_backward), the
             # heads through the modules / the MFMA Linear under autograd, as cn5 / cn7 do
-            x = x.contiguous()
             xcn1, xcn2, xcn3, xij = (_PoolFn3.apply(x, st, wa, wb, nip) if x.requires_grad else st.gather(wa, wb, nip, x))
-            alpha = torch.sigmoid(self.alpha).cumprod(-1)
-            run = _seq_train if (xij.is_cuda and ops.train_linear) else (lambda seq, t: seq(t))
-            z = (alpha[0] * run(self.xcn1lin, xcn1) + alpha[1] * run(self.xcn2lin, xcn2)
-                 + alpha[2] * run(self.xcn3lin, xcn3) + self.beta * run(self.xijlin, xij))
-            return run(self.lin, z)
-        xcn1, xcn2, xcn3, xij = st.gather(wa, wb, nip, x.contiguous())
-        with torch.no_grad():
-            alpha = torch.sigmoid(self.alpha).cumprod(-1)
-            z = (alpha[0] * _seq_eval(self.xcn1lin, xcn1) + alpha[1] * _seq_eval(self.xcn2lin, xcn2)
-                 + alpha[2] * _seq_eval(self.xcn3lin, xcn3) + self.beta * _seq_eval(self.xijlin, xij))
-            return _seq_eval(self.lin, z)
+            run = _runner(xij.is_cuda)
+        else:
+            xcn1, xcn2, xcn3, xij = st.gather(wa, wb, nip, x)
+            run = _seq_eval
+        alpha = torch.sigmoid(self.alpha).cumprod(-1)
+        z = (alpha[0] * run(self.xcn1lin, xcn1) + alpha[1] * run(self.xcn2lin, xcn2)
+             + alpha[2] * run(self.xcn3lin, xcn3) + self.beta * run(self.xijlin, xij))
+        return run(self.lin, z)
 
     def forward(self, x, adj, cn1, cn2, cn3, tar_ei, args=None):
         return self.multidomainforward(x, adj, cn1, cn2, cn3, tar_ei, args)

@@ -19,13 +19,13 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .utils import PermIterator
+from .utils import PermIterator, scratch_set_count
 
 
 def _graphed(predictor, h, adj, make_handles, batch_size, args, n_batches):
     """A ``GraphedPhases`` for this loop where replaying pays: ``ops.graph_loops``, a GPU, an unsharded predictor and enough
     batches to amortise two eager uses and one capture per scratch set."""
-    if not (ops.graph_loops and h.is_cuda and not getattr(predictor, "_sharded", False)):
+    if not (ops.graph_loops and h.is_cuda and not predictor._sharded):
         return None
     g = GraphedPhases(predictor, h, adj, make_handles, batch_size, args)
     return g if n_batches >= ops.graph_loops_min_batches_per_set * g.n_sets else None
@@ -230,14 +230,14 @@ class GraphedPhases:
 
     def __init__(self, predictor, h: Tensor, adj, make_handles, batch_size: int, args=None):
         self.pred, self.h, self.adj, self.handles, self.B, self.args = predictor, h, adj, make_handles, int(batch_size), args
-        self.n_sets = max(2, int(ops.overlap_depth), int(ops.overlap_depth_small))
+        self.n_sets = scratch_set_count()
         self.slots: dict = {}
 
     def begin(self, it: int, e: Tensor):
         """``e``: the batch's candidate ids, [2, b] (any strides).  Returns a token for ``finish``."""
         b = int(e.shape[1])
         s = it % self.n_sets
-        if b != self.B or getattr(self.pred, "_sharded", False):
+        if b != self.B or self.pred._sharded:
             e = e.contiguous()
             return ("eager", self.pred.begin(self.h, self.adj, *self.handles(e), e, slot=s, args=self.args), None)
         sl = self.slots.get(s)

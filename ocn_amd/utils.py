@@ -86,11 +86,32 @@ def _transposed(adj: SparseTensor, undirected: bool):
     return at._rowptr, at._col, adj._nds_t
 
 
-class CNState:
+def scratch_set_count() -> int:
+    """Scratch sets a two-phase scoring loop rotates through (``predictor.begin``'s ``slot``, ``pipeline.GraphedPhases``)."""
+    return max(2, int(ops.overlap_depth), int(ops.overlap_depth_small))
+
+
+class _BatchState:
+    """Every field the predictors and the scoring loops read of a batch state, with its "absent" value: a constructor
+    assigns what its route produces, the rest reads as absent."""
+    adj = ws = src = dst = order = cnt1 = cnt2 = None
+    B = N = 0
+    walk = False
+    cls = pooled = None         # set by the predictor: class-major rows (ops.class_order; None = batch order), phase A's pools
+    _cls_decided = False        # ... and whether it has decided that row order
+
+
+class CNState(_BatchState):
     """Device state of one candidate batch after the intersection kernel: where each batch row
     starts (``off``), one flag byte per neighbour of the source node (bit 0: cn1 entry, bit 1: cn2
     entry), the walk counts of the valued route, the packed per-column histograms
     {n1, n2, n_union, walks}, and the integer CN counts."""
+    t2 = None
+    off = flags = wc = hist = status = scal = None
+    rec = sched = None          # per-slot records and group costs the pattern route leaves for the pooling
+    _hist_live = False          # the histogram is consumed (turned into weights in place) exactly once
+    _sched_ready = False        # the pooling's visiting order was formed in phase A (prepare_schedule)
+    sharded, shard_group = False, None
 
     def __init__(self, adj: SparseTensor, t1: Optional[SparseTensor], t2: Optional[SparseTensor],
                  tarei: Tensor, walk: bool = False, ws: Optional[dict] = None):
@@ -137,7 +158,6 @@ class CNState:
         if tuple(cn1.sizes()) != (st.B, st.N) or tuple(cn2.sizes()) != (st.B, st.N):
             raise ValueError("cn1 / cn2 must be [B, N] with B = tar_ei.shape[1], N = adj.size(1)")
         ops.check_edges(st.src, st.dst, adj.size(0), adj.size(0))
-        st.order = None
         st.off = ops.edge_offsets(adj._rowptr, st.src)
         total = int(st.off[-1])
         st.flags = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
@@ -182,10 +202,9 @@ class CNState:
         the batch's (A, A, A²) pass, which has then checked the edges; standing alone the state forms its own."""
         _check_hop3(adj, adj2, tarei)
         st = cls.__new__(cls)
-        st.adj, st.walk, st.t2, st.ws = adj, False, None, None
+        st.adj = adj
         st.src, st.dst = _endpoints(tarei)
         st.B, st.N = st.src.numel(), adj.size(1)
-        st.rec = st.sched = st.wc = st.cnt2 = None
         if off is None:
             ops.check_edges(st.src, st.dst, adj.size(0), adj.size(0))
             off = ops.edge_offsets(adj._rowptr, st.src)
@@ -198,6 +217,9 @@ class CNState:
         st.scal = torch.zeros(4, dtype=torch.int32, device=st.src.device)
         st._hist_live = True
         return st
+
+    def mark_sharded(self, group) -> None:
+        self.sharded, self.shard_group = True, group       # one rank's slice: histograms are summed over ``group``
 
     def check_status(self) -> None:
         """Raise for the error bits the intersection pass left for this batch (one host sync; ocn_hip.h: OCN_ST_*)."""
@@ -219,7 +241,7 @@ class CNState:
             # innerprod != 0 (a trained checkpoint): S2 summed entry by entry in the reference's order
             run = lambda init: ops.cn_colsum_exact(self.adj._rowptr, self.adj._col, self.src, self.off, self.flags, None,
                                                    self.wc, self.hist, innerprod, scal, self.ws, s2_init=init)[0]
-            if getattr(self, "sharded", False):
+            if self.sharded:
                 from .dist import ring_colsum          # an edge shard continues the chains of the ranks before it
                 s2 = ring_colsum(run, self.hist.shape[0], self.hist.device, self.shard_group)
             else:
@@ -239,13 +261,13 @@ class CNState:
         return ops.cn_gather(self.adj._rowptr, self.adj._col, self.src, self.dst, self.off,
                              self.flags, self.wc, weights, h, order=self.order if order is None else order,
                              max_row_len=self.adj.max_rowcount(), wsd=self.ws, out_row=out_row,
-                             cnt1=self.cnt1, cnt2=self.cnt2, rec=getattr(self, "rec", None) if order is None else None,
-                             sched=getattr(self, "sched", None) if order is None else None,
-                             rowsum=None if self.walk else rowsum, sched_ready=getattr(self, "_sched_ready", False))
+                             cnt1=self.cnt1, cnt2=self.cnt2, rec=self.rec if order is None else None,
+                             sched=self.sched if order is None else None,
+                             rowsum=None if self.walk else rowsum, sched_ready=self._sched_ready)
 
     def prepare_schedule(self, H: int) -> None:
         """Phase A of a scoring loop: the pooling's visiting order needs the intersection pass only."""
-        if H == 256 and getattr(self, "sched", None) is not None and getattr(self, "rec", None) is not None:
+        if H == 256 and self.sched is not None and self.rec is not None:
             self._sched_ready = ops.gather_schedule(self.sched, self.B)
 
     def gather_backward(self, weights: Tensor, h: Tensor, g1: Tensor, g2: Tensor, g3: Tensor) -> Tensor:
@@ -433,10 +455,12 @@ def fuse(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None, adj: Optional[Spar
     return CNState(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, ws=ws)
 
 
-class CN8State:
+class CN8State(_BatchState):
     """A cn8 batch on the pattern route: cn8 pools without column weights, so the batch needs no flags, histogram or
     weights — only the operands of ``ops.cn8_pool`` (intersection and pooling in one pass).  ``pool(h)`` runs it and leaves
-    the integer CN counts in ``cnt1`` / ``cnt2``."""
+    the integer CN counts in ``cnt1`` / ``cnt2`` — too late for a class order: born "batch order, decided"."""
+    t1 = t2 = None
+    _cls_decided = True
 
     def __init__(self, adj: SparseTensor, t1: SparseTensor, t2: SparseTensor, tarei: Tensor, ws: Optional[dict] = None):
         self.src, self.dst = _endpoints(tarei)
@@ -445,8 +469,6 @@ class CN8State:
                 raise ValueError("adjoverlap: adjacency sizes differ")    # utils.py:164 assert
         self.adj, self.t1, self.t2, self.ws = adj, t1, t2, ws
         self.B, self.N = self.src.numel(), adj.size(1)
-        self.walk = False
-        self.cnt1 = self.cnt2 = self.order = None
 
     def pool(self, h: Tensor):
         """(xcn1, xcn2, x_i * x_j) of the batch; sets ``cnt1`` / ``cnt2``."""

@@ -1140,7 +1140,7 @@ def test_phase_a_carries_weights_class_order_and_schedule(hiplib):
 
                     def begin(it):
                         tok = pred.begin(x, adj, *handles(batches[it]), batches[it], slot=it)
-                        seen.append((tok[2] is not None, getattr(tok[0], "_cls_decided", False), getattr(tok[0], "_sched_ready", False)))
+                        seen.append((tok[2] is not None, tok[0]._cls_decided, tok[0]._sched_ready))
                         return tok
                     outs = [o.clone() for o in overlapped_steps(begin, lambda tok: pred.finish(x, tok), len(batches), batch=B)]
                 finally:
@@ -1665,7 +1665,7 @@ def test_cn7_full_rows_share_the_row_sum(hiplib, monkeypatch, H, B, lnnn):
             return pred(x, adj, adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e), e, args)
     monkeypatch.setattr(ops, "share_full_rows", False)
     ref = score()
-    assert getattr(pred, "_rowsum_cache", None) is None
+    assert pred._rowsum_cache is None
     monkeypatch.setattr(ops, "share_full_rows", True)
     got = score()
     assert pred._rowsum_cache is not None and torch.equal(got, ref)
