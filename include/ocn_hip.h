@@ -45,7 +45,8 @@ extern "C" {
  *    _fill, ocn_bitrows_remove_workspace_bytes, ocn_bitrows_remove (edge removal from a resident graph); ocn_spmm_csr_rows,
  *    ocn_rows_neighbourhood_workspace_bytes, ocn_rows_neighbourhood, ocn_bitlist_count / _fill (refreshing the node embeddings
  *    after an edge update: only the rows that can have changed); ocn_cn3_flags (the (A, A³) pass of cn6 from A and the bit rows
- *    of A², without a stored A³). */
+ *    of A², without a stored A³); ocn_cn_flags_pair_min_batch (the intersection pass takes two slots per wave at large batches;
+ *    same bits). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -609,6 +610,13 @@ int ocn_spgemm_pattern_fill(const int64_t* rowptrA, const int32_t* colA, int64_t
 /* Up to this many columns ocn_cn_flags keeps a workgroup's column histogram in LDS and reads T2's row lengths beside its bit rows
  * (so T2 must come with its row pointers there). */
 int32_t ocn_cn_flags_small_graph_cols(void);
+/* On larger graphs, batches of at least `min_rows` candidates run the intersection pass with TWO consecutive processing slots
+ * per wave (cn_flags.hip: NS = 2): both slots' records, target rows, chunks of N(src) and probes are in flight together, so a
+ * CU holds twice the slots at the same registers and LDS.  Every output is bit for bit what the one-slot form writes
+ * (tests/test_flags_pairs_gpu.py).  Smaller batches and the small-graph form (LDS histogram) keep one slot per wave: half as
+ * many waves must still fill the chip several times over.  Sets the bound (process-wide; default 32768) and returns the
+ * previous one; a negative argument only queries. */
+int64_t ocn_cn_flags_pair_min_batch(int64_t min_rows);
 int ocn_spgemm_bit_rows(const int64_t* rowptrA, const int32_t* colA, int64_t n_rows, const int64_t* rowptrB, const int32_t* colB,
                         int64_t n_colsB, const int64_t* rows, int64_t n_req, int32_t* done, uint32_t* bitmap,
                         int64_t bm_stride_words, void* stream);

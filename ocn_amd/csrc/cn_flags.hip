@@ -53,7 +53,15 @@ __device__ __forceinline__ bool lanes_have(int32_t t, int32_t key) {
   return __shfl(t, pos, OCN_WAVE) == key;
 }
 
-template <bool HAS_T2, bool LH, bool RECIN>
+// NS: slots per wave.  1: as above.  2 (large graphs at large batches, cn_flags_launch): wave g of workgroup b owns the
+// consecutive slots 8b + 2g and 8b + 2g + 1 and makes every trip for both at once — both records, both target rows, both
+// chunks of N(src), both probes are issued before the first of them is waited for — so that a CU holds 64 slots in flight
+// where its 32 waves held 32.  Slots are in source order: a pair mostly shares its source (one colA load serves both, and
+// one histogram add carries both increments).  The pair shares the wave's LDS slices: a long target row takes the whole slice
+// when the partner's row sits in registers (or needs none), its own half when it fits there, and is searched in memory
+// otherwise.  A workgroup is then NS schedule groups (SCHED_GROUP slots = GPB / NS waves each).  Every output is what NS = 1
+// writes.
+template <bool HAS_T2, bool LH, bool RECIN, int NS>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
     const i64* __restrict__ rowptrT1, const int32_t* __restrict__ colT1,
@@ -63,7 +71,9 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     i64 n_cols, const i64* __restrict__ off, uint8_t* __restrict__ flags, i64 cap,
     u64* __restrict__ hist, int32_t* __restrict__ cnt1, int32_t* __restrict__ cnt2,
     int32_t* __restrict__ status, u64* rec, int32_t* __restrict__ gcost) {
-  constexpr int GPB = OCN_WPB;
+  constexpr int GPB = OCN_WPB, SPB = GPB * NS;                  // waves, slots per workgroup
+  constexpr int T1_PART = T1_CAP / NS, T2_PART = OCN_WAVE / NS;  // a slot's share of its wave's slices when both slots need them
+  static_assert(NS == 1 || (NS == 2 && !LH), "slot pairs: large-graph forms only");
   __shared__ int s_cost[2][GPB];
   __shared__ int32_t s_t1[GPB][T1_CAP];
   __shared__ int32_t s_t2[GPB][OCN_WAVE];
@@ -77,105 +87,187 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     __syncthreads();
   }
   int par = 0;
-  for (i64 e0 = (i64)blockIdx.x * GPB; e0 < B; e0 += (i64)gridDim.x * GPB, par ^= 1) {
-    const i64 slot = e0 + g;                  // processing slot; `order` maps it to a batch row
-    const bool act = slot < B;
-    i64 e = 0, i = 0, j = 0, a0 = 0, da = 0, b0 = 0, db = 0, c0 = 0, dc = 0, base = 0;
-    const unsigned* bm_row = nullptr;         // bit row of dst in T2, when T2 comes with a dense bitmap
-    const unsigned* bm1_row = nullptr;        // ... and in T1 (small dense graphs: a membership test is one probe)
-    if (act) {
-      if (RECIN) {
-        const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(rec + 4 * slot);
-        const ulonglong2 ra = rp[0], rb = rp[1];
-        e = wave_uniform((i64)ra.x);
-        i = wave_uniform((i64)(ra.y & 0xffffffffull)); j = wave_uniform((i64)(ra.y >> 32));
-        a0 = wave_uniform((i64)(rb.x & ((1ull << REC_LEN_SHIFT) - 1))); da = wave_uniform((i64)(rb.x >> REC_LEN_SHIFT));
-        base = wave_uniform((i64)rb.y);
-      } else {
-        e = order ? order[slot] : slot;
-        i = src[e]; j = dst[e];
-        a0 = rowptrA[i]; da = rowptrA[i + 1] - a0;
-        base = off[e];
-      }
-      if (bmT1) bm1_row = bmT1 + j * bm1_stride;
-      else { b0 = rowptrT1[j]; db = rowptrT1[j + 1] - b0; }
-      if (HAS_T2) {
-        if (bmT2) bm_row = bmT2 + j * bm_stride;
-        if (rowptrT2 && (LH || !bmT2)) { c0 = rowptrT2[j]; dc = rowptrT2[j + 1] - c0; }   // (small graphs with bit rows too: a FULL row — a dense A², ogbl-ddi —
-                                                                                  // needs no probe at all; on large graphs the two loads would only lengthen the chain)
-      }
-      if (void_batch) { da = 0; db = 0; dc = 0; base = 0; }
+  for (i64 e0 = (i64)blockIdx.x * SPB; e0 < B; e0 += (i64)gridDim.x * SPB, par ^= 1) {
+    // Every per-slot quantity is an [NS] array, every loop over s fully unrolled; within a phase the loads of all slots are
+    // issued before the first use.  A slot past the end of the batch (an odd tail) is an empty one: no separate path.
+    i64 slot[NS];                             // processing slots; `order` maps one to a batch row
+    bool act[NS];
+    i64 e[NS], i[NS], j[NS], a0[NS], da[NS], b0[NS], db[NS], c0[NS], dc[NS], base[NS];
+    const unsigned* bm_row[NS];               // bit row of dst in T2, when T2 comes with a dense bitmap
+    const unsigned* bm1_row[NS];              // ... and in T1 (small dense graphs: a membership test is one probe)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      slot[s] = e0 + NS * g + s;
+      act[s] = slot[s] < B;
+      e[s] = i[s] = j[s] = a0[s] = da[s] = b0[s] = db[s] = c0[s] = dc[s] = base[s] = 0;
+      bm_row[s] = bm1_row[s] = nullptr;
     }
-    // the target row: up to 64 entries stay in the wave's registers, one per lane; a longer one, up to T1_CAP, goes to
-    // this wave's LDS slice; beyond that the search runs in memory
-    const bool t1_reg = db <= OCN_WAVE, t1_lds = db <= T1_CAP;
-    int32_t t1 = 0x7fffffff;
-    if (t1_reg) { if (gl < db) t1 = colT1[b0 + gl]; }
-    else if (t1_lds)
-      for (i64 q = gl; q < db; q += OCN_WAVE) s_t1[g][q] = colT1[b0 + q];
-    const bool t2_full = HAS_T2 && rowptrT2 && dc == n_cols;   // a full row (dense A², e.g. ddi) contains every column
-    if (HAS_T2 && !t2_full && !bmT2) {
-      if (dc > OCN_WAVE) s_t2[g][gl] = colT2[c0 + (((i64)gl * dc) >> 6)];      // a 64-point sample of the long row
-      else if (gl < dc) s_t2[g][gl] = colT2[c0 + gl];
+    // NS > 1: the slots' records are consecutive, so lane l loads word l of them — ONE load for all slots, in two registers
+    // (a 32-byte load per slot would hold sixteen) — and a field is read from its lane
+    u64 recw = 0;
+    if (RECIN && NS > 1 && gl < 4 * NS && slot[0] + gl / 4 < B) recw = rec[4 * slot[0] + gl];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      if (act[s]) {
+        if (RECIN) {
+          u64 w[4];
+          if (NS == 1) {
+            const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(rec + 4 * slot[s]);
+            const ulonglong2 ra = rp[0], rb = rp[1];
+            w[0] = ra.x; w[1] = ra.y; w[2] = rb.x; w[3] = rb.y;
+          } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              w[q] = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)recw, 4 * s + q) |
+                     ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(recw >> 32), 4 * s + q) << 32);
+          }
+          e[s] = wave_uniform((i64)w[0]);
+          i[s] = wave_uniform((i64)(w[1] & 0xffffffffull)); j[s] = wave_uniform((i64)(w[1] >> 32));
+          a0[s] = wave_uniform((i64)(w[2] & ((1ull << REC_LEN_SHIFT) - 1))); da[s] = wave_uniform((i64)(w[2] >> REC_LEN_SHIFT));
+          base[s] = wave_uniform((i64)w[3]);
+        } else {                              // (no records: small batches and training — a slot's chain runs on its own)
+          e[s] = order ? order[slot[s]] : slot[s];
+          i[s] = src[e[s]]; j[s] = dst[e[s]];
+          a0[s] = rowptrA[i[s]]; da[s] = rowptrA[i[s] + 1] - a0[s];
+          base[s] = off[e[s]];
+        }
+        if (bmT1) bm1_row[s] = bmT1 + j[s] * bm1_stride;
+        else { b0[s] = rowptrT1[j[s]]; db[s] = rowptrT1[j[s] + 1] - b0[s]; }
+        if (HAS_T2) {
+          if (bmT2) bm_row[s] = bmT2 + j[s] * bm_stride;
+          if (rowptrT2 && (LH || !bmT2)) { c0[s] = rowptrT2[j[s]]; dc[s] = rowptrT2[j[s] + 1] - c0[s]; }   // (small graphs with bit rows too: a FULL row — a dense A², ogbl-ddi —
+                                                                                  // needs no probe at all; on large graphs the two loads would only lengthen the chain)
+        }
+        if (void_batch) { da[s] = 0; db[s] = 0; dc[s] = 0; base[s] = 0; }
+      }
+    // the target row: up to 64 entries stay in the wave's registers, one per lane; a longer one, up to T1_CAP (NS = 2: while
+    // the partner's sits in registers, else up to T1_PART in the slot's own part), goes to this wave's LDS slice; beyond that
+    // the search runs in memory
+    bool t1_reg[NS], t1_lds[NS], t2_full[NS], t2_lds[NS];
+    int t1_at[NS], t2_at[NS];
+    int32_t t1[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int o = (s + 1) % NS;             // the partner
+      const bool whole1 = NS == 1 || db[o] <= OCN_WAVE;
+      t1_reg[s] = db[s] <= OCN_WAVE; t1_lds[s] = db[s] <= (whole1 ? T1_CAP : T1_PART);
+      t1_at[s] = whole1 ? 0 : s * T1_PART;
+      t1[s] = 0x7fffffff;
+      if (t1_reg[s]) { if (gl < db[s]) t1[s] = colT1[b0[s] + gl]; }
+      else if (t1_lds[s])
+        for (i64 q = gl; q < db[s]; q += OCN_WAVE) s_t1[g][t1_at[s] + q] = colT1[b0[s] + q];
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int o = (s + 1) % NS;
+      t2_full[s] = HAS_T2 && rowptrT2 && dc[s] == n_cols;   // a full row (dense A², e.g. ddi) contains every column
+      const bool whole2 = NS == 1 || (HAS_T2 && rowptrT2 && dc[o] == n_cols) || dc[o] == 0;
+      t2_lds[s] = whole2 || dc[s] <= T2_PART;
+      t2_at[s] = whole2 ? 0 : s * T2_PART;
+      if (HAS_T2 && !t2_full[s] && !bmT2 && t2_lds[s]) {
+        if (dc[s] > OCN_WAVE) s_t2[g][gl] = colT2[c0[s] + (((i64)gl * dc[s]) >> 6)];      // a 64-point sample of the long row (it has the whole slice)
+        else if (gl < dc[s]) s_t2[g][t2_at[s] + gl] = colT2[c0[s] + gl];
+      }
     }
     wave_lds_sync();
-    const bool fits = base + da <= cap;
-    int c1 = 0, c2 = 0;
-    for (i64 p0 = 0; p0 < da; p0 += OCN_WAVE) {      // (wave-uniform trips: lanes_have needs every lane)
+    bool fits[NS];
+    int c1[NS], c2[NS];
+    i64 da_max = da[0];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      fits[s] = base[s] + da[s] <= cap;
+      c1[s] = c2[s] = 0;
+      if (s > 0 && da[s] > da_max) da_max = da[s];
+    }
+    const bool same = NS > 1 && i[0] == i[NS - 1];   // one source (wave-uniform): one row of A, one chunk load, one histogram add
+    for (i64 p0 = 0; p0 < da_max; p0 += OCN_WAVE) {      // (wave-uniform trips: lanes_have needs every lane)
       const i64 p = p0 + gl;
-      const bool in = p < da;
-      const int32_t k = in ? colA[a0 + p] : 0;
-      unsigned w2 = 0;
-      if (HAS_T2 && bmT2 && !t2_full && in) w2 = bm_row[k >> 5];    // one probe, in flight while the cn1 search runs
-      bool f1;
-      if (bmT1) f1 = in && ((bm1_row[k >> 5] >> (k & 31)) & 1u);
-      else if (t1_reg) f1 = lanes_have(t1, k) && in;
-      else f1 = in && (t1_lds ? sorted_has(&s_t1[g][0], db, k) : sorted_has(colT1 + b0, db, k));
-      bool f2 = false;
-      if (HAS_T2 && in) {
-        if (t2_full) f2 = true;
-        else if (bmT2) f2 = (w2 >> (k & 31)) & 1u;
-        else f2 = dc > OCN_WAVE ? sampled_has(&s_t2[g][0], colT2 + c0, dc, k) : sorted_has(&s_t2[g][0], dc, k);
+      bool in[NS], f1[NS], f2[NS];
+      int32_t k[NS];
+      unsigned w2[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        in[s] = p < da[s];
+        if (s > 0 && same) k[s] = k[0];       // (unused where !in[s]: an empty partner of the same source id)
+        else k[s] = in[s] ? colA[a0[s] + p] : 0;
       }
-      if (fits && in) flags[base + p] = (uint8_t)((f1 ? OCN_F_CN1 : 0u) | (f2 ? OCN_F_CN2 : 0u));
-      if (f1 | f2) {
-        const u64 inc = (u64)f1 | ((u64)f2 << HF_BITS) | (1ull << (2 * HF_BITS));
-        if (LH) atomicAdd(s_hist + k, inc); else atomicAdd(hist + 2 * (i64)k, inc);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        w2[s] = 0;
+        if (HAS_T2 && bmT2 && !t2_full[s] && in[s]) w2[s] = bm_row[s][k[s] >> 5];    // one probe, in flight while the cn1 search runs
       }
-      c1 += f1;
-      c2 += f2;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (bmT1) f1[s] = in[s] && ((bm1_row[s][k[s] >> 5] >> (k[s] & 31)) & 1u);
+        else if (t1_reg[s]) f1[s] = lanes_have(t1[s], k[s]) && in[s];
+        else f1[s] = in[s] && (t1_lds[s] ? sorted_has(&s_t1[g][t1_at[s]], db[s], k[s]) : sorted_has(colT1 + b0[s], db[s], k[s]));
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        f2[s] = false;
+        if (HAS_T2 && in[s]) {
+          if (t2_full[s]) f2[s] = true;
+          else if (bmT2) f2[s] = (w2[s] >> (k[s] & 31)) & 1u;
+          else if (!t2_lds[s]) f2[s] = sorted_has(colT2 + c0[s], dc[s], k[s]);
+          else f2[s] = dc[s] > OCN_WAVE ? sampled_has(&s_t2[g][0], colT2 + c0[s], dc[s], k[s]) : sorted_has(&s_t2[g][t2_at[s]], dc[s], k[s]);
+        }
+        if (fits[s] && in[s]) flags[base[s] + p] = (uint8_t)((f1[s] ? OCN_F_CN1 : 0u) | (f2[s] ? OCN_F_CN2 : 0u));
+      }
+      if (NS > 1 && same) {                   // k[s] == k[0]: the column's increments of all slots in one add
+        u64 inc = 0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) inc += (u64)f1[s] | ((u64)f2[s] << HF_BITS) | ((u64)(f1[s] | f2[s]) << (2 * HF_BITS));
+        if (inc) atomicAdd(hist + 2 * (i64)k[0], inc);
+      } else {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+          if (f1[s] | f2[s]) {
+            const u64 inc = (u64)f1[s] | ((u64)f2[s] << HF_BITS) | (1ull << (2 * HF_BITS));
+            if (LH) atomicAdd(s_hist + k[s], inc); else atomicAdd(hist + 2 * (i64)k[s], inc);
+          }
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        c1[s] += __popcll(__ballot(f1[s]));   // (wave-uniform counts)
+        c2[s] += __popcll(__ballot(f2[s]));
+      }
     }
     wave_lds_sync();                          // (the next slot's row may overwrite this one's)
 #pragma unroll
-    for (int o = OCN_WAVE / 2; o > 0; o >>= 1) {
-      c1 += __shfl_xor(c1, o, OCN_WAVE);
-      c2 += __shfl_xor(c2, o, OCN_WAVE);
-    }
-    if (act && gl == 0) {
-      cnt1[e] = c1;
-      if (cnt2) cnt2[e] = c2;
-      if (rec) {                              // what the pooling needs to know about this slot, in ONE 32-byte record
-        u64* r = rec + 4 * slot;
-        if (!RECIN) {
-          r[0] = (u64)e;
-          r[1] = (u64)i | ((u64)j << 32);
+    for (int s = 0; s < NS; ++s)
+      if (act[s] && gl == 0) {
+        cnt1[e[s]] = c1[s];
+        if (cnt2) cnt2[e[s]] = c2[s];
+        if (rec) {                              // what the pooling needs to know about this slot, in ONE 32-byte record
+          u64* r = rec + 4 * slot[s];
+          if (!RECIN) {
+            r[0] = (u64)e[s];
+            r[1] = (u64)i[s] | ((u64)j[s] << 32);
+          }
+          if (!RECIN || void_batch) r[2] = (u64)a0[s] | ((u64)da[s] << REC_LEN_SHIFT);
+          r[3] = (u64)base[s] | ((u64)(da[s] > 0 && (i64)c2[s] == da[s]) << REC_FULL2_BIT) | ((u64)(c1[s] > 0) << 62) | ((u64)(c2[s] > 0) << 63);
         }
-        if (!RECIN || void_batch) r[2] = (u64)a0 | ((u64)da << REC_LEN_SHIFT);
-        r[3] = (u64)base | ((u64)(da > 0 && (i64)c2 == da) << REC_FULL2_BIT) | ((u64)(c1 > 0) << 62) | ((u64)(c2 > 0) << 63);
       }
-    }
     if (gcost) {
-      // what this group of GPB consecutive slots will cost the pooling (entries to gather): the pooling visits its
+      // what each group of SCHED_GROUP consecutive slots will cost the pooling (entries to gather): the pooling visits its
       // groups longest first (ocn_gather_schedule), so that no straggler ends its kernel.  The one workgroup barrier of
       // an iteration, at its very end: s_cost alternates between two sets, so a wave that runs ahead into the next
       // iteration writes the other set and stops at that iteration's barrier, which thread 0 reaches after this read.
-      if (gl == 0) s_cost[par][g] = act ? c1 + c2 : 0;
+      // A wave folds its own slots first (SCHED_COST is associative), so s_cost stays one word per wave.
+      int cost = act[0] ? c1[0] + c2[0] : 0;
+#pragma unroll
+      for (int s = 1; s < NS; ++s) cost = SCHED_COST(cost, act[s] ? c1[s] + c2[s] : 0);
+      if (gl == 0) s_cost[par][g] = cost;
       __syncthreads();
       if (threadIdx.x == 0) {
-        int t = 0;
 #pragma unroll
-        for (int q = 0; q < GPB; ++q) t = SCHED_COST(t, s_cost[par][q]);
-        gcost[e0 / GPB] = t;
+        for (int q = 0; q < NS; ++q)          // group q of this workgroup: waves q * GPB / NS ... (gcost has ceil(B / SCHED_GROUP) words)
+          if (NS == 1 || e0 + q * SCHED_GROUP < B) {
+            int t = 0;
+#pragma unroll
+            for (int w = 0; w < GPB / NS; ++w) t = SCHED_COST(t, s_cost[par][q * (GPB / NS) + w]);
+            gcost[e0 / SCHED_GROUP + q] = t;
+          }
       }
     }
   }
@@ -191,6 +283,16 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
 extern "C" {
 
 int32_t ocn_cn_flags_small_graph_cols(void) { return LH_MAX_COLS; }
+
+// Large-graph batches of at least this many candidates take the slot-pair form (NS = 2): B / 2 waves must still fill the
+// chip's 8 192 wave slots several times over.  Process-wide; see ocn_hip.h.
+static int64_t g_flags_pair_min_batch = 32768;
+
+int64_t ocn_cn_flags_pair_min_batch(int64_t min_rows) {
+  const int64_t prev = g_flags_pair_min_batch;
+  if (min_rows >= 0) g_flags_pair_min_batch = min_rows;
+  return prev;
+}
 
 // rec_in: the records come half written from ocn_order_by_node_finish_rec (ocn_cn_flags_rec)
 static int cn_flags_launch(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT1,
@@ -210,15 +312,17 @@ static int cn_flags_launch(const int64_t* rowptrA, const int32_t* colA, const in
   const bool lh = n_cols > 0 && n_cols <= LH_MAX_COLS;
   const size_t lds = lh ? (size_t)n_cols * sizeof(u64) : 0;
   // LH: a persistent grid (a few workgroups per CU) so that each LDS histogram absorbs many edges
-  const int grid = lh ? grid_for((B + GPB - 1) / GPB, 256 * 3) : grid_for((B + GPB - 1) / GPB);
+  const bool pairs = !lh && B >= g_flags_pair_min_batch;      // two slots per wave (cn_flags_kernel: NS)
+  const int spb = pairs ? 2 * GPB : GPB;
+  const int grid = lh ? grid_for((B + GPB - 1) / GPB, 256 * 3) : grid_for((B + spb - 1) / spb);
   if (lh) {                                   // static (target rows) + dynamic (histogram) LDS can pass 64 KiB
     static bool raised_dev[64] = {};          // the attribute is per device (function objects are per device)
     int devid = 0;
     if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OCN_EINVAL;
     bool& raised = raised_dev[devid];
     if (!raised) {
-      const void* fns[4] = {(const void*)cn_flags_kernel<true, true, false>, (const void*)cn_flags_kernel<false, true, false>,
-                            (const void*)cn_flags_kernel<true, true, true>, (const void*)cn_flags_kernel<false, true, true>};
+      const void* fns[4] = {(const void*)cn_flags_kernel<true, true, false, 1>, (const void*)cn_flags_kernel<false, true, false, 1>,
+                            (const void*)cn_flags_kernel<true, true, true, 1>, (const void*)cn_flags_kernel<false, true, true, 1>};
       for (const void* fn : fns) {
         hipError_t e1 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LH_MAX_COLS * (int)sizeof(u64));
         if (e1 != hipSuccess) return (int)e1;
@@ -231,12 +335,13 @@ static int cn_flags_launch(const int64_t* rowptrA, const int32_t* colA, const in
       (const unsigned*)bitmapT1, (i64)bm1_stride_words, (const unsigned*)bitmapT2, (i64)bm_stride_words, (const i64*)src, \
       (const i64*)dst, (const i64*)order, (i64)B, (i64)n_cols, (const i64*)off, flags, (i64)flags_cap, \
       (u64*)hist, cnt1, cnt2, status, (u64*)rec, gcost
-#define CN_FLAGS_LAUNCH(T2, LHV, RI, T2P, T2C)                                                        \
-  hipLaunchKernelGGL((cn_flags_kernel<T2, LHV, RI>), dim3(grid), dim3(OCN_BLOCK), (LHV) ? lds : 0, st, CN_FLAGS_ARGS(T2P, T2C))
+#define CN_FLAGS_LAUNCH(T2, LHV, RI, NSV, T2P, T2C)                                                   \
+  hipLaunchKernelGGL((cn_flags_kernel<T2, LHV, RI, NSV>), dim3(grid), dim3(OCN_BLOCK), (LHV) ? lds : 0, st, CN_FLAGS_ARGS(T2P, T2C))
 #define CN_FLAGS_PICK(T2, T2P, T2C)                                                                   \
   do {                                                                                                \
-    if (lh) { if (rec_in) CN_FLAGS_LAUNCH(T2, true, true, T2P, T2C); else CN_FLAGS_LAUNCH(T2, true, false, T2P, T2C); }   \
-    else { if (rec_in) CN_FLAGS_LAUNCH(T2, false, true, T2P, T2C); else CN_FLAGS_LAUNCH(T2, false, false, T2P, T2C); }    \
+    if (lh) { if (rec_in) CN_FLAGS_LAUNCH(T2, true, true, 1, T2P, T2C); else CN_FLAGS_LAUNCH(T2, true, false, 1, T2P, T2C); }   \
+    else if (pairs) { if (rec_in) CN_FLAGS_LAUNCH(T2, false, true, 2, T2P, T2C); else CN_FLAGS_LAUNCH(T2, false, false, 2, T2P, T2C); }   \
+    else { if (rec_in) CN_FLAGS_LAUNCH(T2, false, true, 1, T2P, T2C); else CN_FLAGS_LAUNCH(T2, false, false, 1, T2P, T2C); }    \
   } while (0)
   if (!rowptrT2 && bitmapT2 && lh) return OCN_EINVAL;      // (small graphs read T2's row lengths beside its bit rows)
   if (rowptrT2 || bitmapT2) CN_FLAGS_PICK(true, rowptrT2, colT2);      // T2 by its bit rows alone: a product whose rows are built on demand
