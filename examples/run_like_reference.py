@@ -12,6 +12,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen # ... with column weights frozen on the validation edges
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
@@ -25,7 +26,9 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ocn_amd import ops                                                             # noqa: E402
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
+from ocn_amd.frozen import freeze_columns                                           # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
@@ -150,6 +153,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
     the trained model, on the adjacency that test candidates see; a source with fewer than K candidates is padded with -1.
     --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route.
+    --recommend-frozen: cn5 / cn7 score with column weights frozen on the validation positives; a call for half the sources
+    is checked to return the same rows.
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
     --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original.
     --recommend-check-refresh: the refreshed node embeddings are compared with a full encoder pass after either update."""
@@ -181,7 +186,22 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
                   flush=True)
         return dst, score
 
+    if args.recommend_frozen:
+        # --recommend-frozen: the column weights of cn5 / cn7 are taken once, from the validation positives as ONE reference batch
+        # (ocn_amd.frozen), and kept: a candidate's score then depends on nobody else who is asked about
+        ref = split_edge['valid']['edge'].to(dev)[:ops.MAX_BATCH].contiguous()
+        fc = freeze_columns(predictor, adj, adj2, ref, args)
+        predictor.set_frozen_columns(fc, args)
+        print(f"frozen {fc.kind} column weights from {fc.ref_size} validation edges ({'walk' if fc.valued else 'pattern'} route)", flush=True)
+
     dst, score = top(adj, adj2, "recommend")
+    if args.recommend_frozen:
+        h = state.h if state is not None else model(data.x, adj)
+        _, half = recommend_links(predictor, h, adj, adj2, sources[::2].contiguous(), k, max(args.testbs // 3, 1), args)
+        same = torch.allclose(half, score[::2], rtol=1e-5, atol=1e-5)
+        print(f"a call for every second source at a third of the batch size returns the same rows = {same}", flush=True)
+        if not same:
+            raise SystemExit("--recommend-frozen: the scores of a source changed with the other sources of the call")
     if args.recommend_accept > 0:
         # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
         # updated, not rebuilt; the node embeddings are refreshed row by row, EncoderState) and the same sources are asked again
@@ -246,6 +266,9 @@ def main(argv=None):
                          "(ocn_amd.sampling) instead of torch.randint pairs, which can be links")
     ap.add_argument("--recommend-walk", action="store_true",
                     help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
+    ap.add_argument("--recommend-frozen", action="store_true",
+                    help="with --recommend and a cn5 / cn7 model: freeze the column weights on the validation positives "
+                         "(ocn_amd.frozen) so that a source's scores do not depend on the other sources or the batch size")
     ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
                     help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
     ap.add_argument("--recommend-undo", action="store_true",
@@ -261,6 +284,8 @@ def main(argv=None):
         ap.error("--recommend-undo: needs --recommend K --recommend-accept M")
     if args.recommend_walk and args.heuristic in TWO_HOP:
         ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")
+    if args.recommend_frozen and (args.heuristic or not args.recommend or args.predictor not in ("cn5", "cn7")):
+        ap.error("--recommend-frozen: needs --recommend K and a cn5 or cn7 model")
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

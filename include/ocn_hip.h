@@ -46,7 +46,8 @@ extern "C" {
  *    ocn_rows_neighbourhood_workspace_bytes, ocn_rows_neighbourhood, ocn_bitlist_count / _fill (refreshing the node embeddings
  *    after an edge update: only the rows that can have changed); ocn_cn3_flags (the (A, A³) pass of cn6 from A and the bit rows
  *    of A², without a stored A³); ocn_cn_flags_pair_min_batch (the intersection pass takes two slots per wave at large batches;
- *    same bits). */
+ *    same bits); ocn_cn_pool_frozen (cn5 / cn7 pooled with a frozen column-weight table: intersection and weighted pooling in
+ *    one pass). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -329,6 +330,27 @@ int ocn_cn8_pool(const int64_t* rowptrA, const int32_t* colA,
                  const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
                  const float* h, int32_t H, float* xcn1, float* xcn2, float* xij,
                  int32_t* cnt1, int32_t* cnt2, void* stream);
+/* cn5 / cn7 with FROZEN column weights (ocn_amd/frozen.py; pattern route): intersection and weighted pooling in ONE pass,
+ * the shape of ocn_cn8_pool with a weight row per member.  weights is a [n_cols][4] table {w1, t, inv2, 0} (row-major fp32,
+ * 16-byte aligned) that ocn_cn_weights_cn5 / _cn7 formed for a REFERENCE batch and the caller kept; every candidate
+ * e = (i, j) = (src[e], dst[e]) is pooled with it instead of the weights of its own batch, so nothing of a candidate depends
+ * on the rest of the batch.  Per member k of N(i), with [cn1] = k in T1(j), [cn2] = k in T2(j):
+ *   wa = [cn1] * weights[k][0]      wb = ([cn2] - [cn1] * weights[k][1]) * weights[k][2]
+ *   xcn1[e] += wa * h[k]   xcn2[e] += wb * h[k]   exactly when wa != 0 or wb != 0 (then to both);   xij[e] = h[i] (.) h[j]
+ * every difference, product and sum rounded separately, N(i) walked in ascending column order by one lane group, hub rows
+ * included: bit for bit what ocn_cn_flags -> ocn_cn_gather(weights) leave for that candidate.  cnt1[e] / cnt2[e] = the
+ * number of members of N(i) ∩ T1(j) / N(i) ∩ T2(j) (int32), whatever their weights.  A candidate without members gets zero
+ * rows and zero counts.  No atomics, no workspace, nothing else written.
+ * T1 / T2, order, h, H and the outputs: as for ocn_cn8_pool.  NULL pointers, B < 0, n_cols < 0, another H, a misaligned
+ * table, a matrix with neither form or bit rows narrower than n_cols: OCN_EINVAL before any HIP call.  B == 0 returns 0. */
+int ocn_cn_pool_frozen(const int64_t* rowptrA, const int32_t* colA,
+                       const int64_t* rowptrT1 /* or NULL */, const int32_t* colT1 /* or NULL */,
+                       const int64_t* rowptrT2 /* or NULL */, const int32_t* colT2 /* or NULL */,
+                       const uint32_t* bitmapT1 /* or NULL */, int64_t bm1_stride_words,
+                       const uint32_t* bitmapT2 /* or NULL */, int64_t bm2_stride_words,
+                       const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
+                       const float* weights /* [n_cols][4] */, const float* h, int32_t H,
+                       float* xcn1, float* xcn2, float* xij, int32_t* cnt1, int32_t* cnt2, void* stream);
 /* Link heuristics (common neighbours, Adamic-Adar, resource allocation, Jaccard, preferential attachment and their 2-hop
  * forms: ocn_amd/heuristics.py) in ONE pass, the shape of ocn_cn8_pool with a 16-byte node row in place of an embedding row:
  *   sum1[e][q] = sum_{k in N(i) ∩ T1(j)} w[k][q]   sum2[e][q] = sum_{k in N(i) ∩ T2(j)} w[k][q]   q = 0..3

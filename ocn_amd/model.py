@@ -617,7 +617,7 @@ _LATE = object()        # token slot 1: the histogram all-reduce is started by f
 class _CNPredictorBase(nn.Module):
     """Parameters, MLP heads and the batch path shared by cn5, cn7 and cn8 (model.py:2173-2239 ≡ 3023-3089).  The
     ``nn.Sequential`` layouts are part of the checkpoint contract (state_dict keys).  A predictor differs from cn5 through
-    ``_weights``, ``_rowsum``, ``_batch_state`` and the three class attributes below."""
+    ``_batch_weights`` (cn8: ``_weights``), ``_rowsum``, ``_batch_state`` and the three class attributes below."""
     cndeg: Final[int]
     _xcn2_on_union = True          # pooled xcn2 lives on cn1 ∪ cn2 (cn5); cn7 overrides: raw cn2 only
     _weights_need_args = False     # cn7: its column weights read ``args.sum``
@@ -662,6 +662,52 @@ class _CNPredictorBase(nn.Module):
         self._cache = {}                       # name -> (key, value): derived constants, see _cached / _drop_caches
         self._rowsum_cache = None              # cn7: A·h of the live embeddings (_rowsum)
         self._skip_state = None                # per-run state of the zero-row skipping, from the first probe on
+        self._frozen = None                    # a FrozenColumns in place of every batch's own column weights (set_frozen_columns)
+
+    def set_frozen_columns(self, fc, args=None):
+        """Install the column weights of a reference batch (``ocn_amd.frozen.freeze_columns``) in place of every batch's own, or
+        None to remove them; returns what was installed before.  Frozen, a cn5 / cn7 predictor in eval mode pools every
+        candidate with that table: nothing of a candidate depends on the rest of its batch, whatever entry point scores it
+        (``score_edges``, ``score_edges_walk``, ``score_mrr_split``, ``recommend_links``, direct calls).  On pattern
+        ``adjoverlap`` handles with ``ops.frozen_fused_eval`` the batch is intersected and pooled in ONE pass
+        (``ocn_cn_pool_frozen``); everything else takes the chain with the table as its weights — same bits.  The table's
+        kind and what it baked in (``innerprod``; ``polyfirst`` / ``polysecond``; with ``args`` given, ``args.sum``) are checked
+        against this predictor here, once (ValueError).  A frozen cn7 needs no ``args`` at scoring time and ignores its ``sum``."""
+        from .frozen import FrozenColumns, _kind_of, baked_values
+        before = self._frozen
+        if fc is None:
+            self._frozen = None
+            return before
+        kind = _kind_of(self)                  # (cn8: ValueError, cn6: NotImplementedError)
+        if not isinstance(fc, FrozenColumns):
+            raise TypeError("set_frozen_columns takes a FrozenColumns (ocn_amd.frozen.freeze_columns) or None")
+        if fc.kind != kind:
+            raise ValueError(f"a {fc.kind} table cannot be installed in a {kind} predictor")
+        w = fc.weights
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and tuple(w.shape) == (int(fc.n_cols), 4) and w.is_contiguous()):
+            raise ValueError("FrozenColumns.weights must be a contiguous float32 [n_cols, 4] tensor")
+        if w.device != self.beta.device:
+            raise ValueError(f"the frozen table lives on {w.device}, the predictor on {self.beta.device}: use FrozenColumns.to()")
+        for k, v in baked_values(self, kind, args).items():
+            if getattr(fc, k) != v:
+                raise ValueError(f"the table was frozen with {k} = {getattr(fc, k)}, the predictor has {v}")
+        self._frozen = fc
+        return before
+
+    def _frozen_weights(self, st):
+        """The installed table as the weights of batch state ``st`` (the chain's, or the one pass's), checked against it."""
+        fc = self._frozen
+        if st.N != fc.n_cols:
+            raise ValueError(f"the frozen table has {fc.n_cols} columns, the batch's adjacency {st.N}")
+        if bool(st.walk) != bool(fc.valued):
+            raise ValueError("a table frozen on the walk route (valued cn2) serves walk handles only, a pattern table pattern handles only")
+        if fc.weights.device != st.src.device:
+            raise ValueError(f"the frozen table lives on {fc.weights.device}, the batch on {st.src.device}")
+        return fc.weights
+
+    def _weights(self, st, args):
+        """The column weights of batch state ``st``: the installed table, else the batch's own (``_batch_weights``)."""
+        return self._frozen_weights(st) if self._frozen is not None else self._batch_weights(st, args)
 
     def set_edge_sharding(self, group=None, enabled: bool = True) -> None:
         """The candidate batch handed to ``forward`` is one rank's slice of a global batch: sum the
@@ -683,7 +729,23 @@ class _CNPredictorBase(nn.Module):
         return st
 
     def _batch_state(self, x, cn1, cn2, tar_ei, ws, adj):
-        """The batch state of (cn1, cn2); a state that pools in its own pass arrives with ``pooled`` set (cn8)."""
+        """The batch state of (cn1, cn2); a state that pools in its own pass arrives with ``pooled`` set (cn8; cn5 / cn7 with
+        frozen column weights on pattern handles, under ``ops.frozen_fused_eval``)."""
+        fc = self._frozen
+        if fc is not None:
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError("frozen column weights are the eval path: call .eval() under torch.no_grad(), or "
+                                   "set_frozen_columns(None) first")
+            if self._sharded:
+                raise RuntimeError("frozen column weights on an edge-sharded predictor are not built")
+            if (ops.frozen_fused_eval and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.float32
+                    and x.shape[1] in ops.LN_WIDTHS):
+                from .utils import fuse8
+                st = fuse8(cn1, cn2, tar_ei, ws, weights=fc.weights)
+                if st is not None:
+                    self._frozen_weights(st)               # (columns, route, device)
+                    st.pooled = st.pool(x.contiguous())
+                    return st
         return fuse(cn1, cn2, tar_ei, ws, adj=adj)
 
     def _score(self, x, adj, cn1, cn2, tar_ei, args=None):
@@ -721,7 +783,8 @@ class _CNPredictorBase(nn.Module):
         # trained cn5 / cn6 (innerprod != 0), the order-exact column sums in front of them, 0.2 ms of latency-bound chains at
         # the collab shape — belong to phase A, which the scoring loops run beside the previous batch's pooling and heads.
         # (cn7's weights need ``args.sum``: pass ``args``.)
-        w = self._weights(st, args) if (args is not None or not self._weights_need_args) else None
+        # (frozen column weights need none either)
+        w = self._weights(st, args) if (args is not None or not self._weights_need_args or self._frozen is not None) else None
         if ops.phase_a_extras:
             self._class_order(st, x)           # reads the per-row counts only: off the critical phase too
             st.prepare_schedule(x.shape[1])    # ... as does the pooling's visiting order (group costs of the intersection pass)
@@ -1108,7 +1171,7 @@ class CNLinkPredictorOringin(_CNPredictorBase):
                            cndropprobs: Iterable[float] = []):
         return self._score(x, adj, cn1, cn2, tar_ei)
 
-    def _weights(self, st, args):
+    def _batch_weights(self, st, args):
         return st.weights_cn5(self.innerprod1(st))
 
     def forward(self, x, adj, cn1, cn2, tar_ei, filled1: bool = False):
@@ -1130,7 +1193,7 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
                            cndropprobs: Iterable[float] = []):
         return self._score(x, adj, cn1, cn2, tar_ei, args)
 
-    def _weights(self, st, args):
+    def _batch_weights(self, st, args):
         dev = st.hist.device
         return st.weights_cn7(float(args.sum), chebyshev_diag(st.N, int(self.polyfirst), dev),
                               chebyshev_diag(st.N, int(self.polysecond), dev))

@@ -684,6 +684,49 @@ def cn8_pool(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor],
     return out[0], out[1], out[2], cnt[0], cnt[1]
 
 
+# A cn5 / cn7 predictor with frozen column weights (ocn_amd/frozen.py) in eval on adjoverlap handles: ocn_cn_pool_frozen when on,
+# else the chain (flags -> the frozen table in place of the batch's weights -> the pooling).  OFF by default, by the rule of
+# ``cn8_fused_eval``: the default goes to the one pass only on a measurement that shows its range below the chain's at the
+# throughput shape (frozen column weights; tools/frozenbench.py).
+frozen_fused_eval = os.environ.get("OCN_FROZEN_FUSED", "0") == "1"
+
+
+@_on_device
+def cn_pool_frozen(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor], Optional[Tensor]]],
+                   t2: Optional[Tuple[Optional[Tensor], Optional[Tensor]]], src: Tensor, dst: Tensor, h: Tensor, weights: Tensor,
+                   t1_bitmap: Optional[Tensor] = None, t2_bitmap: Optional[Tensor] = None, order: Optional[Tensor] = None, wsd=None,
+                   n_cols: Optional[int] = None):
+    """Intersection and pooling with a frozen column-weight table in one pass (ocn_hip.h: ocn_cn_pool_frozen; pattern route).
+    ``weights``: float32 [N, 4] = {w1, t, inv2, 0} per column, N = the rows of ``h``; everything else as for ``cn8_pool``.
+    Bit for bit what ``cn_flags`` -> ``cn_gather(weights=weights)`` leave for every candidate, whatever else is in the batch.
+    Returns (xcn1, xcn2, xij [B, H], cnt1, cnt2 int32 [B] — the member counts, whatever their weights)."""
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    B = _batch_ids(src, dst)
+    N, H = _req(h, torch.float32, "h", 2).shape
+    if H not in LN_WIDTHS:
+        raise NotImplementedError(f"frozen pooling supports hidden widths {LN_WIDTHS}, got {H}")
+    if n_cols is not None and int(n_cols) != N:
+        raise ValueError(f"h has {N} rows, the adjacency {int(n_cols)} columns")
+    if tuple(_req(weights, torch.float32, "weights", 2).shape) != (N, 4):
+        raise ValueError(f"weights must be [N, 4] with N = h.shape[0] = {N}, got {tuple(weights.shape)}")
+    if weights.data_ptr() % 16:
+        raise ValueError("weights must be 16-byte aligned")
+    *csr1, rows = _t_pair_or_bits(t1, t1_bitmap, "T1", N)
+    *csr2, _ = _t_pair_or_bits(t2, t2_bitmap, "T2", N, like=rows)
+    _order_arg(order, B)
+    check_edges(src, dst, rowptrA.numel() - 1, rows)
+    out = buf(wsd, "pooled", (3, B, H), torch.float32, h.device)
+    cnt = buf(wsd, "cn8_cnt", (2, B), torch.int32, h.device)
+    if B == 0:
+        return out[0], out[1], out[2], cnt[0], cnt[1]
+    _mark("cn_prep")
+    check(_lib.lib().ocn_cn_pool_frozen(*_cn_operands(rowptrA, colA, csr1, csr2, t1_bitmap, t2_bitmap, src, dst, order, B, N),
+                                        ptr(weights), ptr(h), H, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(cnt[0]), ptr(cnt[1]),
+                                        stream_ptr()), "ocn_cn_pool_frozen")
+    _mark("cn_pool_frozen")
+    return out[0], out[1], out[2], cnt[0], cnt[1]
+
+
 @_on_device
 def cn_node_sums(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor], Optional[Tensor]]],
                  t2: Optional[Tuple[Optional[Tensor], Optional[Tensor]]], src: Tensor, dst: Tensor, w: Tensor,

@@ -5,7 +5,8 @@
     torch.cat([predictor(h, adj, adjoverlap(adj, adj, e[perm].t()), adjoverlap(adj, adj2, e[perm].t()),
                          e[perm].t(), args).squeeze().cpu() for perm in PermIterator(dev, n, bs, False)])
 
-(NeighborOverlap_large.py:121-159) — same batch composition, so the same batch-coupled normalisation —
+(NeighborOverlap_large.py:121-159) — same batch composition, so the same batch-coupled normalisation (a predictor
+with frozen column weights, ``ocn_amd.frozen``, scores every candidate independently of its batch in all of these loops) —
 with one D2H copy at the end instead of one blocking ``.cpu()`` per batch.  (An earlier version ran the
 CN stage of batch t+1 on a second stream beside the MLP heads of batch t: +4 % only, the MFMA kernels
 leave no registers for a co-resident wave — DESIGN.md §4; the single-stream loop below, which gets the

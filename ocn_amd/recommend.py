@@ -100,7 +100,8 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     The normalisation of cn5 and cn7 couples the candidates of a batch, so the contract is stated in terms of that call:
     the scores are exactly those ``score_edges`` returns for the flat candidate list at this ``batch_size``.  Another set of
     ``sources`` or another ``batch_size`` puts other candidates into a batch and changes cn5 / cn7 scores — as it does in the
-    reference's ``test()``.  Ties go to the lower node id (candidates are in ascending order).
+    reference's ``test()`` — unless the predictor carries frozen column weights (``predictor.set_frozen_columns``,
+    ``ocn_amd.frozen``): then a source's scores depend on neither.  Ties go to the lower node id (candidates are in ascending order).
 
     ``adj2=None``: the candidates come from ``adj`` alone and the one scoring call is
     ``pipeline.score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)``; the contract is the same sentence

@@ -481,17 +481,40 @@ class CN8State(_BatchState):
         csr2 = None if bm2 is not None else (t2._rowptr, t2._col)
         bm1 = t1.bit_rows()
         self.order = ops.batch_order(self.src, adj.size(0), self.ws)
-        x1, x2, xij, self.cnt1, self.cnt2 = ops.cn8_pool(adj._rowptr, adj._col, (t1._rowptr, t1._col), csr2, self.src, self.dst, h,
-                                                         t1_bitmap=bm1, t2_bitmap=bm2, order=self.order, wsd=self.ws, n_cols=self.N)
+        x1, x2, xij, self.cnt1, self.cnt2 = self._pool_op(adj._rowptr, adj._col, (t1._rowptr, t1._col), csr2, self.src, self.dst, h,
+                                                          t1_bitmap=bm1, t2_bitmap=bm2, order=self.order, wsd=self.ws, n_cols=self.N)
         return x1, x2, xij
 
+    def _pool_op(self, rowptr, col, csr1, csr2, src, dst, h, **kw):
+        return ops.cn8_pool(rowptr, col, csr1, csr2, src, dst, h, **kw)
 
-def fuse8(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None) -> Optional[CN8State]:
+
+class FrozenState(CN8State):
+    """A cn5 / cn7 batch on the pattern route whose column weights are FROZEN (``ocn_amd.frozen``): with the table fixed, a
+    candidate's pooled vectors depend on the candidate alone, so the batch needs what a cn8 batch needs plus the table —
+    ``pool(h)`` runs ``ops.cn_pool_frozen`` (intersection and weighted pooling in one pass)."""
+    weights = None
+
+    def __init__(self, adj: SparseTensor, t1: SparseTensor, t2: SparseTensor, tarei: Tensor, weights: Tensor,
+                 ws: Optional[dict] = None):
+        super().__init__(adj, t1, t2, tarei, ws=ws)
+        if tuple(weights.shape) != (self.N, 4):
+            raise ValueError(f"the frozen table has {weights.shape[0]} columns, the adjacency {self.N}")
+        self.weights = weights
+
+    def _pool_op(self, rowptr, col, csr1, csr2, src, dst, h, **kw):
+        return ops.cn_pool_frozen(rowptr, col, csr1, csr2, src, dst, h, self.weights, **kw)
+
+
+def fuse8(cn1, cn2, tar_ei: Tensor, ws: Optional[dict] = None, weights: Optional[Tensor] = None) -> Optional[CN8State]:
     """The cn8 batch of two pattern-mode ``adjoverlap`` handles (same adjacency, same candidate edges: the checks of
-    ``fuse``), or None for anything else — walk handles and explicit matrices take the flag form (``fuse``)."""
+    ``fuse``), or None for anything else — walk handles and explicit matrices take the flag form (``fuse``).  ``weights``: a
+    frozen column-weight table — the batch is then the ``FrozenState`` of a cn5 / cn7 predictor."""
     if not (isinstance(cn1, CNBatch) and isinstance(cn2, CNBatch) and cn1.mode == "pattern" and cn2.mode == "pattern"):
         return None
     _check_one_batch((cn1, cn2), tar_ei, "cn1 and cn2 must select their source rows from the same adjacency")
+    if weights is not None:
+        return FrozenState(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, weights, ws=ws)
     return CN8State(cn1.adj1, cn1.adj2, cn2.adj2, cn1.tarei, ws=ws)
 
 
