@@ -13,6 +13,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen # ... with column weights frozen on the validation edges
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
@@ -32,7 +33,8 @@ from ocn_amd.frozen import freeze_columns                                       
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
-from ocn_amd.recommend import recommend_links, recommend_links_heuristic            # noqa: E402
+from ocn_amd.recommend import (prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
+                               two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
@@ -155,6 +157,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     --recommend-walk: without A² — candidates expanded from the adjacency, the model's scores on the walk route.
     --recommend-frozen: cn5 / cn7 score with column weights frozen on the validation positives; a call for half the sources
     is checked to return the same rows.
+    --recommend-prefilter KIND:M: the model ranks only the M best candidates of every source by the heuristic KIND (cn, aa, ra);
+    with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
     --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original.
     --recommend-check-refresh: the refreshed node embeddings are compared with a full encoder pass after either update."""
@@ -180,7 +184,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
         else:
             h = state.h if state is not None else model(data.x, adj)
-            dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args)
+            dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, prefilter=args.recommend_prefilter)
         for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
             print(f"{tag} source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
                   flush=True)
@@ -197,11 +201,22 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     dst, score = top(adj, adj2, "recommend")
     if args.recommend_frozen:
         h = state.h if state is not None else model(data.x, adj)
-        _, half = recommend_links(predictor, h, adj, adj2, sources[::2].contiguous(), k, max(args.testbs // 3, 1), args)
+        _, half = recommend_links(predictor, h, adj, adj2, sources[::2].contiguous(), k, max(args.testbs // 3, 1), args,
+                                  prefilter=args.recommend_prefilter)    # (like with like: a source's short list is its own)
         same = torch.allclose(half, score[::2], rtol=1e-5, atol=1e-5)
         print(f"a call for every second source at a third of the batch size returns the same rows = {same}", flush=True)
         if not same:
             raise SystemExit("--recommend-frozen: the scores of a source changed with the other sources of the call")
+        if args.recommend_prefilter:
+            # how many of the unfiltered top-K the short list kept: printed only — a synthetic graph under an untrained or briefly
+            # trained model supports no claim about the quality of a prefilter
+            full, _ = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args)
+            kept = int(((dst[:, :, None] == full[:, None, :]) & (full[:, None, :] >= 0)).any(1).sum())
+            kind, m = args.recommend_prefilter
+            n_all = int(two_hop_candidates(adj, adj2, sources)[0][-1])
+            n_short = int(prefilter_candidates(adj, sources, kind, m)[0][-1])
+            print(f"prefilter {kind}:{m} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
+                  f"(the model ranked {n_short} of {n_all} candidates)", flush=True)
     if args.recommend_accept > 0:
         # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
         # updated, not rebuilt; the node embeddings are refreshed row by row, EncoderState) and the same sources are asked again
@@ -269,6 +284,9 @@ def main(argv=None):
     ap.add_argument("--recommend-frozen", action="store_true",
                     help="with --recommend and a cn5 / cn7 model: freeze the column weights on the validation positives "
                          "(ocn_amd.frozen) so that a source's scores do not depend on the other sources or the batch size")
+    ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M",
+                    help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
+                         "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
     ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
                     help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
     ap.add_argument("--recommend-undo", action="store_true",
@@ -286,6 +304,11 @@ def main(argv=None):
         ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")
     if args.recommend_frozen and (args.heuristic or not args.recommend or args.predictor not in ("cn5", "cn7")):
         ap.error("--recommend-frozen: needs --recommend K and a cn5 or cn7 model")
+    if args.recommend_prefilter:
+        kind, _, m = args.recommend_prefilter.partition(":")
+        if args.heuristic or not args.recommend or kind not in ("cn", "aa", "ra") or not m.isdigit() or not args.recommend <= int(m) <= 128:
+            ap.error("--recommend-prefilter KIND:M: needs a model, --recommend K, KIND one of cn, aa, ra and K <= M <= 128")
+        args.recommend_prefilter = (kind, int(m))
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

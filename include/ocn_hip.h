@@ -47,7 +47,8 @@ extern "C" {
  *    after an edge update: only the rows that can have changed); ocn_cn3_flags (the (A, A³) pass of cn6 from A and the bit rows
  *    of A², without a stored A³); ocn_cn_flags_pair_min_batch (the intersection pass takes two slots per wave at large batches;
  *    same bits); ocn_cn_pool_frozen (cn5 / cn7 pooled with a frozen column-weight table: intersection and weighted pooling in
- *    one pass). */
+ *    one pass); ocn_two_hop_sums_window_cols, ocn_two_hop_sums_fill (the 2-hop candidates with their cn / aa / ra path sums:
+ *    the retrieval half of two-stage recommendation). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -413,6 +414,34 @@ int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int
                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self,
                           int64_t window_cols /* 0: the default */, const int64_t* off /* [Q + 1], from ocn_scan_i32 */,
                           int64_t* edges /* [off[Q]][2] */, void* stream);
+/* The candidates of ocn_two_hop_diff_fill, each with a path sum (retrieve-then-rank recommendation: the cheap score the
+ * candidates are short-listed by, from the expansion that enumerates them — no intersection per candidate, no A²).
+ *   edges: exactly the pairs ocn_two_hop_diff_fill writes for the same arguments — the same set, the same ascending order, the
+ *   same `off` protocol (off = ocn_scan_i32 of ocn_two_hop_diff_count: there is no second counting pass), a pair at off[q + 1]
+ *   or beyond is dropped, and so is its value.
+ *   val[p] (fp32 [off[Q]]) for the pair (s, c) at position p = the sum of w[m][wcol] over the m in row s of A whose row holds c,
+ *   taken in ASCENDING m, one fp32 add per member, starting from 0.0f, plain adds without contraction.  w: a node table
+ *   [n_cols][4] row-major (the table of ocn_cn_node_sums), wcol its column 0 .. 3; w == NULL: every weight is 1.0f and wcol is
+ *   ignored.  For a symmetric A that is, bit for bit, what ocn_cn_node_sums adds up for the candidate (s, c) over
+ *   N(s) ∩ N(c): w == NULL the common-neighbour count, the columns of 1 / log deg and 1 / deg Adamic-Adar and resource allocation.
+ *   Membership is a presence bit, not val != 0: a candidate whose sum is zero or negative is emitted like any other.
+ * A workgroup owns a query; a window keeps one presence bit and one fp32 accumulator per column in LDS, so it is
+ * ocn_two_hop_sums_window_cols() columns wide (about 39 000, a multiple of 64) and any n_cols < 2^31 is swept in such windows.
+ * Each of the four waves owns a contiguous quarter of the window's columns and walks all neighbours of s in ascending order,
+ * so an accumulator is touched by one wave only, in program order: LDS atomics on the presence bits alone, no float atomics,
+ * no global atomics, no workspace — val is fixed by the input.  window_cols: 0 = the default, else a positive multiple of 64
+ * no larger than it (for tests of the sweep on small graphs).  The launch has at most 4 096 workgroups; beyond that many
+ * queries a workgroup takes several, grid-stride.  LDS: min(window_cols, n_cols rounded up to 64) * 33 / 8 bytes.
+ * A and M as for ocn_two_hop_diff_*; rows[] must be valid row ids (not checked here).
+ * NULL rowptrA / colA / rowptrM / colM / rows / off / edges / val, Q < 0, n_cols <= 0 or >= 2^31, a bad window_cols, wcol
+ * outside 0 .. 3 with w given: OCN_EINVAL before any HIP call.  Q == 0 returns 0. */
+int64_t ocn_two_hop_sums_window_cols(void);
+int ocn_two_hop_sums_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self,
+                          int64_t window_cols /* 0: the default */,
+                          const float* w /* [n_cols][4] row-major, or NULL: every weight 1.0f */,
+                          int32_t wcol /* 0 .. 3, ignored when w == NULL */, const int64_t* off /* [Q + 1] */,
+                          int64_t* edges /* [off[Q]][2] */, float* val /* [off[Q]] */, void* stream);
 /* The k best entries of every segment scores[ptr[q] .. ptr[q + 1]) of a flat fp32 vector, best first, 1 <= k <=
  * ocn_segment_topk_max_k() (128: two slots per lane).  top_val [Q][k] = the scores, top_pos [Q][k] (int64) = their positions
  * in the FLAT vector, so that one index gathers whatever else the caller keeps per entry; a segment with fewer than k

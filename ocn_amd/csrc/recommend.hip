@@ -6,6 +6,8 @@
 // Where A² is not stored (more columns than the A*A pattern takes, or simply too large) the same candidate set is expanded
 // from A itself: a workgroup owns a query and keeps the union of its neighbours' rows as a bitmap in LDS, one window of the
 // column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
+#include <atomic>
+
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -178,6 +180,133 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// the same set with a path sum per member: val(s, c) = sum of w[m] over the m in A[s,:] whose row holds c
+// ---------------------------------------------------------------------------------------------
+// A window column keeps a presence bit and an fp32 accumulator (33 bits) in the LDS the bitmap kernel keeps: 39 168 columns.
+constexpr i64 TS_WINDOW = (i64)(160 * 1024 - 2048) * 8 / 33 / 64 * 64;
+
+// one member of column k (relative to the window): the presence bit, and the accumulator's next partial sum — the first member
+// of a column adds to 0.0f, so no accumulator is ever cleared
+__device__ __forceinline__ void ts_add(unsigned* bm, float* acc, unsigned k, float wm) {
+  const unsigned bit = 1u << (k & 31u);
+  // Read whatever the bit will say, so that a member costs one LDS round trip, not two.  For a column's first member the slot
+  // holds whatever the last window or query left there: that value is only ever SELECTED AWAY below, it never enters the add.
+  // (Reading after the atomicOr instead would be as correct and a round trip slower.)
+  const float prev = acc[k];
+  const unsigned old = atomicOr(&bm[k >> 5], bit);
+  acc[k] = __fadd_rn((old & bit) ? prev : 0.0f, wm);
+}
+
+__device__ __forceinline__ i64 th_readlane(i64 v, int l) {
+  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), l);
+  return (i64)(((u64)hi << 32) | lo);
+}
+
+// The valued sibling of two_hop_diff_kernel<true>: the same windows, the same bitmap, the same steps 3 and 4 — so the pairs,
+// their order and the `off` protocol are those of the fill pass — and beside every pair its sum.  Step 2 differs, because the
+// sum of a column must add its members in ascending m, whatever the launch:
+//   2. the window's columns are dealt to the four waves in contiguous quarters, and EVERY wave walks ALL neighbours m of s in
+//      ascending order, taking of row m the part inside its own quarter, its lanes on consecutive entries.  (The rows of 64
+//      neighbours are looked up at once, a lane each — here th_lower_bound runs per lane — and the wave then visits, in lane
+//      order, those that have a column in the quarter.)  An accumulator is therefore only ever touched by one wave, the lanes of one
+//      instruction touch distinct columns, and LDS executes a wave's instructions in order: a plain read-add-write per member
+//      is the ascending-m sum, with no accumulator atomics and no barrier between neighbours.  The presence bit is set by an
+//      atomicOr (lanes, and at a quarter's edge waves, do meet in one word) whose return value tells the first member of a
+//      column from the later ones: the first one adds to 0.0f, so the accumulators are never cleared.
+// A member counts by its bit, never by its value: a weight may be zero or negative.  w == nullptr: every weight is 1.0f.
+__global__ __launch_bounds__(OCN_BLOCK) void two_hop_sums_kernel(
+    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+    const i64* __restrict__ rowptrM, const int32_t* __restrict__ colM, i64 n_cols,
+    const i64* __restrict__ rows, i64 Q, int drop_self, i64 window, const float* __restrict__ w, int wcol,
+    const i64* __restrict__ off, longlong2* __restrict__ edges, float* __restrict__ val) {
+  extern __shared__ __attribute__((aligned(16))) unsigned th_bm[];
+  __shared__ i64 sh[2 * OCN_WPB];
+  const i64 span = window < (n_cols + 63) / 64 * 64 ? window : (n_cols + 63) / 64 * 64;   // the columns the launch sized LDS for
+  float* acc = reinterpret_cast<float*>(th_bm + (span >> 5));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (i64 q = blockIdx.x; q < Q; q += gridDim.x) {
+    const i64 s = rows[q];
+    const i64 a0 = rowptrA[s], da = rowptrA[s + 1] - a0;
+    const i64 m0 = rowptrM[s], dm = rowptrM[s + 1] - m0;
+    i64 base = off[q];
+    const i64 end = off[q + 1];
+    for (i64 w0 = 0; w0 < n_cols; w0 += window) {
+      const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
+      const int words = (int)((w1 - w0 + 31) >> 5);
+      for (int t = threadIdx.x; t < words; t += OCN_BLOCK) th_bm[t] = 0u;
+      __syncthreads();
+      const i64 quarter = (w1 - w0 + OCN_WPB - 1) / OCN_WPB;
+      const i64 q0 = w0 + wave * quarter;
+      const i64 q1 = (q0 + quarter) < w1 ? (q0 + quarter) : w1;            // (an empty quarter: q1 <= q0, nothing passes below)
+      for (i64 t0 = 0; t0 < da; t0 += OCN_WAVE) {
+        // 64 neighbours at a time, one per lane: where its row enters the quarter (a search per lane, 64 side by side), where
+        // it ends, its weight, and whether it has a column in the quarter at all — most rows miss most quarters of a wide graph
+        const i64 tt = t0 + lane;
+        i64 lb = 0, le = 0;
+        float lw = 0.0f;
+        if (tt < da) {
+          const i64 m = colA[a0 + tt];
+          const i64 b0 = rowptrA[m];
+          le = rowptrA[m + 1];
+          lb = b0 + (q0 > 0 ? th_lower_bound(colA + b0, le - b0, q0) : 0);
+          lw = w ? w[m * 4 + wcol] : 1.0f;
+        }
+        u64 live = __ballot(lb < le && (i64)colA[lb < le ? lb : a0] < q1);   // (a0: in bounds, da > 0 here; the value is not used)
+        while (live) {                                       // ascending lanes: ascending m (the same trips in every lane)
+          const int j = __ffsll((long long)live) - 1;
+          live &= live - 1;
+          const i64 pe = th_readlane(le, j);
+          const float wm = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(lw), j));
+          for (i64 p = th_readlane(lb, j) + lane; p < pe; p += OCN_WAVE) {
+            const i64 c = colA[p];
+            if (c >= q1) break;                              // (sorted: so is every later column of this lane)
+            ts_add(th_bm, acc, (unsigned)(c - w0), wm);
+          }
+          wave_lds_sync();                                   // the next neighbour's reads stay behind this one's writes
+        }
+      }
+      __syncthreads();
+      const i64 lo_m = w0 > 0 ? th_lower_bound(colM + m0, dm, w0) : 0;
+      for (i64 p = lo_m + threadIdx.x; p < dm; p += OCN_BLOCK) {
+        const i64 c = colM[m0 + p];
+        if (c >= w1) break;
+        if (c >= w0) {
+          const unsigned k = (unsigned)(c - w0);
+          atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
+        }
+      }
+      if (drop_self && threadIdx.x == 0 && s >= w0 && s < w1) {
+        const unsigned k = (unsigned)(s - w0);
+        atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
+      }
+      __syncthreads();
+      const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;   // contiguous words per thread: ascending columns in thread order
+      const int t0 = (int)threadIdx.x * wpt < words ? (int)threadIdx.x * wpt : words;
+      const int t1 = (t0 + wpt) < words ? (t0 + wpt) : words;
+      i64 c = 0;
+      for (int t = t0; t < t1; ++t) c += __popc(th_bm[t]);
+      i64 tot;
+      const i64 ex = block_excl_scan(c, sh, &tot);
+      i64 at = base + ex;
+      for (int t = t0; t < t1; ++t) {
+        unsigned bits = th_bm[t];
+        while (bits) {
+          const int b = __ffs((int)bits) - 1;
+          bits &= bits - 1;
+          if (at < end) {                                    // (at < end: as in the row difference)
+            edges[at] = make_longlong2(s, w0 + ((i64)t << 5) + b);
+            val[at] = acc[(t << 5) + b];
+          }
+          ++at;
+        }
+      }
+      base += tot;
+      __syncthreads();                                       // the next window's clear stays behind this one's reads
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // segmented top-k
 // ---------------------------------------------------------------------------------------------
 constexpr int TOPK_MAX = 2 * OCN_WAVE;                       // two slots per lane
@@ -341,6 +470,41 @@ int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int
                           const int64_t* off, int64_t* edges, void* stream) {
   return two_hop_launch(true, rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, nullptr, off, edges,
                         stream);
+}
+
+int64_t ocn_two_hop_sums_window_cols(void) { return TS_WINDOW; }
+
+int ocn_two_hop_sums_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, const float* w,
+                          int32_t wcol, const int64_t* off, int64_t* edges, float* val, void* stream) {
+  if (Q < 0 || !rowptrA || !colA || !rowptrM || !colM || !rows || !off || !edges || !val) return OCN_EINVAL;
+  if (n_cols <= 0 || n_cols >= ((int64_t)1 << 31)) return OCN_EINVAL;
+  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > TS_WINDOW) return OCN_EINVAL;
+  if (w && (wcol < 0 || wcol > 3)) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  const i64 window = window_cols ? (i64)window_cols : TS_WINDOW;
+  const i64 padded = (n_cols + 63) / 64 * 64;
+  const i64 span = window < padded ? window : padded;                         // a small graph keeps several workgroups per CU
+  const size_t lds = (size_t)(span / 8 + span * 4);                           // the bitmap, then the accumulators
+  // The LDS limit of the kernel is raised ONCE per device, to what the default window takes — never per launch to that launch's
+  // size: two host threads that launch graphs of different widths would race between the set and the launch.  (Setting the
+  // same value twice, by two first callers, is harmless.)
+  static std::atomic<unsigned long long> lds_raised{0ull};
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return (int)err;
+  if (dev >= 64 || !((lds_raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    err = hipFuncSetAttribute((const void*)two_hop_sums_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(TS_WINDOW / 8 + TS_WINDOW * 4));
+    if (err != hipSuccess) return (int)err;
+    if (dev < 64) lds_raised.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  // at most 16 workgroups per CU's worth of queries in flight: a request of a few thousand sources is dealt a workgroup per
+  // source by the hardware, a longer list is taken grid-stride
+  hipLaunchKernelGGL(two_hop_sums_kernel, dim3((unsigned)grid_for(Q, 256 * 16)), dim3(OCN_BLOCK), lds, (hipStream_t)stream,
+                     (const i64*)rowptrA, colA, (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self,
+                     window, w, (int)(w ? wcol : 0), (const i64*)off, (longlong2*)edges, val);
+  return launch_status();
 }
 
 int32_t ocn_segment_topk_max_k(void) { return TOPK_MAX; }

@@ -812,16 +812,17 @@ def two_hop_window_cols() -> int:
     return int(_lib.lib().ocn_two_hop_window_cols())
 
 
-def _two_hop_args(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, window_cols: int) -> Tuple[int, int]:
-    """The operand checks of both 2-hop passes: those of the row difference (A and M square and of one size, sorted
-    duplicate-free columns, which this layer cannot see) and the window.  Returns (Q, n)."""
+def _two_hop_args(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, window_cols: int,
+                  window_limit=two_hop_window_cols) -> Tuple[int, int]:
+    """The operand checks of the 2-hop passes: those of the row difference (A and M square and of one size, sorted
+    duplicate-free columns, which this layer cannot see) and the window (``window_limit``: the entry's own).  Returns (Q, n)."""
     Q = _row_diff_args(rowptrA, colA, rowptrM, colM, rows)
     n = rowptrA.numel() - 1
     if not 0 < n < (1 << 31):
         raise ValueError(f"A has {n} rows: int32 columns serve 1 .. 2^31 - 1")
     window_cols = int(window_cols)
-    if window_cols < 0 or window_cols % 64 or window_cols > two_hop_window_cols():
-        raise ValueError(f"window_cols must be 0 or a multiple of 64 up to {two_hop_window_cols()}, got {window_cols}")
+    if window_cols < 0 or window_cols % 64 or window_cols > window_limit():
+        raise ValueError(f"window_cols must be 0 or a multiple of 64 up to {window_limit()}, got {window_cols}")
     return Q, n
 
 
@@ -855,6 +856,40 @@ def two_hop_diff_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tens
               "ocn_two_hop_diff_fill")
         _mark("two_hop_diff_fill")
     return edges
+
+
+def two_hop_sums_window_cols() -> int:
+    """Columns of one LDS window of ``ocn_two_hop_sums_fill`` (a presence bit and an fp32 accumulator per column)."""
+    return int(_lib.lib().ocn_two_hop_sums_window_cols())
+
+
+@_on_device
+def two_hop_sums_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, off: Tensor,
+                      w: Optional[Tensor] = None, wcol: int = 0, drop_self: bool = True, total: Optional[int] = None,
+                      window_cols: int = 0) -> Tuple[Tensor, Tensor]:
+    """The pairs of ``two_hop_diff_fill`` for the same operands and, beside each pair (s, c), the sum of ``w[m, wcol]`` over the
+    m in row s of A whose row holds c, added in ascending m from 0.0f (ocn_hip.h: ocn_two_hop_sums_fill): (edges int64 [T, 2],
+    val float32 [T]).  ``w``: a float32 [n, 4] node table (``heuristics.node_table``), ``wcol`` its column; None: every weight
+    is 1, the sum counts the common neighbours.  ``off``: ``scan_i32(two_hop_diff_count(...))``, the one counting pass of both
+    fills; ``total`` as for ``row_diff_fill``.  ``window_cols``: 0, the library's window, except in tests of the sweep."""
+    Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols, two_hop_sums_window_cols)
+    if w is not None:
+        if _req(w, torch.float32, "w", 2).shape != (n, 4):
+            raise ValueError(f"w: expected the [{n}, 4] node table of A, got {tuple(w.shape)}")
+        if w.device != rows.device:
+            raise RuntimeError(f"two_hop_sums_fill: operands on different devices ({rows.device}, {w.device})")
+        wcol = int(wcol)
+        if not 0 <= wcol <= 3:
+            raise ValueError(f"wcol must be a column 0..3 of the node table, got {wcol}")
+    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
+    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    val = torch.empty(T, dtype=torch.float32, device=rows.device)
+    if Q and T:
+        check(_lib.lib().ocn_two_hop_sums_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
+                                               int(bool(drop_self)), int(window_cols), ptr(w), int(wcol) if w is not None else 0,
+                                               ptr(off), ptr(edges), ptr(val), stream_ptr()), "ocn_two_hop_sums_fill")
+        _mark("two_hop_sums_fill")
+    return edges, val
 
 
 def segment_topk_max_k() -> int:

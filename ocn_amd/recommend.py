@@ -11,7 +11,11 @@ made and return a flat score vector.  This module makes the pairs and picks from
   citation2 shapes — ``adj2=None`` expands the same set from A itself (``ops.two_hop_diff_count`` / ``_fill``) and the
   model scores it on the walk route (``pipeline.score_edges_walk``), as the drivers of those datasets score;
 * candidate lists are ragged — under a power law from a handful to tens of thousands per source — so the best ``k`` per
-  source are selected segment by segment (``ops.segment_topk``) instead of padding to a [Q, max_len] rectangle.
+  source are selected segment by segment (``ops.segment_topk``) instead of padding to a [Q, max_len] rectangle;
+* retrieve, then rank: the expansion from A that enumerates the candidates of ``s`` visits, for every neighbour ``m`` of ``s``,
+  every ``c`` in N(m) — adding the weight of ``m`` to an accumulator of column ``c`` there yields the cn / aa / ra score of
+  every candidate in the same pass (``two_hop_scored_candidates``, ``ops.two_hop_sums_fill``).  ``prefilter_candidates`` keeps
+  the ``m`` best per source and ``recommend_links(..., prefilter=(kind, m))`` lets the model rank only those.  Opt-in.
 
 Everything runs on one GPU; dealing the sources over several is not built here.
 """
@@ -74,6 +78,85 @@ def two_hop_candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources:
     return ptr, edges
 
 
+PATH_SUMS = ("cn", "aa", "ra")       # the heuristics that are a sum of a node weight over the 2-paths s - m - c
+
+
+def _check_path_sum(kind) -> str:
+    if kind not in PATH_SUMS:
+        raise ValueError(f"{kind!r} is no path sum: the 2-hop expansion scores one of {PATH_SUMS} "
+                         "(jaccard, pa and the 2-hop kinds are not sums over the common neighbours alone)")
+    return kind
+
+
+def two_hop_scored_candidates(adj: SparseTensor, sources: Tensor, kind: str,
+                              known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """``two_hop_candidates(adj, None, sources, known)`` with the heuristic score of every candidate from the same expansion:
+    (``ptr`` int64 [Q + 1], ``edges`` int64 [T, 2], ``val`` float32 [T]).  ``kind``: "cn", "aa" or "ra" — the path sums: the
+    pass that visits, for every neighbour ``m`` of ``s``, every ``c`` in N(m) adds the weight of ``m`` (1, 1 / log deg,
+    1 / deg: ``heuristics.node_table``) to the accumulator of column ``c`` (``ops.two_hop_sums_fill``), in ascending ``m``.
+    For a symmetric ``adj``, ``val`` equals ``heuristics.link_heuristics(adj, None, edges.t(), (kind,))[:, 0]`` bit for bit,
+    without an intersection per candidate."""
+    _check_path_sum(kind)
+    known = adj if known is None else known
+    if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
+        raise ValueError("sources must be a 1-d int64 tensor of node ids")
+    n = adj.size(0)
+    for name, m in (("adj", adj), ("known", known)):
+        if tuple(m.sparse_sizes()) != (n, n):
+            raise ValueError(f"{name} is {tuple(m.sparse_sizes())}, expected the square size ({n}, {n}) of adj")
+    sources = sources.contiguous()
+    w = None
+    if kind != "cn":
+        from .heuristics import node_table
+        w = node_table(adj)
+    rpa, cola, rpk, colk = adj._rowptr, adj._col, known._rowptr, known._col
+    with ops.prevalidated(sources, sources, n, n):
+        count = ops.two_hop_diff_count(rpa, cola, rpk, colk, sources, drop_self=True)
+        ptr = ops.scan_i32(count)
+        edges, val = ops.two_hop_sums_fill(rpa, cola, rpk, colk, sources, ptr, w, 1 if kind == "ra" else 0, drop_self=True)
+    return ptr, edges, val
+
+
+def _check_m(m) -> int:
+    m = int(m)
+    if not 1 <= m <= ops.segment_topk_max_k():
+        raise ValueError(f"m must be in 1..{ops.segment_topk_max_k()}, got {m}")
+    return m
+
+
+def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int,
+                         known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+    """The ``m`` best candidates of every source by a path-sum heuristic: (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2])
+    in the layout of ``two_hop_candidates``.  Per source the candidates of ``two_hop_scored_candidates`` are ranked in the total
+    order of ``segment_topk`` — higher ``val`` first, ties to the lower node id — the first ``m`` are kept (all of them where a
+    source has no more) and returned in ASCENDING node id, so that "ties go to the lower node id" still holds for whoever ranks
+    the retained list again.  ``1 <= m <= ops.segment_topk_max_k()``.  One host sync more than the candidates cost (the size of
+    the retained list)."""
+    _check_path_sum(kind)
+    m = _check_m(m)
+    ptr, edges, val = two_hop_scored_candidates(adj, sources, kind, known)
+    Q = ptr.numel() - 1
+    ptr_m = torch.zeros_like(ptr)
+    torch.cumsum((ptr[1:] - ptr[:-1]).clamp(max=m), 0, out=ptr_m[1:])
+    if Q == 0 or edges.shape[0] == 0:
+        return ptr_m, edges
+    _, pos = ops.segment_topk(val, ptr, m)
+    total = int(ptr_m[-1].item())
+    # positions into the flat list ascend with (source order, node id); the -1 pads of the short segments sort to the front
+    keep = pos.reshape(-1).sort().values[Q * m - total:]
+    return ptr_m, edges[keep]
+
+
+def _check_prefilter(prefilter, k: int) -> Tuple[str, int]:
+    if not isinstance(prefilter, (tuple, list)) or len(prefilter) != 2 or not isinstance(prefilter[0], str) \
+            or isinstance(prefilter[1], bool) or not isinstance(prefilter[1], int):
+        raise ValueError(f"prefilter must be None or (kind, m) with kind one of {PATH_SUMS} and m an int, got {prefilter!r}")
+    kind, m = _check_path_sum(prefilter[0]), _check_m(prefilter[1])
+    if k > m:
+        raise ValueError(f"prefilter keeps m = {m} candidates per source, fewer than k = {k}")
+    return kind, m
+
+
 def segment_topk(scores: Tensor, ptr: Tensor, k: int) -> Tuple[Tensor, Tensor]:
     """The ``k`` best scores of every segment ``scores[ptr[q]:ptr[q + 1]]``, best first: (values float32 [Q, k], positions
     int64 [Q, k] into ``scores``), padded with -inf and -1.  The order is total: the higher score first (+0.0 and -0.0 are
@@ -91,7 +174,8 @@ def _select(scores: Tensor, ptr: Tensor, edges: Tensor, k: int) -> Tuple[Tensor,
 
 @torch.no_grad()
 def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, k: int,
-                    batch_size: int, args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6) -> Tuple[Tensor, Tensor]:
+                    batch_size: int, args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6,
+                    prefilter: Optional[Tuple[str, int]] = None) -> Tuple[Tensor, Tensor]:
     """The ``k`` best predicted links of every source: (``dst`` int64 [Q, k], ``score`` float32 [Q, k]), best first, ``dst``
     = -1 and ``score`` = -inf where a source has fewer than ``k`` candidates.
 
@@ -111,7 +195,19 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
 
     The 3-hop predictor cn6 is served with ``adj2`` given: ``score_edges`` forms its third handle from ``adj`` and the bit rows
     of ``adj2`` (``utils.adjoverlap_3hop``), no A³ is stored.  With ``adj2=None`` it raises ValueError: the walk route has no
-    3-hop form."""
+    3-hop form.
+
+    ``prefilter=(kind, m)``, ``kind`` in ("cn", "aa", "ra") and ``k <= m <= ops.segment_topk_max_k()``: retrieve, then rank.
+    The candidates are short-listed by the heuristic first — ``prefilter_candidates(adj, sources, kind, m, known)``: the ``m``
+    best per source, expanded and scored from ``adj`` in one pass, whether or not ``adj2`` is given (the list equals that of
+    ``adj2`` where ``adj2`` has the pattern of A·A) — and the one scoring call above, ``score_edges`` with ``adj2`` given (cn6
+    included) and ``score_edges_walk`` without, sees the retained list only.  The contract is the same sentence: the scores
+    are exactly those the scoring loop returns for the flat RETAINED list at this ``batch_size``.  A batch of the retained list
+    holds other candidates than a batch of the full one, so batch-coupled cn5 / cn7 scores differ from the unfiltered run's;
+    with frozen column weights a retained pair's score is, within the frozen scoring tolerance, its score in the unfiltered
+    run, and the result differs from the unfiltered one only where the heuristic dropped a pair the model would have ranked
+    among the ``k`` best.  Where no source has more than ``m`` candidates the retained list is the full list and the result
+    is the unfiltered one.  ``prefilter=None``: every candidate is scored, as described above."""
     from .pipeline import score_edges, score_edges_walk
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
@@ -119,6 +215,14 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     from .model import CNLinkPredictor3hopCNs
     if adj2 is None and isinstance(predictor, CNLinkPredictor3hopCNs):
         raise ValueError("cn6 needs adj2 = adj @ adj: the walk route has no 3-hop form")
+    if prefilter is not None:
+        kind, m = _check_prefilter(prefilter, k)
+        ptr, edges = prefilter_candidates(adj, sources, kind, m, known)
+        if adj2 is None:
+            scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
+        else:
+            scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
+        return _select(scores, ptr, edges, k)
     ptr, edges = two_hop_candidates(adj, adj2, sources, known)
     if adj2 is None:
         scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
