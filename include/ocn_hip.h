@@ -809,6 +809,9 @@ int ocn_combine3(const float* coef, const float* x1, const float* x2, const floa
 int ocn_fill_rows(float* dst, int64_t ld, int32_t n_cols, const float* vec, const int64_t* row_range,
                   int64_t max_rows, void* stream);
 
+/* Refused (-1), never dropped: `addend` together with `dotw` (the dot epilogue stores one float per row and adds
+ * nothing), `y_row_map` without `dotw`, and an X, a stored Y (no `dotw`) or an addend that is not 16-byte aligned (rows
+ * are read and written as float4; the row strides are multiples of 4 floats).  N is checked for a launch without rows too. */
 typedef struct OcnLinearGroup {
   const float* X; int64_t ldX;       /* input [M][K], row stride in floats (0 = K) */
   int64_t M;

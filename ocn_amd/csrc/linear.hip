@@ -323,11 +323,17 @@ static int launch_linear(const LinArgs& a, int N, hipStream_t st) {
   return launch_status();
 }
 
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
 static int fill_group(LinGroup& g, const OcnLinearGroup& s, int K, int N) {
   if (s.M < 0 || (s.M > 0 && (!s.X || !s.Wp || !s.Y))) return OCN_EINVAL;
   if ((s.gamma == nullptr) != (s.beta == nullptr)) return OCN_EINVAL;
   const int64_t ldX = s.ldX ? s.ldX : K, ldY = s.ldY ? s.ldY : (s.dotw ? 1 : N), ldA = s.ldAdd ? s.ldAdd : N;
   if (ldX < K || (ldX & 3) || (!s.dotw && (ldY < N || (ldY & 3))) || (s.addend && (ldA < N || (ldA & 3)))) return OCN_EINVAL;
+  // the dot epilogue returns before the addend is read, and only it looks at y_row_map: neither is dropped silently
+  if ((s.addend && s.dotw) || (s.y_row_map && !s.dotw)) return OCN_EINVAL;
+  // X, a stored Y and the addend are accessed as float4
+  if (misaligned16(s.X) || (!s.dotw && misaligned16(s.Y)) || misaligned16(s.addend)) return OCN_EINVAL;
   g.X = s.X; g.ldX = ldX; g.M = s.M; g.Wp = (const __bf16*)s.Wp;
   g.bias = s.bias; g.gamma = s.gamma; g.beta = s.beta; g.scale = s.scale;
   g.addend = s.addend; g.ldAdd = ldA; g.dotw = s.dotw; g.dotb = s.dotb;
@@ -339,6 +345,7 @@ static int fill_group(LinGroup& g, const OcnLinearGroup& s, int K, int N) {
 
 int ocn_linear_grouped(const OcnLinearGroup* groups, int32_t n_groups, int32_t K, int32_t N, void* stream) {
   if (!groups || n_groups < 1 || n_groups > LIN_MAX_GROUPS || K <= 0 || (K % LIN_KS)) return OCN_EINVAL;
+  if (N != 32 && N != 64 && N != 128 && N != 256) return OCN_EINVAL;      // also for a launch without rows
   LinArgs a;
   a.n_groups = n_groups;
   a.K = K;

@@ -1877,7 +1877,8 @@ def linear_grouped(groups, K: int, N: int) -> None:
     x [M, >=K] (row stride may exceed K), weight [N, K], y (preallocated, row stride >= N, or [M, 1] with
     ``dot``), optional bias, ln=(gamma, beta, eps), relu, scale (device float[1]), addend [M, >=N] (or one
     row [1, N] with ``add_bcast``), dot=(w[1, N], b[1]), row_range (device int64[2]: only rows
-    [begin, end) of the buffers), y_row_map (device int64[M]: destination row of the dot output)."""
+    [begin, end) of the buffers), y_row_map (device int64[M]: destination row of the dot output).
+    ``dot`` with an addend and ``y_row_map`` without ``dot`` are refused, as ocn_linear_grouped refuses them."""
     if not 1 <= len(groups) <= 5:
         raise ValueError("1..5 groups")
     idx = groups[0]["x"].device.index
@@ -1891,22 +1892,27 @@ def linear_grouped(groups, K: int, N: int) -> None:
         _req_strided(x, "x"); _req_strided(y, "y")
         if x.shape[1] != K or tuple(w.shape) != (N, K) or x.shape[0] != y.shape[0]:
             raise ValueError("linear_grouped: shape mismatch")
-        panel = linear_panel(w)
-        keep.append(panel)
         ln = g.get("ln")
         dot = g.get("dot")
         add = g.get("addend")
+        if add is not None and dot is not None:
+            raise ValueError("linear_grouped: the dot epilogue takes no addend")
+        if g.get("y_row_map") is not None and dot is None:
+            raise ValueError("linear_grouped: y_row_map needs the dot epilogue")
+        if add is not None:
+            _req_strided(add, "addend")
+            if g.get("add_bcast") and add.shape != (1, N):
+                raise ValueError("add_bcast: addend must be [1, N]")
+        panel = linear_panel(w)
+        keep.append(panel)
         a.X, a.ldX, a.M, a.Wp = x.data_ptr(), x.stride(0), x.shape[0], panel.data_ptr()
         a.bias = 0 if g.get("bias") is None else g["bias"].data_ptr()
         a.gamma, a.beta, a.eps = (0, 0, 0.0) if ln is None else (ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2]))
         a.relu = int(bool(g.get("relu")))
         a.scale = 0 if g.get("scale") is None else g["scale"].data_ptr()
         if add is not None:
-            _req_strided(add, "addend")
             a.addend, a.ldAdd = add.data_ptr(), add.stride(0)
             a.add_bcast = int(bool(g.get("add_bcast")))
-            if a.add_bcast and add.shape != (1, N):
-                raise ValueError("add_bcast: addend must be [1, N]")
         rr, rm = g.get("row_range"), g.get("y_row_map")
         if rr is not None:
             _req(rr, torch.int64, "row_range", 1)
