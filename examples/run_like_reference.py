@@ -14,6 +14,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen # ... with column weights frozen on the validation edges
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
@@ -29,6 +30,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ocn_amd import ops                                                             # noqa: E402
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
+from ocn_amd.explain import explain_links                                           # noqa: E402
 from ocn_amd.frozen import freeze_columns                                           # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
@@ -159,6 +161,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     is checked to return the same rows.
     --recommend-prefilter KIND:M: the model ranks only the M best candidates of every source by the heuristic KIND (cn, aa, ra);
     with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
+    --recommend-explain M: the K winners of the printed sources are explained as ONE batch (ocn_amd.explain): per target the M
+    common neighbours that carry most of its score, with their two shares (via xcn1, via xcn2).
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
     --recommend-undo: the accepted links are then removed again, and the restored pair is compared with the original.
     --recommend-check-refresh: the refreshed node embeddings are compared with a full encoder pass after either update."""
@@ -217,6 +221,27 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             n_short = int(prefilter_candidates(adj, sources, kind, m)[0][-1])
             print(f"prefilter {kind}:{m} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
                   f"(the model ranked {n_short} of {n_all} candidates)", flush=True)
+    if args.recommend_explain:
+        # --recommend-explain M: why these links — gradient x input on the pooled vectors, per common neighbour.  The winners form one
+        # batch of their own: an unfrozen cn5 / cn7 weighs them by THAT batch's column statistics, so only a frozen predictor (or
+        # cn8, which has no column weights) is explained at the scores the recommendation printed
+        h = state.h if state is not None else model(data.x, adj)
+        won = torch.stack([sources.view(-1, 1).expand_as(dst).reshape(-1), dst.reshape(-1)], dim=1)
+        listed = won[:, 1] >= 0
+        won = won[listed].contiguous()
+        if won.shape[0]:
+            exp = explain_links(predictor, h, adj, adj2, won, m=args.recommend_explain, args=args)
+            frozen = predictor._frozen is not None
+            diff = (exp.score - score.reshape(-1)[listed]).abs().max().item()
+            print(f"explain: {won.shape[0]} links as one batch, predictor frozen = {frozen}; max |explained score - recommended "
+                  f"score| = {diff:.2e}" + ("" if frozen else " (not frozen: the batch's own column weights, scores may differ)"),
+                  flush=True)
+            if frozen and not torch.allclose(exp.score, score.reshape(-1)[listed], rtol=1e-5, atol=1e-5):
+                raise SystemExit("--recommend-explain: a frozen predictor's explained scores differ from the recommendation's")
+            for (s, t), v, ks, cs, share in zip(won.tolist(), exp.score.tolist(), exp.nodes.tolist(), exp.contrib.tolist(),
+                                                exp.pooled.tolist()):
+                print(f"explain source {s} target {t} score {v:.4f} pooled {share[0]:+.4f} {share[1]:+.4f} top-{args.recommend_explain}: "
+                      + " ".join(f"{n}({a:+.4f},{b:+.4f})" for n, (a, b) in zip(ks, cs) if n >= 0), flush=True)
     if args.recommend_accept > 0:
         # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
         # updated, not rebuilt; the node embeddings are refreshed row by row, EncoderState) and the same sources are asked again
@@ -287,6 +312,9 @@ def main(argv=None):
     ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M",
                     help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
                          "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
+    ap.add_argument("--recommend-explain", type=int, default=0, metavar="M",
+                    help="with --recommend and a cn5 / cn7 / cn8 model: explain the K winners of the printed sources as one batch "
+                         "(ocn_amd.explain) and print each target's top-M common neighbours with their two contributions")
     ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
                     help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
     ap.add_argument("--recommend-undo", action="store_true",
@@ -304,6 +332,9 @@ def main(argv=None):
         ap.error("--recommend-walk: a 2-hop heuristic intersects with the rows of A²")
     if args.recommend_frozen and (args.heuristic or not args.recommend or args.predictor not in ("cn5", "cn7")):
         ap.error("--recommend-frozen: needs --recommend K and a cn5 or cn7 model")
+    if args.recommend_explain and (args.heuristic or not args.recommend or args.predictor == "cn6"
+                                   or not 1 <= args.recommend_explain <= 128):
+        ap.error("--recommend-explain M: needs --recommend K, a cn5, cn7 or cn8 model and 1 <= M <= 128")
     if args.recommend_prefilter:
         kind, _, m = args.recommend_prefilter.partition(":")
         if args.heuristic or not args.recommend or kind not in ("cn", "aa", "ra") or not m.isdigit() or not args.recommend <= int(m) <= 128:

@@ -48,7 +48,8 @@ extern "C" {
  *    of A², without a stored A³); ocn_cn_flags_pair_min_batch (the intersection pass takes two slots per wave at large batches;
  *    same bits); ocn_cn_pool_frozen (cn5 / cn7 pooled with a frozen column-weight table: intersection and weighted pooling in
  *    one pass); ocn_two_hop_sums_window_cols, ocn_two_hop_sums_fill (the 2-hop candidates with their cn / aa / ra path sums:
- *    the retrieval half of two-stage recommendation). */
+ *    the retrieval half of two-stage recommendation); ocn_cn_attribution (explaining a predicted link: the share of every
+ *    common neighbour in the pooled vectors' part of a score). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -352,6 +353,30 @@ int ocn_cn_pool_frozen(const int64_t* rowptrA, const int32_t* colA,
                        const int64_t* src, const int64_t* dst, const int64_t* order /* or NULL */, int64_t B, int64_t n_cols,
                        const float* weights /* [n_cols][4] */, const float* h, int32_t H,
                        float* xcn1, float* xcn2, float* xij, int32_t* cnt1, int32_t* cnt2, void* stream);
+/* Per-common-neighbour attribution (ocn_amd/explain.py): the sampled dense-dense product on the CN pattern of a batch whose
+ * intersection pass has run.  off [B + 1], flags, wc (or NULL: pattern route) and flags_cap are that pass's; weights is the
+ * [n_cols][4] table {w1, t, inv2, 0} the batch is pooled with (its own, a frozen one, cn8's unit table); g1 / g2 [B][H] are
+ * the gradients of a score with respect to xcn1[e] / xcn2[e].  For candidate e, position p of row src[e] of A
+ * (off[e + 1] - off[e] = the length of that row) and q = off[e] + p:
+ *   k = colA[rowptrA[src[e]] + p]   f = flags[q]   c = wc ? (float)wc[q] : 1   (wa, wb) = the entry weights ocn_cn_gather
+ *   pools that entry with:  wa = [f & 1] * weights[k][0]   wb = ([f & 2] * c - [f & 1] * weights[k][1]) * weights[k][2]
+ *   f == 0 (no member):  attr[q] = {+0, +0}, rank[q] = -inf
+ *   else, all in fp32:   d1 = sum_f h[k][f] * g1[e][f]   d2 = sum_f h[k][f] * g2[e][f]
+ *                        attr[q] = {wa != 0 ? wa * d1 : +0, wb != 0 ? wb * d2 : +0}   rank[q] = attr[q][0] + attr[q][1]
+ * so that sum_q attr[q][0] = <g1[e], xcn1[e]> and sum_q attr[q][1] = <g2[e], xcn2[e]> up to rounding.  h[k] is read exactly
+ * when wa != 0 or wb != 0 (the pooling's fetch rule).  Every position of [off[e], off[e + 1]) of every batch row is written,
+ * nothing at or beyond flags_cap, nothing in [off[B], flags_cap).  The order of the additions of a dot product depends on H
+ * only — not on the launch geometry, on `order` (an optional processing order, a permutation of the batch rows) or on the
+ * rest of the batch: the output is fixed by the input.  No atomics, no workspace, no LDS.
+ * H in {16, 32, 64, 128, 256, 512}; weights, h, g1, g2 16-byte aligned, attr 8-byte aligned.  NULL required pointers, B < 0,
+ * flags_cap < 0, another H or a misaligned pointer: OCN_EINVAL before any HIP call.  B == 0 returns 0 without a launch. */
+int ocn_cn_attribution(const int64_t* rowptrA, const int32_t* colA, const int64_t* src,
+                       const int64_t* order /* or NULL */, int64_t B,
+                       const int64_t* off /* [B + 1] */, const uint8_t* flags, const int32_t* wc /* or NULL */,
+                       int64_t flags_cap, const float* weights /* [n_cols][4] */,
+                       const float* h /* [n_cols][H] */, int32_t H,
+                       const float* g1 /* [B][H] */, const float* g2 /* [B][H] */,
+                       float* attr /* [flags_cap][2] */, float* rank /* [flags_cap] */, void* stream);
 /* Link heuristics (common neighbours, Adamic-Adar, resource allocation, Jaccard, preferential attachment and their 2-hop
  * forms: ocn_amd/heuristics.py) in ONE pass, the shape of ocn_cn8_pool with a 16-byte node row in place of an embedding row:
  *   sum1[e][q] = sum_{k in N(i) ∩ T1(j)} w[k][q]   sum2[e][q] = sum_{k in N(i) ∩ T2(j)} w[k][q]   q = 0..3

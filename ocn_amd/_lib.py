@@ -59,6 +59,7 @@ SIGNATURES = {
                                _P, _P, _P, _P]),
     "ocn_cn_pool_frozen": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, c_int32, _P,
                                      _P, _P, _P, _P, _P]),
+    "ocn_cn_attribution": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P]),
     "ocn_cn_node_sums": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ocn_row_diff_stage_cols": (c_int32, []),

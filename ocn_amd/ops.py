@@ -728,6 +728,42 @@ def cn_pool_frozen(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Te
 
 
 @_on_device
+def cn_attribution(rowptrA: Tensor, colA: Tensor, src: Tensor, off: Tensor, flags: Tensor, wc: Optional[Tensor], weights: Tensor,
+                   h: Tensor, g1: Tensor, g2: Tensor, order: Optional[Tensor] = None, wsd=None) -> Tuple[Tensor, Tensor]:
+    """The share of every common neighbour in <g1[e], xcn1[e]> and <g2[e], xcn2[e]> (ocn_hip.h: ocn_cn_attribution).  ``off``,
+    ``flags``, ``wc`` (None on the pattern route) and ``order`` are a batch state's (``CNState``), ``weights`` the [N, 4] table
+    that state is pooled with, ``g1`` / ``g2`` float32 [B, H] the gradients with respect to its pooled rows.  Returns
+    (attr float32 [flags.numel(), 2], rank float32 [flags.numel()]): per flag position {via xcn1, via xcn2} and their sum, -inf
+    on positions that are no member.  Only the positions below ``off[-1]`` are written."""
+    _req(rowptrA, torch.int64, "rowptrA", 1); _req(colA, torch.int32, "colA", 1)
+    B = _req(src, torch.int64, "src", 1).numel()
+    if _req(off, torch.int64, "off", 1).numel() != B + 1:
+        raise ValueError("off: [B + 1] offsets, one per candidate and the total")
+    cap = _req(flags, torch.uint8, "flags", 1).numel()
+    if wc is not None and _req(wc, torch.int32, "wc", 1).numel() < cap:
+        raise ValueError("wc: one walk count per flag byte")
+    N, H = _req(h, torch.float32, "h", 2).shape
+    if H not in LN_WIDTHS:
+        raise NotImplementedError(f"the attribution supports hidden widths {LN_WIDTHS}, got {H}")
+    if tuple(_req(weights, torch.float32, "weights", 2).shape) != (N, 4):
+        raise ValueError(f"weights must be [N, 4] with N = h.shape[0] = {N}, got {tuple(weights.shape)}")
+    for name, g in (("g1", g1), ("g2", g2)):
+        if tuple(_req(g, torch.float32, name, 2).shape) != (B, H):
+            raise ValueError(f"{name} must be [B, H] = [{B}, {H}], got {tuple(g.shape)}")
+    for name, t in (("weights", weights), ("h", h), ("g1", g1), ("g2", g2)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name} must be 16-byte aligned")
+    _order_arg(order, B)
+    attr = buf(wsd, "attr", (cap, 2), torch.float32, h.device)
+    rank = buf(wsd, "attr_rank", cap, torch.float32, h.device)
+    check(_lib.lib().ocn_cn_attribution(ptr(rowptrA), ptr(colA), ptr(src), ptr(order), B, ptr(off), ptr(flags), ptr(wc), cap,
+                                        ptr(weights), ptr(h), H, ptr(g1), ptr(g2), ptr(attr), ptr(rank), stream_ptr()),
+          "ocn_cn_attribution")
+    _mark("cn_attribution")
+    return attr, rank
+
+
+@_on_device
 def cn_node_sums(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Optional[Tensor], Optional[Tensor]]],
                  t2: Optional[Tuple[Optional[Tensor], Optional[Tensor]]], src: Tensor, dst: Tensor, w: Tensor,
                  t1_bitmap: Optional[Tensor] = None, t2_bitmap: Optional[Tensor] = None, order: Optional[Tensor] = None, wsd=None,
