@@ -14,12 +14,14 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen # ... with column weights frozen on the validation edges
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -36,7 +38,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.recommend import (prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
-                               two_hop_candidates)
+                               three_hop_candidates, two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
@@ -161,6 +163,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     is checked to return the same rows.
     --recommend-prefilter KIND:M: the model ranks only the M best candidates of every source by the heuristic KIND (cn, aa, ra);
     with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
+    --recommend-hops 3: the candidates within three hops (every target with a non-empty cn1 or cn2), expanded from the adjacency;
+    the prefilter is then KIND:M:DECAY and ranks them by the local path index P2 + DECAY * P3.
     --recommend-explain M: the K winners of the printed sources are explained as ONE batch (ocn_amd.explain): per target the M
     common neighbours that carry most of its score, with their two shares (via xcn1, via xcn2).
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
@@ -185,10 +189,11 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
 
     def top(adj, adj2, tag):
         if args.heuristic:
-            dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic)
+            dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic, hops=args.recommend_hops)
         else:
             h = state.h if state is not None else model(data.x, adj)
-            dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, prefilter=args.recommend_prefilter)
+            dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, prefilter=args.recommend_prefilter,
+                                         hops=args.recommend_hops)
         for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
             print(f"{tag} source {s} top-{k}: " + " ".join(str(t) for t in d) + "  scores: " + " ".join(f"{x:.4f}" for x in v),
                   flush=True)
@@ -206,7 +211,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     if args.recommend_frozen:
         h = state.h if state is not None else model(data.x, adj)
         _, half = recommend_links(predictor, h, adj, adj2, sources[::2].contiguous(), k, max(args.testbs // 3, 1), args,
-                                  prefilter=args.recommend_prefilter)    # (like with like: a source's short list is its own)
+                                  prefilter=args.recommend_prefilter, hops=args.recommend_hops)    # (like with like: a source's short list is its own)
         same = torch.allclose(half, score[::2], rtol=1e-5, atol=1e-5)
         print(f"a call for every second source at a third of the batch size returns the same rows = {same}", flush=True)
         if not same:
@@ -214,12 +219,19 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         if args.recommend_prefilter:
             # how many of the unfiltered top-K the short list kept: printed only — a synthetic graph under an untrained or briefly
             # trained model supports no claim about the quality of a prefilter
-            full, _ = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args)
+            full, _ = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, hops=args.recommend_hops)
             kept = int(((dst[:, :, None] == full[:, None, :]) & (full[:, None, :] >= 0)).any(1).sum())
-            kind, m = args.recommend_prefilter
-            n_all = int(two_hop_candidates(adj, adj2, sources)[0][-1])
-            n_short = int(prefilter_candidates(adj, sources, kind, m)[0][-1])
-            print(f"prefilter {kind}:{m} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
+            if args.recommend_hops == 3:
+                kind, m, decay = args.recommend_prefilter
+                n_all = int(three_hop_candidates(adj, sources)[0][-1])
+                n_short = int(prefilter_candidates(adj, sources, kind, m, hops=3, decay=decay)[0][-1])
+                name = f"{kind}:{m}:{decay:g} over 3 hops"
+            else:
+                kind, m = args.recommend_prefilter
+                n_all = int(two_hop_candidates(adj, adj2, sources)[0][-1])
+                n_short = int(prefilter_candidates(adj, sources, kind, m)[0][-1])
+                name = f"{kind}:{m}"
+            print(f"prefilter {name} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
                   f"(the model ranked {n_short} of {n_all} candidates)", flush=True)
     if args.recommend_explain:
         # --recommend-explain M: why these links — gradient x input on the pooled vectors, per common neighbour.  The winners form one
@@ -309,7 +321,10 @@ def main(argv=None):
     ap.add_argument("--recommend-frozen", action="store_true",
                     help="with --recommend and a cn5 / cn7 model: freeze the column weights on the validation positives "
                          "(ocn_amd.frozen) so that a source's scores do not depend on the other sources or the batch size")
-    ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M",
+    ap.add_argument("--recommend-hops", type=int, default=2, choices=(2, 3),
+                    help="with --recommend: candidates within this many hops (recommend_links(hops=...)); 3 reaches the pairs whose "
+                         "only evidence is cn2, and takes --recommend-prefilter KIND:M:DECAY")
+    ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M[:DECAY]",
                     help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
                          "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
     ap.add_argument("--recommend-explain", type=int, default=0, metavar="M",
@@ -335,11 +350,24 @@ def main(argv=None):
     if args.recommend_explain and (args.heuristic or not args.recommend or args.predictor == "cn6"
                                    or not 1 <= args.recommend_explain <= 128):
         ap.error("--recommend-explain M: needs --recommend K, a cn5, cn7 or cn8 model and 1 <= M <= 128")
+    if args.recommend_hops != 2 and not args.recommend:
+        ap.error("--recommend-hops: needs --recommend K")
     if args.recommend_prefilter:
-        kind, _, m = args.recommend_prefilter.partition(":")
+        parts = args.recommend_prefilter.split(":")
+        kind, m, decay = parts[0], "".join(parts[1:2]), parts[2:]
         if args.heuristic or not args.recommend or kind not in ("cn", "aa", "ra") or not m.isdigit() or not args.recommend <= int(m) <= 128:
             ap.error("--recommend-prefilter KIND:M: needs a model, --recommend K, KIND one of cn, aa, ra and K <= M <= 128")
+        if len(decay) != args.recommend_hops - 2:
+            ap.error("--recommend-prefilter: KIND:M with --recommend-hops 2, KIND:M:DECAY with --recommend-hops 3")
         args.recommend_prefilter = (kind, int(m))
+        if decay:
+            try:
+                d = float(decay[0])
+            except ValueError:
+                d = -1.0
+            if not (math.isfinite(d) and d >= 0):
+                ap.error("--recommend-prefilter KIND:M:DECAY: DECAY is a finite number >= 0")
+            args.recommend_prefilter += (d,)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

@@ -49,7 +49,9 @@ extern "C" {
  *    same bits); ocn_cn_pool_frozen (cn5 / cn7 pooled with a frozen column-weight table: intersection and weighted pooling in
  *    one pass); ocn_two_hop_sums_window_cols, ocn_two_hop_sums_fill (the 2-hop candidates with their cn / aa / ra path sums:
  *    the retrieval half of two-stage recommendation); ocn_cn_attribution (explaining a predicted link: the share of every
- *    common neighbour in the pooled vectors' part of a score). */
+ *    common neighbour in the pooled vectors' part of a score); ocn_frontier_window_cols, ocn_frontier_count,
+ *    ocn_frontier_sums_fill (frontier expansion with ordered path sums: chained, the candidates within three hops and their
+ *    local path index). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -400,7 +402,8 @@ int ocn_cn_node_sums(const int64_t* rowptrA, const int32_t* colA,
 /* Candidate generation for link recommendation (ocn_amd/recommend.py): the row difference of two CSR matrices with the same
  * rows, for the rows a caller names.  For query q with s = rows[q] (int64; a source may repeat, its rows may be empty) the
  * set is P[s,:] \ M[s,:], without column s too when drop_self != 0, in ascending column order.  With P = the pattern of A²
- * and M = A that is the 2-hop neighbourhood of s that is not yet linked: the targets with a non-empty cn1 or cn2.
+ * and M = A that is the 2-hop neighbourhood of s that is not yet linked: the targets with a non-empty cn1.  (cn2 = N(s) ∩
+ * pattern(A² row t) is non-empty for every target within THREE hops: those come from ocn_frontier_*, below.)
  * Two phases around a caller-side allocation, as for the A*A pattern: count -> ocn_scan_i32 -> fill.
  *   count[q] (int32) = the size of query q's set;
  *   edges (int64 [T][2], T = off[Q], 16-byte aligned) takes the pairs (s, c) of query q row-major from edges[off[q]] on: the
@@ -467,6 +470,51 @@ int ocn_two_hop_sums_fill(const int64_t* rowptrA, const int32_t* colA, const int
                           const float* w /* [n_cols][4] row-major, or NULL: every weight 1.0f */,
                           int32_t wcol /* 0 .. 3, ignored when w == NULL */, const int64_t* off /* [Q + 1] */,
                           int64_t* edges /* [off[Q]][2] */, float* val /* [off[Q]] */, void* stream);
+/* Frontier expansion with ordered path sums: ocn_two_hop_sums_fill with the frontier made explicit, so that expansions chain —
+ * the output of one is the frontier (and the seed) of the next, one hop per launch.  For query q with s = rows[q]:
+ *   the frontier F_q: the entries ptrF[q] .. ptrF[q + 1] of a pair list — node c = nodeF[2 i + 1] (the second word of pair i: the
+ *   int64 [T][2] layout the fills of this family write, its first word is not read), weight f_c = valF[i] (fp32; valF == NULL:
+ *   every weight is 1.0f) — ascending in c and duplicate-free;
+ *   the seeds S_q (ptrS == nodeS == NULL: none): the same layout, node t and value v_t = valS[i], ascending and duplicate-free.
+ * The set is ( U_{c in F_q} A[c,:]  U  nodes(S_q) ) \ M[s,:], without column s too when drop_self != 0, in ascending column
+ * order; val of the pair (s, t) = v_t where t is seeded, else 0.0f, plus f_c for every c in F_q whose row holds t, the adds in
+ * ASCENDING c, one fp32 add per member, plain adds without contraction.  Membership is the presence bit, never val != 0.
+ * With F_q = the row of s in A weighted by a node table and no seeds that is ocn_two_hop_diff_count / ocn_two_hop_sums_fill,
+ * bit for bit.  With F = the unexcluded 2-hop expansion L2 of s, f_c = decay * w[c] * P2(s, c), the seeds (L2, P2) and M = the
+ * known links, val = P2 + decay * P3: the candidates within three hops — every target with a non-empty cn1 or cn2 — and
+ * their local path index.
+ * The protocol is that of ocn_two_hop_diff_* / ocn_two_hop_sums_fill word for word: count -> ocn_scan_i32 -> fill, count[q]
+ * int32, edges int64 [off[Q]][2] pairs (s, t) row-major, a pair that would land at off[q + 1] or beyond is dropped, and so is
+ * its value; a source may repeat, a list may be empty, a frontier node may have an empty row.  ocn_frontier_sums_fill with
+ * val == NULL writes the pairs alone (valF and valS are then not read).
+ * One kernel body for the three passes.  A workgroup owns a query; a window keeps one presence bit and (with values) one fp32
+ * accumulator per column in LDS, ocn_frontier_window_cols() columns (38 208, a multiple of 64), and any n_cols < 2^31 is swept
+ * in such windows.  Each of the four waves owns a contiguous quarter of the window's columns, enters the seeds of its quarter
+ * and then walks the whole frontier in ascending order, 64 entries at a time: entries with one column in the quarter add side
+ * by side — lanes that meet in a column take turns in lane order through a claim table in LDS — entries with several are walked
+ * by the wave.  An accumulator is touched by one wave only, in program order: LDS atomics on the presence bits and the claim
+ * table alone, no float atomics, no global atomics, no workspace — the output is fixed by the input.
+ * window_cols: 0 = the default, else a positive multiple of 64 no larger than it (for tests of the sweep on small graphs).
+ * The launch has at most 4 096 workgroups; beyond that many queries a workgroup takes several, grid-stride.
+ * LDS: min(window_cols, n_cols rounded up to 64) / 8 bytes, * 33 / 8 with values, and 4 KiB of claim tables with values.
+ * A and M: square, n_cols rows and columns, sorted duplicate-free int32 columns.  rows[] and the nodes of both lists must be
+ * valid row ids, the lists sorted (not checked here).
+ * NULL rowptrA / colA / rowptrM / colM / rows / ptrF / nodeF / count resp. off / edges, ptrS without nodeS or the reverse, seeds
+ * without valS where val is written, Q < 0, n_cols <= 0 or >= 2^31, a bad window_cols: OCN_EINVAL before any HIP call.
+ * Q == 0 returns 0. */
+int64_t ocn_frontier_window_cols(void);
+int ocn_frontier_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM, int64_t n_cols,
+                       const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols /* 0: the default */,
+                       const int64_t* ptrF /* [Q + 1] */, const int64_t* nodeF /* [ptrF[Q]][2] */,
+                       const int64_t* ptrS /* [Q + 1] or NULL */, const int64_t* nodeS /* [ptrS[Q]][2] or NULL */,
+                       int32_t* count /* [Q] */, void* stream);
+int ocn_frontier_sums_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self,
+                           int64_t window_cols /* 0: the default */, const int64_t* ptrF /* [Q + 1] */,
+                           const int64_t* nodeF /* [ptrF[Q]][2] */, const float* valF /* [ptrF[Q]] or NULL: every weight 1.0f */,
+                           const int64_t* ptrS /* [Q + 1] or NULL */, const int64_t* nodeS /* [ptrS[Q]][2] or NULL */,
+                           const float* valS /* [ptrS[Q]] */, const int64_t* off /* [Q + 1], from ocn_scan_i32 */,
+                           int64_t* edges /* [off[Q]][2] */, float* val /* [off[Q]] or NULL: not written */, void* stream);
 /* The k best entries of every segment scores[ptr[q] .. ptr[q + 1]) of a flat fp32 vector, best first, 1 <= k <=
  * ocn_segment_topk_max_k() (128: two slots per lane).  top_val [Q][k] = the scores, top_pos [Q][k] (int64) = their positions
  * in the FLAT vector, so that one index gathers whatever else the caller keeps per entry; a segment with fewer than k

@@ -70,6 +70,10 @@ SIGNATURES = {
     "ocn_two_hop_diff_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, _P]),
     "ocn_two_hop_sums_window_cols": (c_int64, []),
     "ocn_two_hop_sums_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, c_int32, _P, _P, _P, _P]),
+    "ocn_frontier_window_cols": (c_int64, []),
+    "ocn_frontier_count": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, _P, _P, _P, _P]),
+    "ocn_frontier_sums_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                         _P]),
     "ocn_segment_topk_max_k": (c_int32, []),
     "ocn_segment_topk": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     "ocn_philox4x32": (c_int32, [_P, ctypes.c_uint32, ctypes.c_uint32, c_int64, _P, _P]),

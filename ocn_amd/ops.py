@@ -928,6 +928,97 @@ def two_hop_sums_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tens
     return edges, val
 
 
+prefilter_budget = 1 << 26       # candidates of one chunk of a 3-hop short list (recommend.prefilter_candidates): 1.3 GB at 20 B each
+
+
+def frontier_window_cols() -> int:
+    """Columns of one LDS window of ``ocn_frontier_count`` / ``ocn_frontier_sums_fill``."""
+    return int(_lib.lib().ocn_frontier_window_cols())
+
+
+def _frontier_list(lptr: Tensor, pairs: Tensor, val: Optional[Tensor], Q: int, n: int, name: str, device) -> Tensor:
+    """The checks of one per-query list (the frontier or the seeds): ``lptr`` int64 [Q + 1], ``pairs`` int64 [T, 2] (the node
+    is the second of a pair: the layout the fills write), ``val`` float32 [T] or None.  Node ids are range-checked through
+    ``check_edges`` (waived inside ``prevalidated``, like every id check), and with them ``lptr[-1] <= T``.  That a query's
+    nodes ascend is trusted, as for CSR columns.  Returns the pair tensor the entry is handed (never an empty one: the entry
+    refuses NULL)."""
+    if _req(lptr, torch.int64, f"ptr{name}", 1).numel() != Q + 1:
+        raise ValueError(f"ptr{name}: one entry per query and the total")
+    if _req(pairs, torch.int64, f"node{name}", 2).shape[1] != 2:
+        raise ValueError(f"node{name}: expected the [T, 2] pair layout, got {tuple(pairs.shape)}")
+    T = pairs.shape[0]
+    if val is not None and _req(val, torch.float32, f"val{name}", 1).numel() != T:
+        raise ValueError(f"val{name}: expected one value per pair of node{name} ({T}), got {val.numel()}")
+    for t in (lptr, pairs, val):
+        if t is not None and t.device != device:
+            raise RuntimeError(f"frontier: operands on different devices ({device}, {t.device})")
+    if validate_indices and (n, n) not in getattr(_checked, "scopes", ()):
+        if T:
+            nodes = pairs[:, 1].contiguous()
+            check_edges(nodes, nodes, n, n)
+        if Q and not 0 <= int(lptr[-1].item()) <= T:
+            raise IndexError(f"ptr{name}: the total exceeds the {T} pairs of node{name}")
+    return pairs if T else pairs.new_zeros(1, 2)
+
+
+def _frontier_args(rowptrA, colA, rowptrM, colM, rows, window_cols, ptrF, nodeF, valF, ptrS, nodeS, valS):
+    Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols, frontier_window_cols)
+    if (ptrS is None) != (nodeS is None):
+        raise ValueError("seeds: ptrS and nodeS are given together or not at all")
+    nodeF = _frontier_list(ptrF, nodeF, valF, Q, n, "F", rows.device)
+    if ptrS is not None:
+        nodeS = _frontier_list(ptrS, nodeS, valS, Q, n, "S", rows.device)
+    if colM.numel() == 0:
+        colM = colM.new_zeros(1)                                           # (an empty M: no row reads it, the entry still wants a pointer)
+    return Q, n, colM, nodeF, nodeS
+
+
+@_on_device
+def frontier_count(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, ptrF: Tensor, nodeF: Tensor,
+                   ptrS: Optional[Tensor] = None, nodeS: Optional[Tensor] = None, drop_self: bool = True,
+                   window_cols: int = 0) -> Tensor:
+    """count[q] = |(U_{c in F_q} A[c,:] U nodes(S_q)) \\ M[s,:]| for s = rows[q], without column s too under ``drop_self``
+    (ocn_hip.h: ocn_frontier_count): int32 [Q].  ``ptrF`` int64 [Q + 1] and ``nodeF`` int64 [T, 2] are a per-query frontier list
+    in the layout the fills write (the node is the second of a pair), ascending and duplicate-free per query; ``ptrS`` /
+    ``nodeS``: the optional seed list, the same layout.  ``window_cols``: 0, the library's window, except in tests of the sweep."""
+    Q, n, colM, nodeF, nodeS = _frontier_args(rowptrA, colA, rowptrM, colM, rows, window_cols, ptrF, nodeF, None, ptrS, nodeS, None)
+    count = torch.empty(Q, dtype=torch.int32, device=rows.device)
+    if Q:
+        check(_lib.lib().ocn_frontier_count(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
+                                            int(bool(drop_self)), int(window_cols), ptr(ptrF), ptr(nodeF), ptr(ptrS), ptr(nodeS),
+                                            ptr(count), stream_ptr()), "ocn_frontier_count")
+        _mark("frontier_count")
+    return count
+
+
+@_on_device
+def frontier_sums_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, ptrF: Tensor, nodeF: Tensor,
+                       valF: Optional[Tensor], ptrS: Optional[Tensor], nodeS: Optional[Tensor], valS: Optional[Tensor],
+                       off: Tensor, drop_self: bool = True, total: Optional[int] = None, window_cols: int = 0,
+                       values: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """The pairs (s, t) of every query's set, ascending in t, from ``off[q]`` on and, beside each, its ordered path sum
+    (ocn_hip.h: ocn_frontier_sums_fill): (edges int64 [T, 2], val float32 [T]).  val = the seed value of t (``valS``, 0.0f where t
+    is no seed) plus ``valF`` of every frontier node whose row holds t, one fp32 add each in ascending node id.  ``valF`` None:
+    every weight is 1.  ``values=False``: the pairs alone, (edges, None); ``valF`` and ``valS`` are then not read.  ``off``:
+    ``scan_i32(frontier_count(...))`` of the same operands; ``total`` as for ``row_diff_fill``.  The output is itself a list in
+    the layout ``ptrF`` / ``nodeF`` / ``valF`` take: expansions chain without a conversion."""
+    Q, n, colM, nodeF, nodeS = _frontier_args(rowptrA, colA, rowptrM, colM, rows, window_cols, ptrF, nodeF,
+                                              valF if values else None, ptrS, nodeS, valS if values else None)
+    if values and ptrS is not None and valS is None:
+        raise ValueError("valS: seeds need their values where val is written")
+    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
+    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    val = torch.empty(T, dtype=torch.float32, device=rows.device) if values else None
+    if Q and T:
+        check(_lib.lib().ocn_frontier_sums_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
+                                                int(bool(drop_self)), int(window_cols), ptr(ptrF), ptr(nodeF),
+                                                ptr(valF if values else None), ptr(ptrS), ptr(nodeS),
+                                                ptr(valS if values and ptrS is not None else None), ptr(off), ptr(edges), ptr(val),
+                                                stream_ptr()), "ocn_frontier_sums_fill")
+        _mark("frontier_sums_fill")
+    return edges, val
+
+
 def segment_topk_max_k() -> int:
     return int(_lib.lib().ocn_segment_topk_max_k())
 

@@ -3,9 +3,10 @@
 The scoring loops (``pipeline.score_edges``, ``heuristics.score_edges_heuristic``) take candidate pairs that somebody else
 made and return a flat score vector.  This module makes the pairs and picks from the scores, both on the device:
 
-* the natural candidate set of a common-neighbour predictor is the 2-hop neighbourhood of a source that is not yet linked,
-  ``pattern(A² row s) \\ (N(s) ∪ {s})`` — any other target has empty ``cn1`` and ``cn2`` and is scored from ``x_i ⊙ x_j``
-  alone.  ``two_hop_candidates`` enumerates that set difference row by row (``ops.row_diff_count`` -> ``ops.scan_i32`` ->
+* the default candidate set of a common-neighbour predictor is the 2-hop neighbourhood of a source that is not yet linked,
+  ``pattern(A² row s) \\ (N(s) ∪ {s})`` — any other target has an empty ``cn1``.  (Not an empty ``cn2``: ``cn2(s, t) = N(s) ∩
+  pattern(A² row t)`` is non-empty for every target within THREE hops; ``hops=3`` below serves those.)
+  ``two_hop_candidates`` enumerates that set difference row by row (``ops.row_diff_count`` -> ``ops.scan_i32`` ->
   ``ops.row_diff_fill``) straight into the [T, 2] layout the scoring loops take: no dense [Q, N] mask, no host loop;
 * where A² is not stored — more columns than the A·A pattern kernel takes, or a product too large to keep, the ppa and
   citation2 shapes — ``adj2=None`` expands the same set from A itself (``ops.two_hop_diff_count`` / ``_fill``) and the
@@ -15,7 +16,14 @@ made and return a flat score vector.  This module makes the pairs and picks from
 * retrieve, then rank: the expansion from A that enumerates the candidates of ``s`` visits, for every neighbour ``m`` of ``s``,
   every ``c`` in N(m) — adding the weight of ``m`` to an accumulator of column ``c`` there yields the cn / aa / ra score of
   every candidate in the same pass (``two_hop_scored_candidates``, ``ops.two_hop_sums_fill``).  ``prefilter_candidates`` keeps
-  the ``m`` best per source and ``recommend_links(..., prefilter=(kind, m))`` lets the model rank only those.  Opt-in.
+  the ``m`` best per source and ``recommend_links(..., prefilter=(kind, m))`` lets the model rank only those.  Opt-in;
+* three hops: a pair at distance exactly 3 has an empty ``cn1`` and a non-empty ``cn2`` — its only evidence is the higher-order
+  common neighbours.  For a symmetric ``adj``, ``{t : cn1 or cn2 non-empty} \\ (N(s) ∪ {s})`` is ``(pattern(A² row s) ∪
+  pattern(A³ row s)) \\ (N(s) ∪ {s})``.  The expansion above with the frontier made explicit (``ops.frontier_count`` /
+  ``ops.frontier_sums_fill``: a per-query list of nodes and weights, and seeds) chains: the unexcluded 2-hop list of ``s``,
+  weighted by ``decay · w[c] · P₂(s, c)`` and seeded with ``P₂``, expands into the candidates within three hops and their
+  local path index ``P₂ + decay · P₃`` in ordered fp32 (``three_hop_candidates``, ``path_scored_candidates``).  ``hops=3`` in
+  ``recommend_links`` takes its candidates from there, with ``prefilter=(kind, m, decay)`` through a short list.  Opt-in.
 
 Everything runs on one GPU; dealing the sources over several is not built here.
 """
@@ -98,13 +106,8 @@ def two_hop_scored_candidates(adj: SparseTensor, sources: Tensor, kind: str,
     without an intersection per candidate."""
     _check_path_sum(kind)
     known = adj if known is None else known
-    if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
-        raise ValueError("sources must be a 1-d int64 tensor of node ids")
+    sources = _check_sources(adj, sources, known)
     n = adj.size(0)
-    for name, m in (("adj", adj), ("known", known)):
-        if tuple(m.sparse_sizes()) != (n, n):
-            raise ValueError(f"{name} is {tuple(m.sparse_sizes())}, expected the square size ({n}, {n}) of adj")
-    sources = sources.contiguous()
     w = None
     if kind != "cn":
         from .heuristics import node_table
@@ -124,17 +127,102 @@ def _check_m(m) -> int:
     return m
 
 
-def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int,
-                         known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
-    """The ``m`` best candidates of every source by a path-sum heuristic: (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2])
-    in the layout of ``two_hop_candidates``.  Per source the candidates of ``two_hop_scored_candidates`` are ranked in the total
-    order of ``segment_topk`` — higher ``val`` first, ties to the lower node id — the first ``m`` are kept (all of them where a
-    source has no more) and returned in ASCENDING node id, so that "ties go to the lower node id" still holds for whoever ranks
-    the retained list again.  ``1 <= m <= ops.segment_topk_max_k()``.  One host sync more than the candidates cost (the size of
-    the retained list)."""
+def _check_hops(hops) -> int:
+    if isinstance(hops, bool) or hops not in (2, 3):
+        raise ValueError(f"hops must be 2 or 3, got {hops!r}")
+    return int(hops)
+
+
+def _check_decay(decay) -> float:
+    import math
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not math.isfinite(decay) or decay < 0:
+        raise ValueError(f"decay must be a finite number >= 0 (the weight of a 3-walk beside a 2-path; it has no default), got {decay!r}")
+    return float(decay)
+
+
+def _check_sources(adj: SparseTensor, sources: Tensor, known: SparseTensor) -> Tensor:
+    if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
+        raise ValueError("sources must be a 1-d int64 tensor of node ids")
+    n = adj.size(0)
+    for name, m in (("adj", adj), ("known", known)):
+        if tuple(m.sparse_sizes()) != (n, n):
+            raise ValueError(f"{name} is {tuple(m.sparse_sizes())}, expected the square size ({n}, {n}) of adj")
+    return sources.contiguous()
+
+
+class _ThreeHop:
+    """The first half of a 3-hop expansion, for all sources: the unexcluded 2-hop list ``L2`` (empty ``M``, the source itself
+    stays in) with ``u = P₂``, the frontier weights ``f = (decay32 · w[c]) · u`` — two rounded fp32 products in eager torch,
+    ``w ≡ 1`` for "cn" — and the size of every source's candidate set (the count pass).  ``fill(a, b)`` runs the second
+    expansion for the sources ``a .. b``.  ``kind=None``: unit weights and no values (the candidates alone)."""
+
+    def __init__(self, adj: SparseTensor, sources: Tensor, kind: Optional[str], decay: float, known: SparseTensor):
+        n, dev = adj.size(0), sources.device
+        self.rows = sources
+        self.A = (adj._rowptr, adj._col)
+        self.M = (known._rowptr, known._col)
+        none = (torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))   # M = 0: every row empty
+        self.n = n
+        with ops.prevalidated(sources, sources, n, n):
+            self.ptr2 = ops.scan_i32(ops.two_hop_diff_count(*self.A, *none, sources, drop_self=False))
+            if kind is None:
+                self.L2 = ops.two_hop_diff_fill(*self.A, *none, sources, self.ptr2, drop_self=False)
+                self.u = self.f = None
+            else:
+                w = None
+                if kind != "cn":
+                    from .heuristics import node_table
+                    w = node_table(adj)
+                wcol = 1 if kind == "ra" else 0
+                self.L2, self.u = ops.two_hop_sums_fill(*self.A, *none, sources, self.ptr2, w, wcol, drop_self=False)
+                d32 = torch.tensor(decay, dtype=torch.float32, device=dev)
+                self.f = (d32 * self.u) if w is None else ((d32 * w[self.L2[:, 1], wcol]) * self.u)
+            self.count = ops.frontier_count(*self.A, *self.M, sources, self.ptr2, self.L2, self.ptr2, self.L2, drop_self=True)
+            self.ptr = ops.scan_i32(self.count)
+
+    def fill(self, a: int, b: int, total: Optional[int] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+        """(ptr [b - a + 1] from 0, edges, val) of the sources ``a .. b``: the lists are addressed by absolute offsets, so a chunk
+        is a slice of ``rows`` and of the two offset vectors."""
+        p2 = self.ptr2[a:b + 1]
+        off = self.ptr[a:b + 1] if a == 0 else self.ptr[a:b + 1] - self.ptr[a]
+        with ops.prevalidated(self.rows, self.rows, self.n, self.n):
+            edges, val = ops.frontier_sums_fill(*self.A, *self.M, self.rows[a:b], p2, self.L2, self.f, p2, self.L2, self.u,
+                                                off.contiguous(), drop_self=True, total=total, values=self.u is not None)
+        return off, edges, val
+
+
+def three_hop_candidates(adj: SparseTensor, sources: Tensor, known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+    """The candidate targets of ``sources`` within THREE hops, in the layout of ``two_hop_candidates``: for each source ``s``
+    the columns of ``pattern(A² row s) ∪ pattern(A³ row s)`` that are neither ``s`` nor in row ``s`` of ``known`` (``adj`` by
+    default), ascending.  For a symmetric ``adj`` these are exactly the targets with a non-empty ``cn1`` or ``cn2`` — a pair
+    at distance 3 has only the latter.  Two chained expansions from ``adj`` (``ops.two_hop_diff_*`` without an exclusion, then
+    ``ops.frontier_*`` seeded with its own frontier); ``adj2`` is never read, so the list serves the pattern route and the
+    walk route alike.  Under a power law the list is tens of times the 2-hop one."""
+    known = adj if known is None else known
+    sources = _check_sources(adj, sources, known)
+    ptr, edges, _ = _ThreeHop(adj, sources, None, 0.0, known).fill(0, sources.numel())
+    return ptr, edges
+
+
+def path_scored_candidates(adj: SparseTensor, sources: Tensor, kind: str, hops: int, decay: float,
+                           known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The candidates within ``hops`` hops with their local path index: (``ptr`` int64 [Q + 1], ``edges`` int64 [T, 2], ``val``
+    float32 [T]).  ``hops=2``: ``two_hop_scored_candidates(adj, sources, kind, known)``, unchanged (``decay`` is checked and not
+    used).  ``hops=3``: the candidates of ``three_hop_candidates`` with ``val = P₂ + decay · P₃`` — ``P₂`` the path sum of
+    ``two_hop_scored_candidates`` (0 where no 2-path exists), ``P₃(s, t)`` the sum of ``w[m] · w[c]`` over the 3-walks
+    ``s – m – c – t``.  In fp32, in a fixed order: ``P₂`` first, then for every ``c`` of the 2-hop list whose row holds ``t``, in
+    ascending ``c``, the term ``(decay32 · w[c]) · P₂(s, c)`` (two rounded products), one add each.  With ``kind="cn"`` that is
+    the local path index ``A² + decay · A³``.  ``decay``: finite and >= 0; which value ranks well is a modelling decision."""
     _check_path_sum(kind)
-    m = _check_m(m)
-    ptr, edges, val = two_hop_scored_candidates(adj, sources, kind, known)
+    hops, decay = _check_hops(hops), _check_decay(decay)
+    if hops == 2:
+        return two_hop_scored_candidates(adj, sources, kind, known)
+    known = adj if known is None else known
+    sources = _check_sources(adj, sources, known)
+    return _ThreeHop(adj, sources, kind, decay, known).fill(0, sources.numel())
+
+
+def _keep_m_best(ptr: Tensor, edges: Tensor, val: Tensor, m: int) -> Tuple[Tensor, Tensor]:
     Q = ptr.numel() - 1
     ptr_m = torch.zeros_like(ptr)
     torch.cumsum((ptr[1:] - ptr[:-1]).clamp(max=m), 0, out=ptr_m[1:])
@@ -147,14 +235,79 @@ def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int,
     return ptr_m, edges[keep]
 
 
-def _check_prefilter(prefilter, k: int) -> Tuple[str, int]:
-    if not isinstance(prefilter, (tuple, list)) or len(prefilter) != 2 or not isinstance(prefilter[0], str) \
+def _budget_chunks(count: Tensor, budget: int):
+    """Consecutive runs [a, b) of sources whose candidate total stays at or below ``budget``; a source above it goes alone."""
+    sizes = count.tolist()
+    a, run = 0, 0
+    for q, c in enumerate(sizes):
+        if q > a and run + c > budget:
+            yield a, q, run
+            a, run = q, 0
+        run += c
+    if len(sizes) > a:
+        yield a, len(sizes), run
+
+
+def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, known: Optional[SparseTensor] = None,
+                         hops: int = 2, decay: Optional[float] = None, budget: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The ``m`` best candidates of every source by a path-sum heuristic: (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2])
+    in the layout of ``two_hop_candidates``.  Per source the candidates of ``two_hop_scored_candidates`` are ranked in the total
+    order of ``segment_topk`` — higher ``val`` first, ties to the lower node id — the first ``m`` are kept (all of them where a
+    source has no more) and returned in ASCENDING node id, so that "ties go to the lower node id" still holds for whoever ranks
+    the retained list again.  ``1 <= m <= ops.segment_topk_max_k()``.  One host sync more than the candidates cost (the size of
+    the retained list).
+
+    ``hops=3`` (with ``decay``, see ``path_scored_candidates``): the candidates within three hops, ranked by ``P₂ + decay · P₃``.
+    Their list is tens of times the 2-hop one, so the sources are dealt into consecutive chunks whose candidate total, known
+    from the count pass, stays at or below ``budget`` (``ops.prefilter_budget`` by default; a single source above it goes alone);
+    a chunk is filled, ranked and reduced to its ``m`` best before the next.  The result does not depend on ``budget``."""
+    _check_path_sum(kind)
+    m = _check_m(m)
+    if _check_hops(hops) == 3:
+        decay = _check_decay(decay)
+        budget = int(ops.prefilter_budget if budget is None else budget)
+        if budget < 1:
+            raise ValueError(f"budget must be a positive number of candidates, got {budget}")
+        known = adj if known is None else known
+        sources = _check_sources(adj, sources, known)
+        plan = _ThreeHop(adj, sources, kind, decay, known)
+        parts = [_keep_m_best(*plan.fill(a, b, total), m) for a, b, total in _budget_chunks(plan.count, budget)]
+        ptr_m = torch.zeros(sources.numel() + 1, dtype=torch.int64, device=sources.device)
+        if not parts:
+            return ptr_m, torch.empty(0, 2, dtype=torch.int64, device=sources.device)
+        torch.cumsum(torch.cat([p[1:] - p[:-1] for p, _ in parts]), 0, out=ptr_m[1:])
+        return ptr_m, torch.cat([e for _, e in parts])
+    if decay is not None or budget is not None:
+        raise ValueError("decay and budget belong to hops=3")
+    return _keep_m_best(*two_hop_scored_candidates(adj, sources, kind, known), m)
+
+
+def _check_prefilter(prefilter, k: int, hops: int = 2):
+    """(kind, m) for ``hops=2``, (kind, m, decay) for ``hops=3``: the other arity is refused."""
+    form = "(kind, m)" if hops == 2 else "(kind, m, decay) under hops=3,"
+    if not isinstance(prefilter, (tuple, list)) or len(prefilter) != hops or not isinstance(prefilter[0], str) \
             or isinstance(prefilter[1], bool) or not isinstance(prefilter[1], int):
-        raise ValueError(f"prefilter must be None or (kind, m) with kind one of {PATH_SUMS} and m an int, got {prefilter!r}")
+        raise ValueError(f"prefilter must be None or {form} with kind one of {PATH_SUMS} and m an int, got {prefilter!r}")
     kind, m = _check_path_sum(prefilter[0]), _check_m(prefilter[1])
     if k > m:
         raise ValueError(f"prefilter keeps m = {m} candidates per source, fewer than k = {k}")
-    return kind, m
+    return (kind, m) if hops == 2 else (kind, m, _check_decay(prefilter[2]))
+
+
+def _candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, known: Optional[SparseTensor], hops: int,
+                prefilter) -> Tuple[Tensor, Tensor]:
+    """The candidate list of a request: the short list where ``prefilter`` (checked) is given, else every candidate within
+    ``hops`` hops.  A segment of the top-k takes fewer than 2^32 - 1 entries, and so does the flat list."""
+    if prefilter is not None:
+        return prefilter_candidates(adj, sources, prefilter[0], prefilter[1], known) if hops == 2 else \
+            prefilter_candidates(adj, sources, prefilter[0], prefilter[1], known, hops=3, decay=prefilter[2])
+    if hops == 2:
+        return two_hop_candidates(adj, adj2, sources, known)
+    ptr, edges = three_hop_candidates(adj, sources, known)
+    if edges.shape[0] >= (1 << 32) - 1:
+        raise ValueError(f"{edges.shape[0]} candidates within three hops: the flat list must have fewer than 2^32 - 1 entries "
+                         "(ask for fewer sources per call, or short-list with prefilter=(kind, m, decay))")
+    return ptr, edges
 
 
 def segment_topk(scores: Tensor, ptr: Tensor, k: int) -> Tuple[Tensor, Tensor]:
@@ -175,7 +328,7 @@ def _select(scores: Tensor, ptr: Tensor, edges: Tensor, k: int) -> Tuple[Tensor,
 @torch.no_grad()
 def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, k: int,
                     batch_size: int, args=None, known: Optional[SparseTensor] = None, run_ahead: int = 6,
-                    prefilter: Optional[Tuple[str, int]] = None) -> Tuple[Tensor, Tensor]:
+                    prefilter: Optional[tuple] = None, hops: int = 2) -> Tuple[Tensor, Tensor]:
     """The ``k`` best predicted links of every source: (``dst`` int64 [Q, k], ``score`` float32 [Q, k]), best first, ``dst``
     = -1 and ``score`` = -inf where a source has fewer than ``k`` candidates.
 
@@ -207,7 +360,14 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     with frozen column weights a retained pair's score is, within the frozen scoring tolerance, its score in the unfiltered
     run, and the result differs from the unfiltered one only where the heuristic dropped a pair the model would have ranked
     among the ``k`` best.  Where no source has more than ``m`` candidates the retained list is the full list and the result
-    is the unfiltered one.  ``prefilter=None``: every candidate is scored, as described above."""
+    is the unfiltered one.  ``prefilter=None``: every candidate is scored, as described above.
+
+    ``hops=3``: the candidates are those within three hops (``three_hop_candidates``: every target with a non-empty cn1 or
+    cn2, expanded from ``adj`` alone on either route) and the contract is the same sentence — the scores are exactly those of
+    the one scoring call on the flat list; ValueError if that list has 2^32 - 1 entries or more.  Under a power law it is tens
+    of times the 2-hop list, so the form to serve is ``hops=3`` with ``prefilter=(kind, m, decay)``: the short list is then
+    taken over three hops by ``P₂ + decay · P₃`` (``prefilter_candidates(..., hops=3, decay=decay)``).  A 2-tuple with
+    ``hops=3`` or a 3-tuple with ``hops=2`` is refused.  cn6 is served over these <= 3 hops; its own evidence reaches four."""
     from .pipeline import score_edges, score_edges_walk
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
@@ -215,15 +375,10 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     from .model import CNLinkPredictor3hopCNs
     if adj2 is None and isinstance(predictor, CNLinkPredictor3hopCNs):
         raise ValueError("cn6 needs adj2 = adj @ adj: the walk route has no 3-hop form")
+    hops = _check_hops(hops)
     if prefilter is not None:
-        kind, m = _check_prefilter(prefilter, k)
-        ptr, edges = prefilter_candidates(adj, sources, kind, m, known)
-        if adj2 is None:
-            scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
-        else:
-            scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
-        return _select(scores, ptr, edges, k)
-    ptr, edges = two_hop_candidates(adj, adj2, sources, known)
+        prefilter = _check_prefilter(prefilter, k, hops)
+    ptr, edges = _candidates(adj, adj2, sources, known, hops, prefilter)
     if adj2 is None:
         scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
     else:
@@ -233,14 +388,15 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
 
 @torch.no_grad()
 def recommend_links_heuristic(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, k: int, batch_size: int,
-                              kind: str, known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+                              kind: str, known: Optional[SparseTensor] = None, hops: int = 2) -> Tuple[Tensor, Tensor]:
     """``recommend_links`` with one training-free heuristic (``heuristics.score_edges_heuristic``) in place of a model.  A
     heuristic score depends on its candidate alone: the result does not change with ``batch_size`` or with the other sources.
     ``adj2=None`` serves the 1-hop kinds (cn, aa, ra, jaccard, pa), which never read A²: same candidates, same scores as with
-    the product given.  The 2-hop kinds intersect with the rows of ``adj2`` and refuse None."""
+    the product given.  The 2-hop kinds intersect with the rows of ``adj2`` and refuse None.  ``hops=3``: the candidates within
+    three hops (``three_hop_candidates``); a 1-hop kind scores those beyond two hops 0."""
     from .heuristics import _check_kinds, score_edges_heuristic
     _check_kinds((kind,), adj2)
     k = _check_k(k)
-    ptr, edges = two_hop_candidates(adj, adj2, sources, known)
+    ptr, edges = _candidates(adj, adj2, sources, known, _check_hops(hops), None)
     scores = score_edges_heuristic(adj, adj2, edges, batch_size, kind)
     return _select(scores, ptr, edges, k)
