@@ -15,6 +15,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen # ... with column weights frozen on the validation edges
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32 --recommend-eval 200   # ... and where the test links rank
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
@@ -37,6 +38,7 @@ from ocn_amd.frozen import freeze_columns                                       
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
+from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
 from ocn_amd.recommend import (prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
@@ -165,6 +167,9 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
     --recommend-hops 3: the candidates within three hops (every target with a non-empty cn1 or cn2), expanded from the adjacency;
     the prefilter is then KIND:M:DECAY and ranks them by the local path index P2 + DECAY * P3.
+    --recommend-eval Q: the held-out test links of the first Q distinct test sources are ranked among the candidates of the selected
+    route (ocn_amd.ranking) and recall / NDCG / hit rate @K, MRR, coverage and retention are printed; with a prefilter the
+    unfiltered run stands beside it.
     --recommend-explain M: the K winners of the printed sources are explained as ONE batch (ocn_amd.explain): per target the M
     common neighbours that carry most of its score, with their two shares (via xcn1, via xcn2).
     --recommend-accept M: the M best of them are then inserted and the sources asked again.
@@ -233,6 +238,34 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
                 name = f"{kind}:{m}"
             print(f"prefilter {name} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
                   f"(the model ranked {n_short} of {n_all} candidates)", flush=True)
+    if args.recommend_eval:
+        # --recommend-eval Q: where the held-out test links land in the ranking served above (ocn_amd.ranking).  The first Q distinct
+        # test sources; truth = the test edges, both ways, on the graph the candidates come from.  Printed only: a synthetic graph
+        # under a briefly trained model supports no claim about which route ranks best.
+        test = split_edge['test']['edge'].to(dev)
+        n = adj.size(0)
+        first = torch.tensor(list(dict.fromkeys(test[:, 0].tolist()))[:args.recommend_eval], dtype=torch.int64, device=dev)
+        truth = SparseTensor.from_edge_index(test.t().contiguous(), sparse_sizes=(n, n)).to_symmetric()
+        ks = tuple(sorted({k, 10, 50, 100}))
+
+        def show(tag, res):
+            met = ranking_metrics(res, ks)
+            print(f"recommend-eval {tag}: {met['n_eval']} sources, {met['n_pairs']} pairs, coverage {met['coverage']:.4f}"
+                  + (f" retention {met['retention']:.4f}" if "retention" in met else "") + f" mrr {met['mrr']:.4f}  "
+                  + "  ".join(f"recall/ndcg/hit@{x} {met[f'recall@{x}']:.4f}/{met[f'ndcg@{x}']:.4f}/{met[f'hit_rate@{x}']:.4f}" for x in ks),
+                  flush=True)
+        if args.heuristic:
+            show(f"{args.heuristic} over {args.recommend_hops} hops",
+                 rank_links_heuristic(adj, adj2, first, truth, args.testbs, args.heuristic, hops=args.recommend_hops))
+        else:
+            h = state.h if state is not None else model(data.x, adj)
+            route = f"{args.predictor} over {args.recommend_hops} hops" + (" (walk route)" if adj2 is None else "")
+            if args.recommend_prefilter:
+                show(route + " prefilter " + ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in args.recommend_prefilter),
+                     rank_links(predictor, h, adj, adj2, first, truth, args.testbs, args, prefilter=args.recommend_prefilter,
+                                hops=args.recommend_hops))
+            show(route + (" unfiltered" if args.recommend_prefilter else ""),
+                 rank_links(predictor, h, adj, adj2, first, truth, args.testbs, args, hops=args.recommend_hops))
     if args.recommend_explain:
         # --recommend-explain M: why these links — gradient x input on the pooled vectors, per common neighbour.  The winners form one
         # batch of their own: an unfrozen cn5 / cn7 weighs them by THAT batch's column statistics, so only a frozen predictor (or
@@ -327,6 +360,10 @@ def main(argv=None):
     ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M[:DECAY]",
                     help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
                          "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
+    ap.add_argument("--recommend-eval", type=int, default=0, metavar="Q",
+                    help="with --recommend: rank the held-out test links of the first Q distinct test sources among the candidates of "
+                         "the selected route (ocn_amd.ranking) and print recall / NDCG / hit rate @K, MRR, coverage and, with "
+                         "--recommend-prefilter, retention beside the unfiltered run")
     ap.add_argument("--recommend-explain", type=int, default=0, metavar="M",
                     help="with --recommend and a cn5 / cn7 / cn8 model: explain the K winners of the printed sources as one batch "
                          "(ocn_amd.explain) and print each target's top-M common neighbours with their two contributions")
@@ -352,6 +389,8 @@ def main(argv=None):
         ap.error("--recommend-explain M: needs --recommend K, a cn5, cn7 or cn8 model and 1 <= M <= 128")
     if args.recommend_hops != 2 and not args.recommend:
         ap.error("--recommend-hops: needs --recommend K")
+    if args.recommend_eval < 0 or (args.recommend_eval and not args.recommend):
+        ap.error("--recommend-eval Q: needs --recommend K and Q >= 1")
     if args.recommend_prefilter:
         parts = args.recommend_prefilter.split(":")
         kind, m, decay = parts[0], "".join(parts[1:2]), parts[2:]

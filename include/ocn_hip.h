@@ -51,7 +51,8 @@ extern "C" {
  *    the retrieval half of two-stage recommendation); ocn_cn_attribution (explaining a predicted link: the share of every
  *    common neighbour in the pooled vectors' part of a score); ocn_frontier_window_cols, ocn_frontier_count,
  *    ocn_frontier_sums_fill (frontier expansion with ordered path sums: chained, the candidates within three hops and their
- *    local path index). */
+ *    local path index); ocn_segment_rank (the place of held-out links among a source's candidates, in the order of
+ *    ocn_segment_topk: ranking metrics). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -528,6 +529,21 @@ int ocn_frontier_sums_fill(const int64_t* rowptrA, const int32_t* colA, const in
 int32_t ocn_segment_topk_max_k(void);
 int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t k, float* top_val, int64_t* top_pos,
                      void* stream);
+/* The place of given nodes in that order: a segmented rank.  Segment q is scores[ptr[q] .. ptr[q + 1]) and its ids are
+ * edges[.][1] over the same range — the [T][2] pair layout every candidate builder writes — ASCENDING within a segment
+ * (trusted, not checked, as ptr is).  tnode[tptr[q] .. tptr[q + 1]) are the nodes to rank in segment q: in any order, with
+ * repeats, possibly none; tptr [Q + 1] ascends from 0 to P.  For target j of segment q: rank[j] = 0 and pos[j] = -1 where
+ * tnode[j] is no id of the segment (any int64 value: negative and out-of-range ids simply are not found); else pos[j] is the
+ * entry's position in the FLAT vector and rank[j] = 1 + the number of entries of the segment that precede it in the total
+ * order of ocn_segment_topk — the 1-based place it takes in an unbounded top-k, so rank <= k exactly when ocn_segment_topk(k)
+ * lists it, at top_pos[q][rank - 1].
+ * A wave owns a target: it finds its segment by a search of its own index in tptr (no work list), the node by a binary
+ * search of the ids, and streams the segment's scores counting the keys that beat the target's.  No sort, no atomics, no
+ * workspace, no barriers; the result is fixed by the input.  A segment must have fewer than 2^32 - 1 entries.
+ * NULL pointers, Q < 0, P < 0: OCN_EINVAL before any HIP call.  Q == 0 or P == 0 returns 0 and launches nothing. */
+int ocn_segment_rank(const float* scores, const int64_t* ptr, const int64_t* edges /* [ptr[Q]][2] */, int64_t Q,
+                     const int64_t* tptr /* [Q + 1] */, const int64_t* tnode /* [P] */, int64_t P,
+                     int64_t* rank /* [P] */, int64_t* pos /* [P] */, void* stream);
 
 /* Structured negative sampling (ocn_amd/sampling.py): pairs that are guaranteed not to be links of a square `known` matrix
  * (sorted, duplicate-free int32 columns, n_cols rows and columns, 1 <= n_cols < 2^31), drawn exactly uniformly, with

@@ -2,7 +2,8 @@
 // that is not yet linked: pattern(A² row s) \ (N(s) ∪ {s})), and the k best entries of every segment of a flat score
 // vector.  Both are ragged and row-parallel: a wave owns a query / a segment from its first load to its last store, no
 // atomics, no workspace, and the output of every row is fixed by its input alone.
-// See include/ocn_hip.h (ocn_row_diff_count / ocn_row_diff_fill, ocn_segment_topk).
+// See include/ocn_hip.h (ocn_row_diff_count / ocn_row_diff_fill, ocn_segment_topk).  ocn_segment_rank answers the inverse
+// question in the same order: the place a given node takes in its segment, however far down.
 // Where A² is not stored (more columns than the A*A pattern takes, or simply too large) the same candidate set is expanded
 // from A itself: a workgroup owns a query and keeps the union of its neighbours' rows as a bitmap in LDS, one window of the
 // column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
@@ -393,6 +394,57 @@ __global__ __launch_bounds__(OCN_BLOCK) void segment_topk_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// segmented rank
+// ---------------------------------------------------------------------------------------------
+// Where a given node stands in the order above: a wave owns target j.  Its segment is the last q with tptr[q] <= j (a search
+// of the wave's own index: empty target lists are stepped over, and no index leaves [0, Q) whatever tptr holds); the node is
+// looked up in the segment's ascending ids (the second of every pair: a lower bound, the same loads in every lane); then the
+// segment's scores are streamed as the top-k streams them — TOPK_AHEAD chunks loaded ahead of their tests, the tail clamped —
+// and every lane counts the keys that beat the target's.  Keys are distinct, so 1 + that count is the place the entry takes
+// in an unbounded top-k.  Every branch below is taken by the whole wave; no LDS, no barrier, no atomics.
+__global__ __launch_bounds__(OCN_BLOCK) void segment_rank_kernel(
+    const float* __restrict__ scores, const i64* __restrict__ ptr, const longlong2* __restrict__ edges, i64 Q,
+    const i64* __restrict__ tptr, const i64* __restrict__ tnode, i64 P, i64* __restrict__ rank, i64* __restrict__ pos) {
+  const int lane = threadIdx.x & 63;
+  for (i64 j = (i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6); j < P; j += (i64)gridDim.x * OCN_WPB) {
+    i64 q = 0;
+    for (i64 len = Q; len > 1;) {                            // the last q in [0, Q) with tptr[q] <= j (0 if there is none)
+      const i64 half = len >> 1;
+      q += (tptr[q + half] <= j) ? half : 0;
+      len -= half;
+    }
+    const i64 b = ptr[q], n = ptr[q + 1] - b;
+    const i64 node = tnode[j];
+    i64 lo = 0, hi = n;                                      // the first entry whose id is not below node
+    while (lo < hi) {
+      const i64 mid = lo + ((hi - lo) >> 1);
+      if (edges[b + mid].y < node) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= n || edges[b + lo].y != node) {                // any int64 that is no id of the segment, an empty segment
+      if (lane == 0) { rank[j] = 0; pos[j] = -1; }
+      continue;
+    }
+    const u64 tk = topk_key(scores[b + lo], (unsigned)lo);
+    unsigned ahead = 0u;                                     // (a lane tests fewer than 2^26 entries)
+    for (i64 c0 = 0; c0 < n; c0 += (i64)OCN_WAVE * TOPK_AHEAD) {
+      float x[TOPK_AHEAD];
+#pragma unroll
+      for (int t = 0; t < TOPK_AHEAD; ++t) {
+        const i64 p = c0 + t * OCN_WAVE + lane;
+        x[t] = scores[b + (p < n ? p : n - 1)];
+      }
+#pragma unroll
+      for (int t = 0; t < TOPK_AHEAD; ++t) {
+        const i64 p = c0 + t * OCN_WAVE + lane;
+        ahead += (p < n && topk_key(x[t], (unsigned)p) > tk) ? 1u : 0u;
+      }
+    }
+    const i64 total = wave_sum((i64)ahead);
+    if (lane == 0) { rank[j] = total + 1; pos[j] = b + lo; }
+  }
+}
+
 static inline unsigned wave_grid(i64 items) { return (unsigned)grid_for((items + OCN_WPB - 1) / OCN_WPB, 256 * 8); }
 
 extern "C" {
@@ -521,6 +573,15 @@ int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t
   else
     hipLaunchKernelGGL(segment_topk_kernel<2>, grid, dim3(OCN_BLOCK), 0, (hipStream_t)stream, scores, (const i64*)ptr, (i64)Q,
                        (int)k, top_val, (i64*)top_pos);
+  return launch_status();
+}
+
+int ocn_segment_rank(const float* scores, const int64_t* ptr, const int64_t* edges, int64_t Q, const int64_t* tptr,
+                     const int64_t* tnode, int64_t P, int64_t* rank, int64_t* pos, void* stream) {
+  if (Q < 0 || P < 0 || !scores || !ptr || !edges || !tptr || !tnode || !rank || !pos) return OCN_EINVAL;
+  if (Q == 0 || P == 0) return 0;
+  hipLaunchKernelGGL(segment_rank_kernel, dim3(wave_grid(P)), dim3(OCN_BLOCK), 0, (hipStream_t)stream, scores, (const i64*)ptr,
+                     (const longlong2*)edges, (i64)Q, (const i64*)tptr, (const i64*)tnode, (i64)P, (i64*)rank, (i64*)pos);
   return launch_status();
 }
 

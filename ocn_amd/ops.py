@@ -1048,6 +1048,40 @@ def segment_topk(scores: Tensor, seg_ptr: Tensor, k: int) -> Tuple[Tensor, Tenso
 
 
 @_on_device
+def segment_rank(scores: Tensor, seg_ptr: Tensor, edges: Tensor, tptr: Tensor, tnode: Tensor) -> Tuple[Tensor, Tensor]:
+    """Where given nodes stand in the order of ``segment_topk`` (ocn_hip.h: ocn_segment_rank): (rank int64 [P], pos int64 [P]).
+    Segment ``q`` is ``scores[seg_ptr[q] : seg_ptr[q + 1]]`` with the ids ``edges[seg_ptr[q] : seg_ptr[q + 1], 1]``, ascending
+    (the [T, 2] layout of the candidate builders); ``tnode[tptr[q] : tptr[q + 1]]`` are the nodes to rank in it — any order,
+    repeats allowed, possibly none.  ``rank`` = 1 + the number of entries of the segment that come before the node's in that
+    order, ``pos`` = its position in the flat vector; 0 and -1 where the node is no id of the segment (any int64 value).
+    ``seg_ptr`` and ``tptr`` are trusted to be ascending offsets with ``seg_ptr[-1] <= scores.numel()`` and ``tptr[-1] ==
+    tnode.numel()``, and the ids to ascend (checking would cost a host sync)."""
+    _req(scores, torch.float32, "scores", 1); _req(seg_ptr, torch.int64, "ptr", 1)
+    _req(tptr, torch.int64, "tptr", 1); _req(tnode, torch.int64, "tnode", 1)
+    if _req(edges, torch.int64, "edges", 2).shape[1] != 2:
+        raise ValueError(f"edges: expected the [T, 2] pair layout, got {tuple(edges.shape)}")
+    if seg_ptr.numel() < 1:
+        raise ValueError("ptr: [Q + 1] offsets")
+    if tptr.numel() != seg_ptr.numel():
+        raise ValueError(f"tptr: one target list per segment and the total ({seg_ptr.numel()} offsets), got {tptr.numel()}")
+    if edges.shape[0] != scores.numel():
+        raise ValueError(f"edges: one pair per score ({scores.numel()}), got {edges.shape[0]}")
+    if scores.numel() >= (1 << 32) - 1:
+        raise ValueError("scores: segments of 2^32 - 1 entries or more are not supported")
+    Q, P = seg_ptr.numel() - 1, tnode.numel()
+    if not (Q and P):                                                    # (targets without a segment are not found either)
+        return (torch.zeros(P, dtype=torch.int64, device=scores.device), torch.full((P,), -1, dtype=torch.int64, device=scores.device))
+    rank = torch.empty(P, dtype=torch.int64, device=scores.device)
+    pos = torch.empty(P, dtype=torch.int64, device=scores.device)
+    src = scores if scores.numel() else scores.new_empty(1)              # (no score to read: every segment is empty, the entry still wants
+    ids = edges if scores.numel() else edges.new_zeros(1, 2)             #  its pointers)
+    check(_lib.lib().ocn_segment_rank(ptr(src), ptr(seg_ptr), ptr(ids), Q, ptr(tptr), ptr(tnode), P, ptr(rank), ptr(pos),
+                                      stream_ptr()), "ocn_segment_rank")
+    _mark("segment_rank")
+    return rank, pos
+
+
+@_on_device
 def philox4x32(ctr: Tensor, key0: int, key1: int) -> Tensor:
     """Philox4x32-10 of every counter row (ocn_hip.h: ocn_philox4x32): ``ctr`` int32 [n, 4] holds the bit patterns of the four
     uint32 counter words, ``key0`` / ``key1`` are the key words (0 .. 2^32 - 1); returns the four output words, int32 [n, 4]

@@ -248,6 +248,51 @@ def _budget_chunks(count: Tensor, budget: int):
         yield a, len(sizes), run
 
 
+def _path_index_pass(adj: SparseTensor, sources: Tensor, kind: str, m: Optional[int], known: Optional[SparseTensor], hops: int,
+                     decay: Optional[float], budget: Optional[int], targets: Optional[Tuple[Tensor, Tensor]] = None):
+    """One pass over the path-scored candidates of every source, shared by ``prefilter_candidates`` and ``ocn_amd.ranking``:
+    (``short``, ``rank``, ``count``).  ``short``: the (``ptr_m``, ``edges_m``) of ``prefilter_candidates`` where ``m`` is given,
+    else None.  ``rank``: with ``targets = (tptr int64 [Q + 1], tnode int64 [P])``, the place of every target among ALL the
+    candidates of its source by the path index (``ops.segment_rank``: 0 = no candidate), else None.  ``count`` int64 [Q]: the
+    candidates of every source.  Under ``hops=3`` both are taken chunk by chunk — a chunk's targets are ranked against the
+    chunk's ``val`` before it is reduced to its ``m`` best — so the full three-hop list never exists at once and neither result
+    depends on ``budget``.  Ranking costs one host copy of ``tptr`` (the chunks slice ``tnode`` by it)."""
+    _check_path_sum(kind)
+    if _check_hops(hops) == 3:
+        decay = _check_decay(decay)
+        budget = int(ops.prefilter_budget if budget is None else budget)
+        if budget < 1:
+            raise ValueError(f"budget must be a positive number of candidates, got {budget}")
+        known = adj if known is None else known
+        sources = _check_sources(adj, sources, known)
+        plan = _ThreeHop(adj, sources, kind, decay, known)
+        tp = targets[0].tolist() if targets is not None else None
+        parts, ranks = [], []
+        for a, b, total in _budget_chunks(plan.count, budget):
+            ptr, edges, val = plan.fill(a, b, total)
+            if targets is not None:
+                ranks.append(ops.segment_rank(val, ptr, edges, targets[0][a:b + 1] - tp[a], targets[1][tp[a]:tp[b]])[0])
+            if m is not None:
+                parts.append(_keep_m_best(ptr, edges, val, m))
+        rank = None
+        if targets is not None:
+            rank = torch.cat(ranks) if ranks else torch.zeros_like(targets[1])
+        short = None
+        if m is not None:
+            ptr_m = torch.zeros(sources.numel() + 1, dtype=torch.int64, device=sources.device)
+            if not parts:
+                short = ptr_m, torch.empty(0, 2, dtype=torch.int64, device=sources.device)
+            else:
+                torch.cumsum(torch.cat([p[1:] - p[:-1] for p, _ in parts]), 0, out=ptr_m[1:])
+                short = ptr_m, torch.cat([e for _, e in parts])
+        return short, rank, plan.count.long()
+    if decay is not None or budget is not None:
+        raise ValueError("decay and budget belong to hops=3")
+    ptr, edges, val = two_hop_scored_candidates(adj, sources, kind, known)
+    rank = ops.segment_rank(val, ptr, edges, *targets)[0] if targets is not None else None
+    return (_keep_m_best(ptr, edges, val, m) if m is not None else None), rank, ptr[1:] - ptr[:-1]
+
+
 def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, known: Optional[SparseTensor] = None,
                          hops: int = 2, decay: Optional[float] = None, budget: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """The ``m`` best candidates of every source by a path-sum heuristic: (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2])
@@ -262,24 +307,7 @@ def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, 
     from the count pass, stays at or below ``budget`` (``ops.prefilter_budget`` by default; a single source above it goes alone);
     a chunk is filled, ranked and reduced to its ``m`` best before the next.  The result does not depend on ``budget``."""
     _check_path_sum(kind)
-    m = _check_m(m)
-    if _check_hops(hops) == 3:
-        decay = _check_decay(decay)
-        budget = int(ops.prefilter_budget if budget is None else budget)
-        if budget < 1:
-            raise ValueError(f"budget must be a positive number of candidates, got {budget}")
-        known = adj if known is None else known
-        sources = _check_sources(adj, sources, known)
-        plan = _ThreeHop(adj, sources, kind, decay, known)
-        parts = [_keep_m_best(*plan.fill(a, b, total), m) for a, b, total in _budget_chunks(plan.count, budget)]
-        ptr_m = torch.zeros(sources.numel() + 1, dtype=torch.int64, device=sources.device)
-        if not parts:
-            return ptr_m, torch.empty(0, 2, dtype=torch.int64, device=sources.device)
-        torch.cumsum(torch.cat([p[1:] - p[:-1] for p, _ in parts]), 0, out=ptr_m[1:])
-        return ptr_m, torch.cat([e for _, e in parts])
-    if decay is not None or budget is not None:
-        raise ValueError("decay and budget belong to hops=3")
-    return _keep_m_best(*two_hop_scored_candidates(adj, sources, kind, known), m)
+    return _path_index_pass(adj, sources, kind, _check_m(m), known, hops, decay, budget)[0]
 
 
 def _check_prefilter(prefilter, k: int, hops: int = 2):
@@ -295,19 +323,21 @@ def _check_prefilter(prefilter, k: int, hops: int = 2):
 
 
 def _candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, known: Optional[SparseTensor], hops: int,
-                prefilter) -> Tuple[Tensor, Tensor]:
+                prefilter, targets: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
     """The candidate list of a request: the short list where ``prefilter`` (checked) is given, else every candidate within
-    ``hops`` hops.  A segment of the top-k takes fewer than 2^32 - 1 entries, and so does the flat list."""
+    ``hops`` hops.  A segment of the top-k takes fewer than 2^32 - 1 entries, and so does the flat list.  Third: with a short
+    list and ``targets``, the retrieval rank of every target (``_path_index_pass``), else None."""
     if prefilter is not None:
-        return prefilter_candidates(adj, sources, prefilter[0], prefilter[1], known) if hops == 2 else \
-            prefilter_candidates(adj, sources, prefilter[0], prefilter[1], known, hops=3, decay=prefilter[2])
+        short, rank, _ = _path_index_pass(adj, sources, prefilter[0], prefilter[1], known, hops,
+                                          None if hops == 2 else prefilter[2], None, targets)
+        return short[0], short[1], rank
     if hops == 2:
-        return two_hop_candidates(adj, adj2, sources, known)
+        return (*two_hop_candidates(adj, adj2, sources, known), None)
     ptr, edges = three_hop_candidates(adj, sources, known)
     if edges.shape[0] >= (1 << 32) - 1:
         raise ValueError(f"{edges.shape[0]} candidates within three hops: the flat list must have fewer than 2^32 - 1 entries "
                          "(ask for fewer sources per call, or short-list with prefilter=(kind, m, decay))")
-    return ptr, edges
+    return ptr, edges, None
 
 
 def segment_topk(scores: Tensor, ptr: Tensor, k: int) -> Tuple[Tensor, Tensor]:
@@ -323,6 +353,33 @@ def _select(scores: Tensor, ptr: Tensor, edges: Tensor, k: int) -> Tuple[Tensor,
         return torch.full_like(pos, -1), val
     dst = edges[:, 1][pos.clamp(min=0)]
     return torch.where(pos >= 0, dst, torch.full_like(dst, -1)), val
+
+
+def _check_request(predictor, adj2: Optional[SparseTensor], k: int, prefilter, hops):
+    """The refusals of a model request, before anything touches the device: the checked (``hops``, ``prefilter``).  ``k``: what a
+    short list must at least keep (checked by the caller)."""
+    from .model import CNLinkPredictor3hopCNs
+    if adj2 is None and isinstance(predictor, CNLinkPredictor3hopCNs):
+        raise ValueError("cn6 needs adj2 = adj @ adj: the walk route has no 3-hop form")
+    hops = _check_hops(hops)
+    if prefilter is not None:
+        prefilter = _check_prefilter(prefilter, k, hops)
+    return hops, prefilter
+
+
+def _score_request(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, batch_size: int,
+                   args, known: Optional[SparseTensor], run_ahead: int, prefilter, hops: int,
+                   targets: Optional[Tuple[Tensor, Tensor]] = None):
+    """Candidates, then ONE scoring call — what ``recommend_links`` selects from and ``ranking.rank_links`` ranks in:
+    (``ptr``, ``edges``, ``scores``, the retrieval rank of ``targets`` under a short list or None).  ``hops`` and ``prefilter``
+    come from ``_check_request``."""
+    from .pipeline import score_edges, score_edges_walk
+    ptr, edges, rank = _candidates(adj, adj2, sources, known, hops, prefilter, targets)
+    if adj2 is None:
+        scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
+    else:
+        scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
+    return ptr, edges, scores, rank
 
 
 @torch.no_grad()
@@ -368,21 +425,11 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     of times the 2-hop list, so the form to serve is ``hops=3`` with ``prefilter=(kind, m, decay)``: the short list is then
     taken over three hops by ``P₂ + decay · P₃`` (``prefilter_candidates(..., hops=3, decay=decay)``).  A 2-tuple with
     ``hops=3`` or a 3-tuple with ``hops=2`` is refused.  cn6 is served over these <= 3 hops; its own evidence reaches four."""
-    from .pipeline import score_edges, score_edges_walk
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
-    from .model import CNLinkPredictor3hopCNs
-    if adj2 is None and isinstance(predictor, CNLinkPredictor3hopCNs):
-        raise ValueError("cn6 needs adj2 = adj @ adj: the walk route has no 3-hop form")
-    hops = _check_hops(hops)
-    if prefilter is not None:
-        prefilter = _check_prefilter(prefilter, k, hops)
-    ptr, edges = _candidates(adj, adj2, sources, known, hops, prefilter)
-    if adj2 is None:
-        scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
-    else:
-        scores = score_edges(predictor, h, adj, adj2, edges, batch_size, args, run_ahead)
+    hops, prefilter = _check_request(predictor, adj2, k, prefilter, hops)
+    ptr, edges, scores, _ = _score_request(predictor, h, adj, adj2, sources, batch_size, args, known, run_ahead, prefilter, hops)
     return _select(scores, ptr, edges, k)
 
 
@@ -397,6 +444,6 @@ def recommend_links_heuristic(adj: SparseTensor, adj2: Optional[SparseTensor], s
     from .heuristics import _check_kinds, score_edges_heuristic
     _check_kinds((kind,), adj2)
     k = _check_k(k)
-    ptr, edges = _candidates(adj, adj2, sources, known, _check_hops(hops), None)
+    ptr, edges, _ = _candidates(adj, adj2, sources, known, _check_hops(hops), None)
     scores = score_edges_heuristic(adj, adj2, edges, batch_size, kind)
     return _select(scores, ptr, edges, k)
