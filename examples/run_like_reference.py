@@ -20,6 +20,8 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
+    python examples/run_like_reference.py --dataset cora --hard-negatives 0.5              # half the training negatives from the source's 2-hop candidates
+    python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --hard-negatives 0.5 --hard-eval-negatives   # ... and MRR negatives
 """
 import argparse
 import math
@@ -42,7 +44,8 @@ from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics   
 from ocn_amd.recommend import (prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
-from ocn_amd.sampling import negative_edges, negative_targets                       # noqa: E402
+from ocn_amd.sampling import (negative_edges, negative_targets, two_hop_negative_edges,  # noqa: E402
+                              two_hop_negative_targets)
 from ocn_amd.sparse import SparseTensor                                             # noqa: E402
 from ocn_amd.synth import loaddataset_like                                          # noqa: E402
 from ocn_amd.utils import PermIterator, adjoverlap, sparse_tensor_multiply          # noqa: E402
@@ -65,6 +68,15 @@ def train(model, predictor, data, split_edge, optimizer, batch_size, maskinput, 
         negedge = negative_edges(data.adj_t, pos_train_edge.shape[1], seed=epoch)
     else:
         negedge = torch.randint(0, data.num_nodes, pos_train_edge.shape, device=pos_train_edge.device)
+    share = round(100 * args.hard_negatives)
+    if share:
+        # positive t with t % 100 < share gets its target corrupted within the source's 2-hop candidates (the pairs that
+        # recommend_links / rank_links order) in place of the draw above; a source without a candidate keeps that draw.
+        # PermIterator shuffles, so every batch gets the mix.  One draw per epoch.
+        t = torch.arange(pos_train_edge.shape[1], device=pos_train_edge.device)
+        t = t[t % 100 < share]
+        hard = two_hop_negative_edges(data.adj_t, pos_train_edge[:, t], seed=epoch, fallback=None)
+        negedge[:, t] = torch.where(hard[1] >= 0, hard, negedge[:, t])
     for perm in PermIterator(adjmask.device, adjmask.shape[0], batch_size):
         optimizer.zero_grad()
         if maskinput:
@@ -128,7 +140,9 @@ def test_mrr(model, predictor, data, split_edge, evaluator, batch_size, use_vale
     """The citation2 evaluation (NeighborOverlapCitation2.py:227-254): per positive (source, target) the negatives that share
     its source, scored on the walk route by ``pipeline.score_mrr_split``; the mean reciprocal rank of valid and test.  The
     negatives are the split's own (uniform random targets), or with --structured-negatives as many per source from
-    ``negative_targets(data.full_adj_t, ..)``: never the source itself and never a link the model has seen."""
+    ``negative_targets(data.full_adj_t, ..)``: never the source itself and never a link the model has seen.  With
+    --hard-eval-negatives they come from ``two_hop_negative_targets(data.full_adj_t, ..)`` instead: non-links within two hops
+    of the source, the pairs a recommendation has to order (uniform non-links where a source has no such node)."""
     model.eval(); predictor.eval()
     dev = data.x.device
     out = []
@@ -136,7 +150,9 @@ def test_mrr(model, predictor, data, split_edge, evaluator, batch_size, use_vale
         source = split_edge[split]['edge'][:, 0].to(dev).contiguous()
         target = split_edge[split]['edge'][:, 1].to(dev).contiguous()
         neg = split_edge[split]['edge_neg'][..., 1].to(dev).contiguous()
-        if args.structured_negatives:
+        if args.hard_eval_negatives:
+            neg = two_hop_negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
+        elif args.structured_negatives:
             neg = negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
         out.append(score_mrr_split(predictor, model(data.x, adj), adj, source, target, neg, batch_size, args, evaluator))
     return {'MRR': tuple(out)}, None
@@ -349,6 +365,13 @@ def main(argv=None):
     ap.add_argument("--structured-negatives", action="store_true",
                     help="draw the training negatives (and citation2's evaluation negatives) from the non-edges on the device "
                          "(ocn_amd.sampling) instead of torch.randint pairs, which can be links")
+    ap.add_argument("--hard-negatives", type=float, default=0.0, metavar="SHARE",
+                    help="share in [0, 1] of the training positives whose negative is the 2-hop corruption of their target "
+                         "(ocn_amd.sampling.two_hop_negative_edges): positive t when t %% 100 < round(100 * SHARE); the others keep "
+                         "the draw of --structured-negatives / torch.randint.  0: that draw alone")
+    ap.add_argument("--hard-eval-negatives", action="store_true",
+                    help="citation2's evaluation negatives from the 2-hop candidates of each source "
+                         "(ocn_amd.sampling.two_hop_negative_targets) where --structured-negatives draws uniform non-links")
     ap.add_argument("--recommend-walk", action="store_true",
                     help="--recommend without A² (adj2=None): for graphs whose A² cannot be formed; 1-hop heuristics or the model")
     ap.add_argument("--recommend-frozen", action="store_true",
@@ -376,6 +399,8 @@ def main(argv=None):
                     help="with --recommend-accept and a model: assert that the refreshed node embeddings (ocn_amd.update.EncoderState) "
                          "equal a full encoder pass bit for bit after the insert, and after the undo")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.hard_negatives <= 1.0:
+        ap.error("--hard-negatives SHARE: a share in [0, 1]")
     if args.recommend_check_refresh and (args.heuristic or not (args.recommend and args.recommend_accept > 0)):
         ap.error("--recommend-check-refresh: needs a model and --recommend K --recommend-accept M")
     if args.recommend_undo and not (args.recommend and args.recommend_accept > 0):

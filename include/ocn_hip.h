@@ -52,7 +52,8 @@ extern "C" {
  *    common neighbour in the pooled vectors' part of a score); ocn_frontier_window_cols, ocn_frontier_count,
  *    ocn_frontier_sums_fill (frontier expansion with ordered path sums: chained, the candidates within three hops and their
  *    local path index); ocn_segment_rank (the place of held-out links among a source's candidates, in the order of
- *    ocn_segment_topk: ranking metrics). */
+ *    ocn_segment_topk: ranking metrics); ocn_sample_two_hop_window_cols, ocn_sample_two_hop (hard negatives: draws from the
+ *    2-hop candidate set that is served, selected in the expansion's LDS bitmap without listing the set). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -587,6 +588,32 @@ int ocn_sample_complement_rows(const int64_t* rowptrK, const int32_t* colK, int6
 int ocn_sample_complement_pairs(const int64_t* rowptrK, const int32_t* colK, int64_t n_cols,
                                 const int64_t* cptr /* [n_cols + 1] */, int64_t T, int64_t t0, uint64_t seed,
                                 int64_t* out /* [2][T] */, void* stream);
+
+/* Hard negatives: draws from the candidate set that recommendation serves, not from all non-links.  For query q with
+ * s = rows[q] the set H_q is that of ocn_two_hop_diff_count / _fill word for word,
+ *   ( U_{m in A[s,:]} A[m,:] ) \ M[s,:], without column s too when drop_self != 0,
+ * and c_q = |H_q| (written to count[q] where count is given: ocn_two_hop_diff_count's value).  Query q owns the slots
+ * sptr[q] .. sptr[q + 1] of out (sptr ascends from 0 and is trusted, as `off` is elsewhere; a query may own none; a source
+ * may repeat).  Slot i receives the r_i-th smallest member of H_q (0-based), r_i = floor(u_i * c_q / 2^64) for the 64-bit word
+ * u_i = out[0] | out[1] << 32 of Philox4x32-10 under the key rule above, with counters of their own streams:
+ *   sid == NULL : (i - sptr[q], (q0 + q) & 0xffffffff, (q0 + q) >> 32, 3)
+ *   sid given   : (sid[i] & 0xffffffff, sid[i] >> 32, 0, 4), and q0 is ignored
+ * — uniform over H_q with replacement — or -1 where H_q is empty.  A sample is fixed bit for bit by (seed, its own index, A,
+ * M, s): not by the window width, the launch geometry, Q or the other slots.  No global atomics, no workspace.
+ * The candidates are never listed: a workgroup owns a query, builds each window's part of H_q as the LDS bitmap of
+ * ocn_two_hop_diff_* (the same device function), keeps the block scan of its threads' popcounts in LDS, and one thread per
+ * slot finds its member there (a search of the thread prefixes, a walk of one thread's words, the n-th set bit).  Where the
+ * column range fits one window the same expansion yields c_q and the selection; a wider graph is swept twice, once for c_q
+ * and once selecting behind a running base.  The prefix table takes LDS from the bitmap: the default window is this entry's
+ * own, ocn_sample_two_hop_window_cols() (a multiple of 64, about 1.28 M columns).  window_cols, A, M, rows[]: as for
+ * ocn_two_hop_diff_*, against that limit.
+ * NULL pointers (sid and count excepted), Q < 0, q0 < 0, n_cols outside 1 .. 2^31 - 1, a bad window_cols: OCN_EINVAL before any
+ * HIP call.  Q == 0 returns 0 (after the checks). */
+int64_t ocn_sample_two_hop_window_cols(void);
+int ocn_sample_two_hop(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM, int64_t n_cols,
+                       const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols /* 0: the default */,
+                       const int64_t* sptr /* [Q + 1] */, const int64_t* sid /* [sptr[Q]] or NULL */, int64_t q0, uint64_t seed,
+                       int32_t* count /* [Q] or NULL */, int64_t* out /* [sptr[Q]] */, void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

@@ -82,6 +82,9 @@ SIGNATURES = {
     "ocn_sample_stage_cols": (c_int32, []),
     "ocn_sample_complement_rows": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int64, c_int64, ctypes.c_uint64, _P, _P]),
     "ocn_sample_complement_pairs": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int64, ctypes.c_uint64, _P, _P]),
+    "ocn_sample_two_hop_window_cols": (c_int64, []),
+    "ocn_sample_two_hop": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, c_int64, ctypes.c_uint64, _P, _P,
+                                     _P]),
     "ocn_gather_schedule": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "ocn_coo_to_csr_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     "ocn_coo_to_csr": (c_int32, [_P, _P, c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

@@ -13,7 +13,7 @@ constexpr int FR_TAGS = 256;                                 // claim slots per 
 constexpr i64 FR_WINDOW = (i64)(160 * 1024 - 2048 - OCN_WPB * FR_TAGS * 4) * 8 / 33 / 64 * 64;
 constexpr unsigned FR_FREE = 0xffffffffu;                    // a claim slot nobody bids for
 
-// first position of the sorted row a[0..n) whose column is not below key (recommend.hip keeps its own copy: th_lower_bound)
+// first position of the sorted row a[0..n) whose column is not below key (two_hop_window.h keeps its own copy: th_lower_bound)
 __device__ __forceinline__ i64 fr_lower_bound(const int32_t* __restrict__ a, i64 n, i64 key) {
   i64 lo = 0, hi = n;
   while (lo < hi) {

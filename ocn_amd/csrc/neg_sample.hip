@@ -5,14 +5,20 @@
 // number of free columns below x_i, a non-decreasing sequence): one binary search on the CSR row, whatever its length.
 // Every sample is a function of (seed, its own index, known) alone: no atomics, no workspace, no launch geometry in the result.
 // See include/ocn_hip.h (ocn_philox4x32, ocn_complement_count, ocn_sample_complement_rows, ocn_sample_complement_pairs).
+// Hard negatives are drawn the same way from the candidate set that is served: the r-th smallest member of a source's 2-hop row
+// difference, selected in the LDS bitmap the 2-hop expansion builds, without ever listing the set (ocn_sample_two_hop).
+#include <atomic>
+
 #include "common.h"
+#include "two_hop_window.h"
 
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants)
 // ---------------------------------------------------------------------------------------------
 constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
 constexpr unsigned PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-constexpr unsigned SAMPLE_STREAM_PAIRS = 1u, SAMPLE_STREAM_ROWS = 2u;      // counter word 3: the two samplers never share a word
+constexpr unsigned SAMPLE_STREAM_PAIRS = 1u, SAMPLE_STREAM_ROWS = 2u;      // counter word 3: the samplers never share a word
+constexpr unsigned SAMPLE_STREAM_TWO_HOP = 3u, SAMPLE_STREAM_TWO_HOP_ID = 4u;
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
 #pragma unroll
@@ -169,6 +175,110 @@ __global__ __launch_bounds__(OCN_BLOCK) void sample_pairs_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// selection in a 2-hop row difference: H_q = ( U_{m in A[s,:]} A[m,:] ) \ M[s,:]
+// ---------------------------------------------------------------------------------------------
+// The default window: the bitmap kernel's (recommend.hip: TH_WINDOW) less the 2 KiB the thread prefixes are rounded up to.
+// 1 277 952 columns, a multiple of 64.
+constexpr i64 S2_WINDOW = (i64)(160 * 1024 - 4096) * 8;
+
+// the n-th set bit (0-based) of a word that has more than n
+__device__ __forceinline__ int nth_set_bit(unsigned bits, int n) {
+  for (int k = 0; k < n; ++k) bits &= bits - 1;
+  return __ffs((int)bits) - 1;
+}
+
+// the rank slot i draws among m candidates: one 64-bit word of its own counter
+__device__ __forceinline__ i64 two_hop_rank(const i64* __restrict__ sid, i64 i, i64 slot0, u64 qq, u64 seed, i64 m) {
+  uint4 ctr;
+  if (sid) {
+    const u64 id = (u64)sid[i];
+    ctr = make_uint4((unsigned)id, (unsigned)(id >> 32), 0u, SAMPLE_STREAM_TWO_HOP_ID);
+  } else {
+    ctr = make_uint4((unsigned)(i - slot0), (unsigned)qq, (unsigned)(qq >> 32), SAMPLE_STREAM_TWO_HOP);
+  }
+  return (i64)sample_rank(ctr, seed, (u64)m);
+}
+
+// A workgroup owns query q and sweeps the column range in windows, as two_hop_diff_kernel does: th_window_bitmap leaves the
+// window's part of H_q as a bitmap in LDS, every thread counts the bits of its contiguous words and the block scan of these
+// counts — the thread prefixes, kept in LDS — orders the window's members.  Then a thread per slot, OCN_BLOCK slots at a time:
+// it draws its rank r again from its counter, and where base <= r < base + the window's total it finds the thread whose
+// words hold member r - base (a search of the prefixes in fixed trips), walks that thread's words by popcount and takes the
+// n-th set bit of the word.  A slot is written by exactly one window, or with -1 where H_q is empty.
+// The rank needs c_q = |H_q| before the first selection: when the whole column range is one window (`window >= n_cols`, a
+// kernel argument) its total is c_q and one expansion serves both; else a first sweep counts and a second one selects.
+// Every barrier is reached by the whole workgroup: the query and the window loops run on blockIdx and kernel arguments, the
+// slot loop (which holds no barrier) on sptr[q], sptr[q + 1], which every thread reads alike — never on a row length.
+__global__ __launch_bounds__(OCN_BLOCK) void sample_two_hop_kernel(
+    const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
+    const i64* __restrict__ rowptrM, const int32_t* __restrict__ colM, i64 n_cols,
+    const i64* __restrict__ rows, i64 Q, int drop_self, i64 window,
+    const i64* __restrict__ sptr, const i64* __restrict__ sid, i64 q0, u64 seed,
+    int32_t* __restrict__ count, i64* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned th_bm[];
+  __shared__ i64 sh[2 * OCN_WPB];
+  __shared__ int s_pre[OCN_BLOCK];                           // members of the window in the words of the threads below (< 2^21)
+  const bool one_window = window >= n_cols;
+  for (i64 q = blockIdx.x; q < Q; q += gridDim.x) {
+    const i64 slot0 = sptr[q], slot1 = sptr[q + 1];
+    if (slot1 <= slot0 && !count) continue;                  // (the same in every thread: nothing to write for this query)
+    const i64 s = rows[q];
+    const i64 a0 = rowptrA[s], da = rowptrA[s + 1] - a0;
+    const i64 m0 = rowptrM[s], dm = rowptrM[s + 1] - m0;
+    const u64 qq = (u64)(q0 + q);
+    i64 cq = 0;
+    if (!one_window) {                                       // the counting sweep: two_hop_diff_kernel<false>
+      for (i64 w0 = 0; w0 < n_cols; w0 += window) {
+        const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
+        const int words = (int)((w1 - w0 + 31) >> 5);
+        th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);
+        int t0, t1;
+        i64 tot;
+        block_excl_scan(th_thread_bits(th_bm, words, t0, t1), sh, &tot);
+        cq += tot;                                           // (the scan's last barrier keeps the next clear behind these reads)
+      }
+    }
+    if (one_window || (cq > 0 && slot1 > slot0)) {           // the selecting sweep (the same in every thread)
+      i64 base = 0;
+      for (i64 w0 = 0; w0 < n_cols; w0 += window) {
+        const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
+        const int words = (int)((w1 - w0 + 31) >> 5);
+        th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);
+        int t0, t1;
+        i64 tot;
+        s_pre[threadIdx.x] = (int)block_excl_scan(th_thread_bits(th_bm, words, t0, t1), sh, &tot);
+        if (one_window) cq = tot;
+        __syncthreads();                                     // the prefixes of all threads, before any slot searches them
+        if (tot > 0) {
+          const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;
+          for (i64 i = slot0 + threadIdx.x; i < slot1; i += OCN_BLOCK) {
+            const i64 r = two_hop_rank(sid, i, slot0, qq, seed, cq) - base;
+            if (r < 0 || r >= tot) continue;                 // another window's member
+            int at = 0;                                      // the last thread whose prefix does not exceed r: its words hold it
+            for (int step = OCN_BLOCK >> 1; step > 0; step >>= 1) at += (s_pre[at + step] <= (int)r) ? step : 0;
+            int left = (int)r - s_pre[at];
+            const int e = (at + 1) * wpt < words ? (at + 1) * wpt : words;
+            i64 v = -1;
+            for (int w = at * wpt; w < e; ++w) {
+              const unsigned bits = th_bm[w];
+              const int pc = __popc(bits);
+              if (left < pc) { v = w0 + ((i64)w << 5) + nth_set_bit(bits, left); break; }
+              left -= pc;
+            }
+            out[i] = v;
+          }
+        }
+        base += tot;
+        __syncthreads();                                     // the next window's clear and prefixes stay behind these reads
+      }
+    }
+    if (cq == 0)
+      for (i64 i = slot0 + threadIdx.x; i < slot1; i += OCN_BLOCK) out[i] = -1;
+    if (count && threadIdx.x == 0) count[q] = (int32_t)cq;
+  }
+}
+
 static inline bool ns_cols_ok(int64_t n_cols) { return n_cols >= 1 && n_cols < ((int64_t)1 << 31); }
 static inline unsigned ns_thread_grid(i64 items) { return (unsigned)grid_for((items + OCN_BLOCK - 1) / OCN_BLOCK, 256 * 8); }
 
@@ -214,6 +324,35 @@ int ocn_sample_complement_pairs(const int64_t* rowptrK, const int32_t* colK, int
   if (T == 0) return 0;
   hipLaunchKernelGGL(sample_pairs_kernel, dim3(ns_thread_grid(T)), dim3(OCN_BLOCK), 0, (hipStream_t)stream, (const i64*)rowptrK,
                      colK, (i64)n_cols, (const i64*)cptr, (i64)T, (i64)t0, (u64)seed, (i64*)out);
+  return launch_status();
+}
+
+int64_t ocn_sample_two_hop_window_cols(void) { return S2_WINDOW; }
+
+int ocn_sample_two_hop(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM, int64_t n_cols,
+                       const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, const int64_t* sptr,
+                       const int64_t* sid, int64_t q0, uint64_t seed, int32_t* count, int64_t* out, void* stream) {
+  if (!rowptrA || !colA || !rowptrM || !colM || !rows || !sptr || !out || !ns_cols_ok(n_cols)) return OCN_EINVAL;
+  if (Q < 0 || q0 < 0 || q0 > INT64_MAX - Q) return OCN_EINVAL;             // (the query counter q0 + q stays a non-negative int64)
+  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > S2_WINDOW) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  const i64 window = window_cols ? (i64)window_cols : S2_WINDOW;
+  const i64 padded = (n_cols + 63) / 64 * 64;
+  const size_t lds = (size_t)((window < padded ? window : padded) / 8);       // a small graph keeps several workgroups per CU
+  // The LDS limit of the kernel is raised ONCE per device, to what the default window takes — never per launch to that launch's
+  // size: two host threads that launch graphs of different widths would race between the set and the launch.
+  static std::atomic<unsigned long long> lds_raised{0ull};
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return (int)err;
+  if (dev >= 64 || !((lds_raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    err = hipFuncSetAttribute((const void*)sample_two_hop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S2_WINDOW / 8));
+    if (err != hipSuccess) return (int)err;
+    if (dev < 64) lds_raised.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(sample_two_hop_kernel, dim3((unsigned)grid_for(Q, 256 * 16)), dim3(OCN_BLOCK), lds, (hipStream_t)stream,
+                     (const i64*)rowptrA, colA, (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self,
+                     window, (const i64*)sptr, (const i64*)sid, (i64)q0, (u64)seed, count, (i64*)out);
   return launch_status();
 }
 

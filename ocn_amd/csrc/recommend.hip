@@ -10,6 +10,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "two_hop_window.h"
 
 // ---------------------------------------------------------------------------------------------
 // row difference P[s,:] \ M[s,:]
@@ -85,19 +86,9 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
 // runtime), as bits.  1 294 336 columns, a multiple of 64.
 constexpr i64 TH_WINDOW = (i64)(160 * 1024 - 2048) * 8;
 
-// first position of the sorted row a[0..n) whose column is not below key; the same steps and the same loads in every lane
-// (not common.h's sorted_has: it returns the position, and the key is a 64-bit window bound)
-__device__ __forceinline__ i64 th_lower_bound(const int32_t* __restrict__ a, i64 n, i64 key) {
-  i64 lo = 0, hi = n;
-  while (lo < hi) {
-    const i64 mid = lo + ((hi - lo) >> 1);
-    if ((i64)a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // One body for both passes, so they cannot disagree.  A workgroup owns query q; the column range is swept in windows
-// [w0, w1) of `window` columns, the window's part of the set as a bitmap in LDS:
+// [w0, w1) of `window` columns, the window's part of the set as a bitmap in LDS (steps 1 - 3: th_window_bitmap of
+// two_hop_window.h, which the 2-hop sampler of neg_sample.hip calls too):
 //   1. the bitmap is cleared;
 //   2. a wave takes a neighbour m of s, finds where row m enters the window (binary search, skipped for the first window)
 //      and sets a bit per column below w1 — LDS atomicOr: the lanes of a wave, and the waves, do meet in one word;
@@ -114,7 +105,6 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
     int32_t* __restrict__ count, const i64* __restrict__ off, longlong2* __restrict__ edges) {
   extern __shared__ __attribute__((aligned(16))) unsigned th_bm[];
   __shared__ i64 sh[2 * OCN_WPB];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (i64 q = blockIdx.x; q < Q; q += gridDim.x) {
     const i64 s = rows[q];
     const i64 a0 = rowptrA[s], da = rowptrA[s + 1] - a0;
@@ -124,41 +114,9 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
     for (i64 w0 = 0; w0 < n_cols; w0 += window) {
       const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
       const int words = (int)((w1 - w0 + 31) >> 5);
-      for (int w = threadIdx.x; w < words; w += OCN_BLOCK) th_bm[w] = 0u;
-      __syncthreads();
-      for (i64 t = wave; t < da; t += OCN_WPB) {
-        const i64 m = colA[a0 + t];
-        const i64 b0 = rowptrA[m], db = rowptrA[m + 1] - b0;
-        const i64 lo = w0 > 0 ? th_lower_bound(colA + b0, db, w0) : 0;
-        for (i64 p = lo + lane; p < db; p += OCN_WAVE) {
-          const i64 c = colA[b0 + p];
-          if (c >= w1) break;                                // (sorted: so is every later column of this lane)
-          if (c >= w0) {
-            const unsigned k = (unsigned)(c - w0);
-            atomicOr(&th_bm[k >> 5], 1u << (k & 31u));
-          }
-        }
-      }
-      __syncthreads();
-      const i64 lo_m = w0 > 0 ? th_lower_bound(colM + m0, dm, w0) : 0;
-      for (i64 p = lo_m + threadIdx.x; p < dm; p += OCN_BLOCK) {
-        const i64 c = colM[m0 + p];
-        if (c >= w1) break;
-        if (c >= w0) {
-          const unsigned k = (unsigned)(c - w0);
-          atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
-        }
-      }
-      if (drop_self && threadIdx.x == 0 && s >= w0 && s < w1) {
-        const unsigned k = (unsigned)(s - w0);
-        atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
-      }
-      __syncthreads();
-      const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;   // contiguous words per thread: ascending columns in thread order
-      const int t0 = (int)threadIdx.x * wpt < words ? (int)threadIdx.x * wpt : words;
-      const int t1 = (t0 + wpt) < words ? (t0 + wpt) : words;
-      i64 c = 0;
-      for (int w = t0; w < t1; ++w) c += __popc(th_bm[w]);
+      th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);   // steps 1 - 3
+      int t0, t1;                                            // contiguous words per thread: ascending columns in thread order
+      const i64 c = th_thread_bits(th_bm, words, t0, t1);
       i64 tot;
       const i64 ex = block_excl_scan(c, sh, &tot);
       if (FILL) {

@@ -1176,6 +1176,44 @@ def sample_complement_pairs(rowptrK: Tensor, colK: Tensor, cptr: Tensor, num: in
     return out
 
 
+def sample_two_hop_window_cols() -> int:
+    """Columns of one LDS window of ``ocn_sample_two_hop`` (the 2-hop bitmap less the thread prefixes the selection searches)."""
+    return int(_lib.lib().ocn_sample_two_hop_window_cols())
+
+
+@_on_device
+def sample_two_hop(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, sptr: Tensor, seed: int,
+                   sid: Optional[Tensor] = None, first: int = 0, drop_self: bool = True, total: Optional[int] = None,
+                   want_count: bool = False, window_cols: int = 0):
+    """Uniform draws, with replacement, from the set ``two_hop_diff_fill`` lists for s = rows[q] — without listing it (ocn_hip.h:
+    ocn_sample_two_hop).  Query q owns the slots ``sptr[q] .. sptr[q + 1]`` of the result (``sptr``: int64 [Q + 1] ascending
+    from 0, trusted; ``total`` = ``sptr[-1]`` where the caller knows it, else read here: one host sync): int64 [total], -1 in
+    the slots of a query whose set is empty.  Slot i is fixed by (seed, first + q, i - sptr[q], A, M, s), or with ``sid`` (int64
+    [total], non-negative sample ids) by (seed, sid[i], A, M, s) and ``first`` is ignored.  ``want_count``: returns (out, count)
+    with count int32 [Q] = ``two_hop_diff_count`` of the same operands.  ``window_cols``: 0, the library's window, except in
+    tests of the sweep."""
+    Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols, sample_two_hop_window_cols)
+    T = _scan_total(sptr, Q, total, "sptr", "sptr: one entry per query and the total")
+    first = int(first)
+    if first < 0:
+        raise ValueError(f"first must not be negative, got {first}")
+    seed = _seed(seed)
+    if sid is not None:
+        if _req(sid, torch.int64, "sid", 1).numel() != T:
+            raise ValueError(f"sid: one sample id per slot ({T}), got {sid.numel()}")
+        if sid.device != rows.device:
+            raise RuntimeError(f"sample_two_hop: operands on different devices ({rows.device}, {sid.device})")
+    out = torch.empty(max(T, 1), dtype=torch.int64, device=rows.device)      # (a count-only call still hands the entry an address)
+    count = torch.empty(Q, dtype=torch.int32, device=rows.device) if want_count else None
+    if Q and (T or want_count):
+        check(_lib.lib().ocn_sample_two_hop(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q, int(bool(drop_self)),
+                                            int(window_cols), ptr(sptr), ptr(sid), first, seed, ptr(count), ptr(out), stream_ptr()),
+              "ocn_sample_two_hop")
+        _mark("sample_two_hop")
+    out = out[:T]
+    return (out, count) if want_count else out
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 
