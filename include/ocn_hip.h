@@ -716,8 +716,18 @@ int ocn_cn_gather_backward_det_lists(const int64_t* rowptrA, const int32_t* colA
  *             1 -> entry weight is fl(pre[r]*pre[k]) (GCNConv / PureConv2: normalised A).
  * self_mode: 0 none; 1 add the row's own term after the neighbours (PureConv gcn);
  *            2 insert it at its sorted column position (GCNConv fill_diag).
- * max of a valued adjacency is max_k fl(val_rk * x[k]) (torch_sparse spmm_max); an empty row gives 0.  Max is defined for
- * pre = post = NULL and self_mode = 0 only: no caller passes them with mode 2, and what it computes with them is unspecified. */
+ * max of a valued adjacency is max_k fl(val_rk * x[k]) (torch_sparse spmm_max); an empty row gives 0.  No caller
+ * passes pre, post or self_mode with mode 2; what it computes with them is the max over the same terms the sum adds (the
+ * self term included), times post[r] — and 0 for a row without a term.
+ * Index spaces: x has a row per COLUMN of the operator and pre an entry per row of x — pre is indexed by column id (pre[k]).
+ * post is indexed by output row.  pre[r] of the output row r is read only with edge_scale = 1 or self_mode != 0, and both need
+ * r to be a column id as well: the caller passes them only for an operator with no more rows than x has (self_mode: a square
+ * one).  With edge_scale = 0 and self_mode = 0 the operator may be rectangular either way and pre is never indexed by a row.
+ * Order of a row's terms (tests/spmm_mirror.py is this paragraph as code): the entries in ascending column order, each term
+ * fl(w * x[k]) with w = pre[k] or fl(pre[r]*pre[k]), then fl(val * w) for a valued adjacency (no pre, no val: x[k] itself),
+ * added as fl(acc + term); the self term, weight pre[r] or fl(pre[r]*pre[r]) (1 without pre), stands before the first column
+ * >= r under self_mode 2 (at the end where there is none; an entry with column r is replaced by it, not added too) and after
+ * the last entry under self_mode 1; mean divides by the number of terms added (1 where none); post[r] multiplies last. */
 int ocn_spmm_csr(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows,
                  const float* x, int32_t F, const float* pre, const float* post,
                  int32_t mode, int32_t edge_scale, int32_t self_mode,

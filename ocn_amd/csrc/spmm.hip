@@ -66,7 +66,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void spmm_csr_kernel(
   const float4* x4 = reinterpret_cast<const float4*>(x);
   const i64 rowq = F >> 2;
   const bool weighted = pre != nullptr || val != nullptr;
-  const float pr = pre ? pre[r] : 1.0f;
+  // pre lives in the operator's COLUMN space (one entry per row of x).  pre[r] is used by edge_scale and by the self term only —
+  // both need r to be a column id too — so it is loaded only for them: a rectangular operator with more rows than columns
+  // (the valued-mean backward over Aᵀ) never indexes pre with a row id.
+  const float pr = (pre && (edge_scale || self_mode)) ? pre[r] : 1.0f;
 
   float4 acc[NV];
   const float init = MODE == SPMM_MAX ? -INFINITY : 0.f;

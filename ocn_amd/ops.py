@@ -1360,6 +1360,8 @@ def spmm_csr(rowptr: Tensor, col: Tensor, x: Tensor, pre: Optional[Tensor] = Non
     n = rowptr.numel() - 1
     if pre is not None and (_req(pre, torch.float32, "pre", 1).numel() != x.shape[0]):
         raise ValueError("pre must have one entry per row of x")
+    if pre is not None and edge_scale and n > x.shape[0]:      # pre lives in the column space; edge_scale reads pre[r] too
+        raise ValueError("edge_scale reads pre[r] of every output row: the operator has more rows than pre has entries")
     if post is not None and (_req(post, torch.float32, "post", 1).numel() != n):
         raise ValueError("post must have one entry per output row")
     if self_mode and x.shape[0] != n:
@@ -1388,6 +1390,8 @@ def spmm_csr_rows(rowptr: Tensor, col: Tensor, x: Tensor, rows: Tensor, pre: Opt
         raise ValueError(f"spmm_csr_rows: unsupported width {x.shape[1]}")
     if pre is not None and (_req(pre, torch.float32, "pre", 1).numel() != x.shape[0]):
         raise ValueError("pre must have one entry per row of x")
+    if pre is not None and edge_scale and n > x.shape[0]:      # pre lives in the column space; edge_scale reads pre[r] too
+        raise ValueError("edge_scale reads pre[r] of every output row: the operator has more rows than pre has entries")
     if post is not None and (_req(post, torch.float32, "post", 1).numel() != n):
         raise ValueError("post must have one entry per output row")
     if self_mode and x.shape[0] != n:
