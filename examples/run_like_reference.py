@@ -17,6 +17,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32 --recommend-eval 200   # ... and where the test links rank
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain-edges 10 # ... down to the edges: the 10 strongest messages
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
     python examples/run_like_reference.py --dataset cora --structured-negatives           # training negatives that are never links
     python examples/run_like_reference.py --dataset citation2 --scale 0.002 --hiddim 64 --structured-negatives   # ... and MRR negatives
@@ -35,7 +36,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ocn_amd import ops                                                             # noqa: E402
 from ocn_amd.evaluate import Evaluator                                              # noqa: E402
-from ocn_amd.explain import explain_links                                           # noqa: E402
+from ocn_amd.explain import explain_link_edges, explain_links                       # noqa: E402
 from ocn_amd.frozen import freeze_columns                                           # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
@@ -303,6 +304,20 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
                                                 exp.pooled.tolist()):
                 print(f"explain source {s} target {t} score {v:.4f} pooled {share[0]:+.4f} {share[1]:+.4f} top-{args.recommend_explain}: "
                       + " ".join(f"{n}({a:+.4f},{b:+.4f})" for n, (a, b) in zip(ks, cs) if n >= 0), flush=True)
+    if args.recommend_explain_edges:
+        # --recommend-explain-edges M: which links of the graph made the first printed recommendation look the way it does —
+        # gradient x input on the messages of every conv layer (ocn_amd.explain.explain_link_edges), through the pooling and the
+        # encoder.  The winners again form one batch; the explained candidate is its first row
+        won = torch.stack([sources.view(-1, 1).expand_as(dst).reshape(-1), dst.reshape(-1)], dim=1)
+        won = won[won[:, 1] >= 0].contiguous()
+        if won.shape[0]:
+            ex = explain_link_edges(model, predictor, data.x, adj, adj2, won, 0, top=args.recommend_explain_edges, args=args)
+            s, t = won[0].tolist()
+            print(f"explain-edges source {s} target {t} score {float(ex.score):.4f}: the {args.recommend_explain_edges} strongest messages "
+                  f"of {ex.per_layer.shape[1]} conv layers, as col->row(total; per layer)", flush=True)
+            for (r, c), v, per in zip(ex.entries.tolist(), ex.saliency.tolist(), ex.per_layer.tolist()):
+                if r >= 0:
+                    print(f"explain-edges message {c}->{r} ({v:+.3e}; " + " ".join(f"{p:+.3e}" for p in per) + ")", flush=True)
     if args.recommend_accept > 0:
         # --recommend-accept M: the M best of these links join the graph (ocn_amd.update.insert_edges: A and the stored A² are
         # updated, not rebuilt; the node embeddings are refreshed row by row, EncoderState) and the same sources are asked again
@@ -390,6 +405,9 @@ def main(argv=None):
     ap.add_argument("--recommend-explain", type=int, default=0, metavar="M",
                     help="with --recommend and a cn5 / cn7 / cn8 model: explain the K winners of the printed sources as one batch "
                          "(ocn_amd.explain) and print each target's top-M common neighbours with their two contributions")
+    ap.add_argument("--recommend-explain-edges", type=int, default=0, metavar="M",
+                    help="with --recommend and a cn5 / cn7 / cn8 model: list the M strongest messages (links of the graph, per conv "
+                         "layer) behind the first printed recommendation (ocn_amd.explain.explain_link_edges)")
     ap.add_argument("--recommend-accept", type=int, default=0, metavar="M",
                     help="with --recommend: insert the M best recommended links into the graph (ocn_amd.update) and recommend again")
     ap.add_argument("--recommend-undo", action="store_true",
@@ -412,6 +430,9 @@ def main(argv=None):
     if args.recommend_explain and (args.heuristic or not args.recommend or args.predictor == "cn6"
                                    or not 1 <= args.recommend_explain <= 128):
         ap.error("--recommend-explain M: needs --recommend K, a cn5, cn7 or cn8 model and 1 <= M <= 128")
+    if args.recommend_explain_edges and (args.heuristic or not args.recommend or args.predictor == "cn6"
+                                         or not 1 <= args.recommend_explain_edges <= 128):
+        ap.error("--recommend-explain-edges M: needs --recommend K, a cn5, cn7 or cn8 model and 1 <= M <= 128")
     if args.recommend_hops != 2 and not args.recommend:
         ap.error("--recommend-hops: needs --recommend K")
     if args.recommend_eval < 0 or (args.recommend_eval and not args.recommend):

@@ -53,7 +53,8 @@ extern "C" {
  *    ocn_frontier_sums_fill (frontier expansion with ordered path sums: chained, the candidates within three hops and their
  *    local path index); ocn_segment_rank (the place of held-out links among a source's candidates, in the order of
  *    ocn_segment_topk: ranking metrics); ocn_sample_two_hop_window_cols, ocn_sample_two_hop (hard negatives: draws from the
- *    2-hop candidate set that is served, selected in the expansion's LDS bitmap without listing the set). */
+ *    2-hop candidate set that is served, selected in the expansion's LDS bitmap without listing the set); ocn_sddmm_csr (the sampled
+ *    dense-dense product on the pattern of an encoder operator: the gradient of a layer with respect to its messages). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -759,6 +760,27 @@ int ocn_spmm_csr_max_arg(const int64_t* rowptr, const int32_t* col, const float*
                          const float* x, int32_t F, float* y, int32_t* arg, void* stream);
 int ocn_spmm_max_backward(const int64_t* rowptrT, const int32_t* colT, const float* valT, int64_t n_rows,
                           const int32_t* arg, const float* g, int32_t F, float* gx, void* stream);
+
+/* The sampled dense-dense product on the pattern of the operator (SDDMM): the gradient of ocn_spmm_csr's y with respect to a
+ * mask on its messages, at mask = 1 — out[p] = fl(c * d) for entry p of row r with column k, where
+ *   w = the entry weight exactly as the forward forms it: 1 without pre, pre[k] with edge_scale = 0, fl(pre[r]*pre[k]) with
+ *       edge_scale = 1, then fl(val[p]*w) for a valued adjacency;
+ *   c = w, then fl(post[r]*c) with post, then fl(c / len_r) with mode 1 (len_r = the row's entry count);
+ *   d = sum_f g[r][f]*x[k][f] in fp32: every lane of the row's lane group chains fused multiply-adds over its own features
+ *       (ascending), an xor butterfly adds the lanes — the order depends on F only, not on the launch geometry, the row
+ *       length or the rest of the matrix, so an entry has the same bits in any operator that holds it with the same operands.
+ * The self term is no entry and gets no output; under self_mode 2 an entry with k == r gets +0 (the forward replaces it by the
+ * self term).  rowptr / col / val / pre / post / mode / edge_scale / self_mode are ocn_spmm_csr's; g = [n_rows][F], x = one row
+ * per column, out = [nnz].  Every out[p] below rowptr[n_rows] is written and nothing else; no atomics, no workspace.  Long rows
+ * are cut into fixed-size runs of entries, so a hub row is many work items.
+ * OCN_EINVAL before any HIP call: F outside {16, 32, 64, 128, 256, 512}; mode 2 (max has no per-message linearisation) or out
+ * of range; mode 1 together with pre, post or self_mode; self_mode out of range; NULL rowptr / col / g / x / out; g or x not
+ * 16-byte aligned; n_rows < 0.  n_rows == 0 (otherwise valid) returns 0 without a launch. */
+int ocn_sddmm_csr(const int64_t* rowptr, const int32_t* col, const float* val /* or NULL */, int64_t n_rows,
+                  const float* g /* [n_rows][F] */, const float* x /* [n_cols][F] */, int32_t F,
+                  const float* pre /* or NULL */, const float* post /* or NULL */,
+                  int32_t mode /* 0 sum, 1 mean */, int32_t edge_scale, int32_t self_mode,
+                  float* out /* [nnz] */, void* stream);
 
 /* out[r] = 1/sqrt(add + deg(r)) (0 where the argument is 0): rsqrt_(1+adj.sum(-1)) of
  * model.py:51,106 (add=1) and gcn_norm's deg^-1/2 (add=1 after fill_diag); deg = row length, or the

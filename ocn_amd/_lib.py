@@ -110,6 +110,7 @@ SIGNATURES = {
     "ocn_spmm_csr_rows": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
     "ocn_spmm_csr_max_arg": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, _P, _P, _P]),
     "ocn_spmm_max_backward": (c_int32, [_P, _P, _P, c_int64, _P, _P, c_int32, _P, _P]),
+    "ocn_sddmm_csr": (c_int32, [_P, _P, _P, c_int64, _P, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "ocn_deg_rsqrt": (c_int32, [_P, _P, c_int64, c_float, _P, _P]),
     "ocn_spgemm_max_cols": (c_int64, []),
     "ocn_spgemm_pattern_count": (c_int32, [_P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P]),

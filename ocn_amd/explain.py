@@ -18,8 +18,17 @@ strongest per pair.
     exp.nodes[e]        # the m common neighbours that count most for edges[e], best first (-1: fewer than m)
     exp.contrib[e]      # their shares {via xcn1, via xcn2}; exp.pooled[e] is what all members together account for
 
-cn6 (three tables and ``nip``), edge-sharded predictors, training mode, attribution to the encoder's inputs and explanations
-accumulated over batches are out of scope.
+``explain_link_edges`` goes on from there, through the encoder: which MESSAGES of the graph made h[i], h[j] and the h[k] look the
+way they do.  Put a mask M = 1 on every message of every conv layer (``model.message_masks``); the saliency of message v -> u in
+layer l is d score_e / d M_l[u, v] at M = 1 — gradient x input again, the normalisation coefficients held fixed as PyG's
+explainers hold them.  The gradient of a layer with respect to its messages is the sampled dense-dense product on the pattern
+of A (``ops.sddmm_csr``); ``ops.segment_topk`` lists the strongest.
+
+    ex = explain_link_edges(model, predictor, x, adj, adj2, edges, which, top=20)
+    ex.entries[t]       # message col -> row as (row, col); ex.saliency[t] its total, ex.per_layer[t] its share per conv layer
+
+cn6 (three tables and ``nip``), ``max`` aggregation, edge-sharded predictors, training mode, several GPUs, symmetrising the
+messages (u, v) and (v, u), and explanations accumulated over batches are out of scope.
 """
 from __future__ import annotations
 
@@ -64,27 +73,31 @@ if hasattr(torch.serialization, "add_safe_globals"):        # (torch.load's weig
     torch.serialization.add_safe_globals([LinkExplanation])
 
 
-def _check_request(predictor, h, edges, m, rank, args) -> int:
-    """The refusals, all before any device work; returns ``m``."""
+_NO_H = object()
+
+
+def _check_request(predictor, h, edges, m, rank, args, what: str = "explain_links", count: str = "m") -> int:
+    """The refusals, all before any device work; returns ``m``.  ``h=_NO_H``: there is no embedding matrix to check yet
+    (``explain_link_edges`` forms it)."""
     from .model import (CNLinkPredictor3hopCNs, CNLinkPredictorbaselearn, CNLinkPredictorbaselearnablation,
                         CNLinkPredictorOringin)
     if isinstance(predictor, CNLinkPredictor3hopCNs):
         raise NotImplementedError("cn6 pools with three column tables and nip: explaining it is not built")
     if not isinstance(predictor, (CNLinkPredictorOringin, CNLinkPredictorbaselearn, CNLinkPredictorbaselearnablation)):
-        raise TypeError(f"explain_links takes a cn5, cn7 or cn8 predictor, got {type(predictor).__name__}")
+        raise TypeError(f"{what} takes a cn5, cn7 or cn8 predictor, got {type(predictor).__name__}")
     if predictor.training:
-        raise RuntimeError("explain_links explains eval-mode scores; call predictor.eval() first")
+        raise RuntimeError(f"{what} explains eval-mode scores; call predictor.eval() first")
     if predictor._sharded:
         raise RuntimeError("an edge-sharded predictor scores one rank's slice of a batch: explain on an unsharded one")
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= ops.segment_topk_max_k():
-        raise ValueError(f"m must be an int in 1..{ops.segment_topk_max_k()}, got {m!r}")
+        raise ValueError(f"{count} must be an int in 1..{ops.segment_topk_max_k()}, got {m!r}")
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
     if not isinstance(edges, Tensor) or edges.dim() != 2 or edges.shape[1] != 2 or edges.dtype != torch.int64:
         raise ValueError("edges must be an int64 [B, 2] tensor")
     if not 1 <= int(edges.shape[0]) <= ops.MAX_BATCH:
         raise ValueError(f"edges is ONE batch of 1 .. {ops.MAX_BATCH} candidates (the histogram field width), got {int(edges.shape[0])}")
-    if not isinstance(h, Tensor) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[1] not in ops.LN_WIDTHS:
+    if h is not _NO_H and (not isinstance(h, Tensor) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[1] not in ops.LN_WIDTHS):
         raise ValueError(f"h must be float32 [N, H] with H in {ops.LN_WIDTHS}")
     if predictor._weights_need_args and predictor._frozen is None and args is None:
         raise ValueError("cn7's column weights read args.sum: pass args (or install frozen column weights)")
@@ -191,3 +204,121 @@ def explain_links(predictor, h: Tensor, adj, adj2, edges: Tensor, m: int = 8, ar
                                flat=(st.off, attr, rk) if return_flat else None,
                                _grads=(g1, g2, g3) if return_flat else None,
                                _pooled_vectors=(xcn1, xcn2, xij) if return_flat else None)
+
+
+# ---- down to the edges: message saliency through the encoder ----------------------------------------------------------------------
+@dataclass
+class EdgeExplanation:
+    """What ``explain_link_edges`` returns for one candidate.  ``score`` fp32 scalar: the autograd path's score of the pair;
+    ``entries`` int64 [top, 2]: the listed messages as (row, col) of the adjacency — message col -> row — strongest first, -1
+    where fewer than ``top`` messages have a non-zero saliency; ``saliency`` fp32 [top]: their totals over the conv layers,
+    padding 0; ``per_layer`` fp32 [top, L]: the share of every conv layer (layer 0 first), padding 0; ``input_share`` fp32 [N] =
+    <d score / d x[v], x[v]>: gradient x input on the encoder's input features (None for id inputs); ``flat``
+    (``return_flat=True``, else None): fp32 [L, nnz], every message of every layer in the adjacency's CSR order.  A plain
+    object: ``torch.save`` / ``torch.load`` keep it."""
+    score: Tensor
+    entries: Tensor
+    saliency: Tensor
+    per_layer: Tensor
+    input_share: Optional[Tensor] = None
+    flat: Optional[Tensor] = None
+
+
+if hasattr(torch.serialization, "add_safe_globals"):
+    torch.serialization.add_safe_globals([EdgeExplanation])
+
+
+def _check_edge_request(model, predictor, edges, which, top, rank, args) -> int:
+    """The refusals of ``explain_link_edges``, all before any device work; returns the number of conv layers."""
+    _check_request(predictor, _NO_H, edges, top, rank, args, what="explain_link_edges", count="top")
+    if model.training:
+        raise RuntimeError("explain_link_edges explains eval-mode scores; call model.eval() first")
+    if isinstance(which, bool) or not isinstance(which, int) or not 0 <= which < int(edges.shape[0]):
+        raise ValueError(f"which must be the index of a candidate of edges, 0..{int(edges.shape[0]) - 1}, got {which!r}")
+    convs = getattr(model, "convs", None)
+    if convs is None or len(convs) == 0:
+        raise ValueError("the encoder has no message-passing layer: there is no message to attribute to")
+    if any(getattr(conv, "aggr", None) == "max" for conv in convs):
+        raise ValueError("max aggregation has no per-message linearisation: explain_link_edges takes sum, mean and gcn layers")
+    return len(convs)
+
+
+def explain_link_edges(model, predictor, x: Tensor, adj, adj2, edges: Tensor, which: int, top: int = 20, args=None,
+                       rank: str = "magnitude", return_flat: bool = False) -> EdgeExplanation:
+    """The ``top`` messages of the graph that count most for the score of candidate ``edges[which]``, through the pooling AND
+    the encoder ``model`` (a GCN / GCN2 / GCN3 of ``ocn_amd.model``): an ``EdgeExplanation``.
+
+    ``edges`` (int64 [B, 2]) is ONE batch, 1 <= B <= ``ops.MAX_BATCH``, scored as a direct ``predictor(model(x, adj), ...)`` call
+    would score it; the other candidates only supply the batch's column weights — with frozen column weights or cn8 they do not
+    matter.  ``adj2=None`` selects the walk route.  ``top`` in 1..``ops.segment_topk_max_k()``.  cn6 raises NotImplementedError,
+    training mode of either module and an edge-sharded predictor RuntimeError, a bad ``which`` / ``top`` / ``rank`` / ``edges``,
+    a ``max`` layer and cn7 without ``args`` and without a frozen table ValueError — all before any device work.
+
+    What the numbers are: GRADIENT x INPUT ON THE MESSAGES.  Every conv layer l gets a mask M_l = 1 on its nnz messages
+    (``model.message_masks``: y[u] = post[u] sum_v M_l[u, v] c(u, v) x[v] + self term); the saliency of message v -> u in layer l
+    is d score / d M_l[u, v] at M = 1, with the normalisation coefficients c held fixed (they do not see the mask).  It is
+    exact for what is linear in the messages and a linearisation through LayerNorm / ReLU and the heads, as ``explain_links``
+    documents for the heads.  The self term is no message and gets nothing.  The backward of the pooling is
+    ``gather_backward`` on the batch's flag chain, not autograd: a frozen predictor works, and no parameter's ``.grad`` is
+    touched anywhere.
+
+    ``rank``: "magnitude" lists the largest ``|saliency|`` first, "signed" the largest signed value; ``saliency`` is the sum of
+    the layers taken in layer order; ties go to the lower CSR position (``ops.segment_topk``'s order)."""
+    from .model import message_masks
+    from .utils import adjoverlap, fuse, get_cn1_cn2
+    L = _check_edge_request(model, predictor, edges, which, top, rank, args)
+    e = edges.t().contiguous()
+    adj.warm(walk=adj2 is None)
+    if adj2 is not None:
+        adj2.complete()
+    handles = get_cn1_cn2(adj, e) if adj2 is None else (adjoverlap(adj, adj, e), adjoverlap(adj, adj2, e))
+    nnz = int(adj._col.numel())
+    dev = adj._col.device
+    floats = isinstance(x, Tensor) and x.is_floating_point()
+    with torch.enable_grad():
+        xl = x.detach().clone().requires_grad_() if floats else x
+        masks = [torch.ones(nnz, dtype=torch.float32, device=dev, requires_grad=True) for _ in range(L)]
+        with message_masks(adj, masks):
+            h = model(xl, adj)
+    hc = h.detach().contiguous()
+    if hc.dim() != 2 or hc.dtype != torch.float32 or hc.shape[1] not in ops.LN_WIDTHS:
+        raise ValueError(f"the encoder's output must be float32 [N, H] with H in {ops.LN_WIDTHS}")
+    with torch.no_grad():
+        st = fuse(*handles, e, None, adj=adj)                               # always the flag chain, as in explain_links
+        w = predictor._weights(st, args)
+        xcn1, xcn2, xij = st.gather(w, hc)
+    with torch.enable_grad():
+        x1, x2, x3 = (t.detach().clone().requires_grad_() for t in (xcn1, xcn2, xij))
+        out = predictor._heads(hc, x1, x2, x3, None)
+        if out.numel() != st.B:
+            raise ValueError("explain_link_edges explains a predictor with one output channel")
+        g1, g2, g3 = torch.autograd.grad(out.reshape(-1)[which], (x1, x2, x3))     # zero outside row ``which``
+    with torch.no_grad():
+        dh = st.gather_backward(w, hc, g1, g2, g3)
+        st.check_status()
+    # the encoder backward: the L mask gradients and the input gradient, and no parameter's .grad
+    grads = torch.autograd.grad(h, masks + ([xl] if floats else []), grad_outputs=dh.reshape(h.shape), allow_unused=True)
+    with torch.no_grad():
+        flat = torch.stack([torch.zeros(nnz, dtype=torch.float32, device=dev) if g is None else g for g in grads[:L]])
+        total = flat[0].clone()
+        for l in range(1, L):
+            total += flat[l]
+        live = torch.nonzero(total != 0).flatten()                          # ascending position
+        val = total[live].contiguous()
+        by = val.abs() if rank == "magnitude" else val
+        seg = torch.tensor([0, int(live.numel())], dtype=torch.int64, device=dev)
+        best, pos = ops.segment_topk(by, seg, top)
+        pad = pos[0] < 0
+        p = live[pos[0].clamp(min=0)] if live.numel() else torch.zeros(top, dtype=torch.int64, device=dev)
+        row = torch.searchsorted(adj._rowptr, p, right=True) - 1
+        col = adj._col[p.clamp(max=max(nnz - 1, 0))].to(torch.int64) if nnz else torch.zeros_like(p)
+        entries = torch.where(pad[:, None], torch.full((), -1, dtype=torch.int64, device=dev), torch.stack([row, col], dim=1))
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        saliency = torch.where(pad, zero, total[p] if nnz else zero.expand(top))
+        per_layer = torch.where(pad[:, None], zero, flat[:, p].t() if nnz else zero.expand(top, L)).contiguous()
+        share = None
+        if floats:
+            gx = grads[L]
+            share = torch.zeros(x.shape[0], dtype=torch.float32, device=dev) if gx is None else (gx * x).sum(1)
+        return EdgeExplanation(score=out.detach().reshape(-1)[which].clone(), entries=entries, saliency=saliency, per_layer=per_layer,
+                               input_share=share, flat=flat if return_flat else None)

@@ -94,29 +94,99 @@ class _SpmmFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        adj, kw = ctx.adj, dict(ctx.kw)
+        return _spmm_input_grad(ctx.adj, ctx.kw, g, ctx.saved_tensors), None, None
+
+
+def _spmm_input_grad(adj: SparseTensor, kw, g: Tensor, saved=()) -> Tensor:
+    """The gradient of ``_SpmmFn``'s product with respect to ``x`` (its docstring says why each transpose is what it is);
+    ``saved``: what a max forward kept.  ``_MaskedSpmmFn`` returns the same gradient through the same code."""
+    kw = dict(kw)
+    g = g.contiguous()
+    mode = kw.get("mode", "sum")
+    n_rows, n_cols = adj.sparse_sizes()
+    if mode in ("mean", "max"):
+        _plain_aggr(kw)
+    if mode == "max":
+        (arg,) = saved
+        at = adj.t() if (adj._value is not None or n_rows != n_cols) else adj
+        return ops.spmm_max_backward(at._rowptr, at._col, arg, g, val=at._value, n_cols=n_rows)
+    if mode == "mean" and adj._value is not None:
+        cnt = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
+        at = adj.t()
+        return ops.spmm_csr(at._rowptr, at._col, g, pre=1.0 / cnt, mode="sum", val=at._value)
+    if adj._value is not None:
+        adj = adj.t()
+    if mode == "mean":
+        deg = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
+        return ops.spmm_csr(adj._rowptr, adj._col, g, pre=1.0 / deg, mode="sum")
+    return ops.spmm_csr(adj._rowptr, adj._col, g, val=adj._value, **kw)
+
+
+class _MaskedSpmmFn(torch.autograd.Function):
+    """``_SpmmFn`` with a mask variable on every message: y[r] = post[r] * sum_k mask[p] c(r, k) x[k] (+ self term), p the
+    position of entry (r, k).  ``mask`` is all ones BY CONTRACT and is not read: the forward is the call ``_SpmmFn.forward``
+    makes, so its bits are the unmasked layer's.  The backward returns ``_SpmmFn``'s gradient for ``x`` and, for ``mask``, the
+    sampled dense-dense product on the pattern of A (``ops.sddmm_csr``): d y / d mask[p] contracted with the upstream gradient
+    is c(r, k) <g[r], x[k]>, the normalisation coefficients held fixed.  ``max`` is refused: a winner-take-all layer has no
+    per-message linearisation here."""
+
+    @staticmethod
+    def forward(ctx, x, mask, adj, kw):
+        if kw.get("mode", "sum") == "max":
+            raise ValueError("max aggregation has no per-message linearisation: message masks take sum and mean layers")
+        if mask.dim() != 1 or mask.numel() != adj._col.numel():
+            raise ValueError("a message mask has one entry per stored entry of the adjacency")
+        ctx.adj, ctx.kw = adj, kw
+        ctx.save_for_backward(x)
+        return ops.spmm_csr(adj._rowptr, adj._col, x, val=adj._value, **kw)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        adj = ctx.adj
         g = g.contiguous()
-        mode = kw.get("mode", "sum")
-        n_rows, n_cols = adj.sparse_sizes()
-        if mode in ("mean", "max"):
-            _plain_aggr(kw)
-        if mode == "max":
-            (arg,) = ctx.saved_tensors
-            at = adj.t() if (adj._value is not None or n_rows != n_cols) else adj
-            return ops.spmm_max_backward(at._rowptr, at._col, arg, g, val=at._value, n_cols=n_rows), None, None
-        if mode == "mean" and adj._value is not None:
-            cnt = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
-            at = adj.t()
-            return ops.spmm_csr(at._rowptr, at._col, g, pre=1.0 / cnt, mode="sum", val=at._value), None, None
-        if adj._value is not None:
-            adj = adj.t()
-        if mode == "mean":
-            deg = (adj._rowptr[1:] - adj._rowptr[:-1]).clamp(min=1).to(torch.float32)
-            return ops.spmm_csr(adj._rowptr, adj._col, g, pre=1.0 / deg, mode="sum"), None, None
-        return ops.spmm_csr(adj._rowptr, adj._col, g, val=adj._value, **kw), None, None
+        gx = _spmm_input_grad(adj, ctx.kw, g) if ctx.needs_input_grad[0] else None
+        gm = ops.sddmm_csr(adj._rowptr, adj._col, g, x, val=adj._value, **ctx.kw) if ctx.needs_input_grad[1] else None
+        return gx, gm, None, None
+
+
+class message_masks:
+    """Context manager: while it is active, every ``_spmm`` call on the CSR arrays of ``adj`` runs through ``_MaskedSpmmFn``
+    with the next mask of ``masks``, in call order — whether or not its ``x`` requires grad.  The masks are all-ones float32
+    vectors of nnz entries (they are not read); after a backward pass their ``.grad`` holds the per-message gradients.  On exit
+    a number of calls other than ``len(masks)`` raises RuntimeError.  Outside the context ``_spmm`` is unchanged.  Not
+    re-entrant, one thread."""
+    _active = None
+
+    def __init__(self, adj: SparseTensor, masks):
+        self.adj, self.masks, self.calls = adj, list(masks), 0
+
+    def __enter__(self):
+        if message_masks._active is not None:
+            raise RuntimeError("message_masks is not re-entrant")
+        self.calls = 0
+        message_masks._active = self
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        message_masks._active = None
+        if exc_type is None and self.calls != len(self.masks):
+            raise RuntimeError(f"message_masks: {len(self.masks)} masks for {self.calls} aggregation calls on this adjacency")
+        return False
+
+    def take(self, adj: SparseTensor):
+        """The mask of this call, or None (another adjacency, or more calls than masks: counted, reported on exit)."""
+        if adj._rowptr is not self.adj._rowptr or adj._col is not self.adj._col:
+            return None
+        self.calls += 1
+        return self.masks[self.calls - 1] if self.calls <= len(self.masks) else None
 
 
 def _spmm(adj: SparseTensor, x: Tensor, **kw) -> Tensor:
+    if message_masks._active is not None:
+        mask = message_masks._active.take(adj)
+        if mask is not None:
+            return _MaskedSpmmFn.apply(x, mask, adj, kw)
     if torch.is_grad_enabled() and x.requires_grad:
         return _SpmmFn.apply(x, adj, kw)
     return ops.spmm_csr(adj._rowptr, adj._col, x, val=adj._value, **kw)

@@ -1409,6 +1409,53 @@ def spmm_csr_rows(rowptr: Tensor, col: Tensor, x: Tensor, rows: Tensor, pre: Opt
 
 
 @_on_device
+def sddmm_csr(rowptr: Tensor, col: Tensor, g: Tensor, x: Tensor, pre: Optional[Tensor] = None,
+              post: Optional[Tensor] = None, mode: str = "sum", edge_scale: bool = False,
+              self_mode: int = 0, val: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The sampled dense-dense product on the pattern of the operator (ocn_hip.h: ocn_sddmm_csr): float32 [nnz],
+    ``out[p] = c * <g[r], x[k]>`` for entry p = (r, k), c the coefficient ``spmm_csr`` with the same keywords gives that entry
+    — the gradient of ``spmm_csr``'s result with respect to a mask on its messages, for an upstream gradient ``g``.  ``g``
+    [n_rows, F], ``x`` [n_cols, F], F in ``LN_WIDTHS``; the other operands are ``spmm_csr``'s.  ``mode`` "max" and "mean" with
+    ``pre`` / ``post`` / ``self_mode`` are refused.  ``out``: a float32 vector of at least nnz entries to write into (the rest
+    is left alone); the result is its first nnz entries.  Column ids are trusted, as ``spmm_csr`` trusts them."""
+    _req(rowptr, torch.int64, "rowptr", 1); _req(col, torch.int32, "col", 1)
+    _req(g, torch.float32, "g", 2); _req(x, torch.float32, "x", 2)
+    n, nnz = rowptr.numel() - 1, col.numel()
+    if n < 0:
+        raise ValueError("rowptr: [n_rows + 1] offsets")
+    if g.shape[0] != n or g.shape[1] != x.shape[1]:
+        raise ValueError("g must be [n_rows, F] with the width of x")
+    if x.shape[1] not in LN_WIDTHS:
+        raise ValueError(f"sddmm_csr: unsupported width {x.shape[1]}")
+    if mode not in SPMM_MODES or SPMM_MODES[mode] == 2:
+        raise ValueError(f"sddmm_csr: mode must be sum or mean, got {mode!r} (max has no per-message linearisation)")
+    if SPMM_MODES[mode] == 1 and (pre is not None or post is not None or self_mode):
+        raise ValueError("sddmm_csr: mean takes no pre / post / self term")
+    if self_mode not in (0, 1, 2):
+        raise ValueError(f"self_mode must be 0, 1 or 2, got {self_mode!r}")
+    if pre is not None and (_req(pre, torch.float32, "pre", 1).numel() != x.shape[0]):
+        raise ValueError("pre must have one entry per row of x")
+    if pre is not None and edge_scale and n > x.shape[0]:      # pre lives in the column space; edge_scale reads pre[r] too
+        raise ValueError("edge_scale reads pre[r] of every output row: the operator has more rows than pre has entries")
+    if post is not None and (_req(post, torch.float32, "post", 1).numel() != n):
+        raise ValueError("post must have one entry per output row")
+    if self_mode and x.shape[0] != n:
+        raise ValueError("self term needs a square operator")
+    if val is not None and _req(val, torch.float32, "val", 1).numel() != nnz:
+        raise ValueError("val must have one entry per stored column")
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=x.device)
+    elif _req(out, torch.float32, "out", 1).numel() < nnz:
+        raise ValueError("out must hold one entry per stored column")
+    if n and nnz:
+        check(_lib.lib().ocn_sddmm_csr(ptr(rowptr), ptr(col), ptr(val), n, ptr(g), ptr(x), x.shape[1], ptr(pre), ptr(post),
+                                       SPMM_MODES[mode], int(edge_scale), int(self_mode), ptr(out), stream_ptr()),
+              "ocn_sddmm_csr")
+        _mark("sddmm_csr", 2.0 * nnz * x.shape[1])
+    return out[:nnz]
+
+
+@_on_device
 def spmm_max_arg(rowptr: Tensor, col: Tensor, x: Tensor, val: Optional[Tensor] = None,
                  n_cols: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """(y, arg): y = the max aggregation of ``spmm_csr(mode="max")`` (valued: max_k val_ik * x_k), arg [n, F] int32 = the
