@@ -20,7 +20,9 @@
 // Arithmetic: an f32 product as THREE f16 MFMAs.  x = xh + xl, w = wh + wl with xh = f16(x), xl = f16(x - xh)
 // (22 significant bits; the dropped wl xl term is below 2^-22 |w x|) and w x ~ wh xl + wl xh + wh xh accumulated in
 // fp32 — half the matrix instructions of the bf16x6 split (six cross terms of three 8-bit terms) at the same fp64
-// error (tests/test_parity_gpu.py::test_heads_product_accuracy; the fp32 accumulation dominates both).  f16 has a
+// error (tests/test_parity_gpu.py::test_heads_product_accuracy, and tests/test_heads_gpu.py with class ranges, both xcn2
+// forms, a one-layer xijlin, panel scales far from their defaults and three rounds of the persistent grid: the same fp64
+// bar; the fp32 accumulation dominates both).  f16 has a
 // 5-bit exponent, so both operands are scaled by powers of two (exact): a weight panel once on the host so that
 // max |w| is in [2^13, 2^14), an activation row per layer by the exponent of its own largest element (a candidate is
 // a lane: the row maximum is a register reduction and one lane exchange).  Elements more than 2^27 below their
@@ -650,7 +652,10 @@ __global__ __launch_bounds__(OCN_BLOCK, 1) void heads_fused_kernel(const HeadsAr
 // The arithmetic is heads_fused_kernel's, operation for operation — same panels, same k order, same split, same row scales,
 // the sums over a row's features as four quarter sums combined (P0 + P1) + (P2 + P3) in both kernels (hd_quad) — so the two
 // return the same BITS (tests/test_parity_gpu.py::test_heads_small_batch_kernel_is_bit_equal); a tile none of whose
-// candidates has a branch's input takes the branch's constant from cpark, as there.
+// candidates has a branch's input takes the branch's constant from cpark, as there.  The selection itself — which tiles run a
+// branch, which rows count as zero rows — is written once per form; tests/test_heads_gpu.py holds each copy against the
+// unranged kernel on zeroed rows, bit for bit, at every class boundary (test_class_boundaries_change_no_bit) and over three
+// rounds of the persistent grid (test_persistent_rounds_against_fp64).
 template <int NT>
 struct HeadsN {
   using HD = Heads<NT>;
