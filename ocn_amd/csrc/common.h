@@ -90,6 +90,14 @@ __device__ __forceinline__ i64 wave_incl_scan(i64 v, int lane) {
   return v;
 }
 
+// lane l's 64-bit value (i64 / u64) in every lane, as a scalar: two 32-bit readlanes
+template <typename T>
+__device__ __forceinline__ T wave_readlane64(T v, int l) {
+  static_assert(sizeof(T) == 8, "wave_readlane64: a 64-bit integer");
+  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), l);
+  return (T)(((u64)hi << 32) | lo);
+}
+
 // exclusive scan of one value per thread over a 256-thread block; returns the thread's prefix and
 // the block total.  `sh` is 2*OCN_WPB i64 of LDS.
 __device__ __forceinline__ i64 block_excl_scan(i64 v, i64* sh, i64* total) {

@@ -3,9 +3,8 @@
 // an optional seed list of starting values.  Chained, it walks a source's neighbourhood one hop per launch: the candidates
 // within three hops with the local path index A² + decay·A³ (or its AA / RA weighted forms) are two launches of it.
 // See include/ocn_hip.h (ocn_frontier_count / ocn_frontier_sums_fill).
-#include <atomic>
-
 #include "common.h"
+#include "window_sweep.h"
 
 // A window column keeps a presence bit and an fp32 accumulator (33 bits) in the CU's 160 KiB without the 2 KiB left to the scan's
 // words and the runtime and the 4 KiB of the waves' claim tables below: 38 208 columns.
@@ -13,49 +12,10 @@ constexpr int FR_TAGS = 256;                                 // claim slots per 
 constexpr i64 FR_WINDOW = (i64)(160 * 1024 - 2048 - OCN_WPB * FR_TAGS * 4) * 8 / 33 / 64 * 64;
 constexpr unsigned FR_FREE = 0xffffffffu;                    // a claim slot nobody bids for
 
-// first position of the sorted row a[0..n) whose column is not below key (two_hop_window.h keeps its own copy: th_lower_bound)
-__device__ __forceinline__ i64 fr_lower_bound(const int32_t* __restrict__ a, i64 n, i64 key) {
-  i64 lo = 0, hi = n;
-  while (lo < hi) {
-    const i64 mid = lo + ((hi - lo) >> 1);
-    if ((i64)a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// the same over the nodes of a pair list (the second word of every pair)
-__device__ __forceinline__ i64 fr_pair_lower_bound(const longlong2* __restrict__ a, i64 n, i64 key) {
-  i64 lo = 0, hi = n;
-  while (lo < hi) {
-    const i64 mid = lo + ((hi - lo) >> 1);
-    if (a[mid].y < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ i64 fr_readlane(i64 v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), l);
-  return (i64)(((u64)hi << 32) | lo);
-}
-
-// one member of column k (relative to the window): the presence bit and, where sums are kept, the accumulator's next partial sum.
-// The first member of an unseeded column adds to 0.0f, so no accumulator is ever cleared: the slot is read before the bit says
-// whether it counts, and a stale value is only ever selected away (as ts_add of recommend.hip).
-template <bool VAL>
-__device__ __forceinline__ void fr_add(unsigned* bm, float* acc, unsigned k, float f) {
-  const unsigned bit = 1u << (k & 31u);
-  if (VAL) {
-    const float prev = acc[k];
-    const unsigned old = atomicOr(&bm[k >> 5], bit);
-    acc[k] = __fadd_rn((old & bit) ? prev : 0.0f, f);
-  } else {
-    atomicOr(&bm[k >> 5], bit);
-  }
-}
-
 // One body for the three passes, so they cannot disagree: FILL == false leaves the size of every query's set in count[q];
 // FILL == true writes the pairs (s, t) from edges[off[q]] on, ascending in t; VAL == true keeps an accumulator per column and
-// writes val beside the pairs.  A workgroup owns query q and sweeps the column range in windows [w0, w1):
+// writes val beside the pairs.  A workgroup owns query q and sweeps the column range in windows [w0, w1); steps 1, 3 and 4 are
+// the bodies of window_sweep.h that the 2-hop kernels of recommend.hip run, step 2 is this kernel's own:
 //   1. the bitmap is cleared;
 //   2. the window's columns are dealt to the four waves in contiguous quarters.  A wave first enters the seed entries of its
 //      quarter (bit set, accumulator = the seed value), then walks the WHOLE frontier in ascending order, 64 entries at a time, a
@@ -84,8 +44,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned fr_bm[];
   __shared__ i64 sh[2 * OCN_WPB];
   __shared__ unsigned s_tag[VAL ? OCN_WPB : 1][VAL ? FR_TAGS : 1];
-  const i64 span = window < (n_cols + 63) / 64 * 64 ? window : (n_cols + 63) / 64 * 64;   // the columns the launch sized LDS for
-  float* acc = reinterpret_cast<float*>(fr_bm + (span >> 5));                             // (VAL only: no LDS behind the bitmap otherwise)
+  float* acc = ws_accumulators(fr_bm, window, n_cols);       // (VAL only: no LDS behind the bitmap otherwise)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned* tag = s_tag[VAL ? wave : 0];
   if (VAL) {
@@ -100,21 +59,20 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
     i64 base = FILL ? off[q] : 0;
     const i64 end = FILL ? off[q + 1] : 0;
     for (i64 w0 = 0; w0 < n_cols; w0 += window) {
-      const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
-      const int words = (int)((w1 - w0 + 31) >> 5);
-      for (int t = threadIdx.x; t < words; t += OCN_BLOCK) fr_bm[t] = 0u;
+      const i64 w1 = ws_window_end(w0, window, n_cols);
+      const int words = ws_words(w0, w1);
+      ws_clear(fr_bm, words);
       __syncthreads();
-      const i64 quarter = (w1 - w0 + OCN_WPB - 1) / OCN_WPB;
-      const i64 q0 = w0 + wave * quarter;
-      const i64 q1 = (q0 + quarter) < w1 ? (q0 + quarter) : w1;            // (an empty quarter: q1 <= q0, nothing passes below)
+      i64 q0, q1;                                            // (an empty quarter: q1 <= q0, nothing passes below)
+      ws_quarter(w0, w1, wave, q0, q1);
       if (ds > 0 && q0 < q1) {                               // the seeds of the quarter: distinct columns, before any frontier add
-        const i64 lo = q0 > 0 ? fr_pair_lower_bound(nodeS + s0, ds, q0) : 0;
+        const i64 lo = q0 > 0 ? ws_pair_lower_bound(nodeS, s0, ds, q0) : 0;
         for (i64 p = lo + lane; p < ds; p += OCN_WAVE) {
           const i64 c = nodeS[s0 + p].y;
           if (c >= q1) break;                                // (sorted: so is every later node of this lane)
           if (c >= q0) {
             const unsigned k = (unsigned)(c - w0);
-            atomicOr(&fr_bm[k >> 5], 1u << (k & 31u));
+            ws_set(fr_bm, k);
             if (VAL) acc[k] = valS[s0 + p];
           }
         }
@@ -130,7 +88,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
           const i64 c = nodeF[f0 + tt].y;
           const i64 b0 = rowptrA[c];
           le = rowptrA[c + 1];
-          lb = b0 + (q0 > 0 ? fr_lower_bound(colA + b0, le - b0, q0) : 0);
+          lb = b0 + (q0 > 0 ? ws_lower_bound(colA + b0, le - b0, q0) : 0);
           if (lb < le) {
             c0 = colA[lb];
             one = lb + 1 >= le || (i64)colA[lb + 1] >= q1;
@@ -143,7 +101,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
             for (i64 p = lb; p < le; ++p) {
               const i64 c = colA[p];
               if (c >= q1) break;
-              fr_add<false>(fr_bm, acc, (unsigned)(c - w0), 0.0f);
+              ws_set(fr_bm, (unsigned)(c - w0));
             }
           continue;
         }
@@ -153,12 +111,12 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
           const int j = __ffsll((long long)live) - 1;
           if (!((ones >> j) & 1ull)) {                       // several columns in the quarter: the wave walks the entry's row
             live &= live - 1;
-            const i64 pe = fr_readlane(le, j);
+            const i64 pe = wave_readlane64(le, j);
             const float f = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(lf), j));
-            for (i64 p = fr_readlane(lb, j) + lane; p < pe; p += OCN_WAVE) {
+            for (i64 p = wave_readlane64(lb, j) + lane; p < pe; p += OCN_WAVE) {
               const i64 c = colA[p];
               if (c >= q1) break;                            // (sorted: so is every later column of this lane)
-              fr_add<true>(fr_bm, acc, (unsigned)(c - w0), f);
+              ws_add(fr_bm, acc, (unsigned)(c - w0), f);
             }
             wave_lds_sync();                                 // the next entry's reads stay behind this one's writes
             continue;
@@ -171,7 +129,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
           bool pend = (run >> lane) & 1ull;
           const unsigned k = pend ? (unsigned)(c0 - w0) : 0u;
           if ((run & (run - 1)) == 0ull) {                   // a run of one
-            if (pend) fr_add<true>(fr_bm, acc, k, lf);
+            if (pend) ws_add(fr_bm, acc, k, lf);
             wave_lds_sync();
             continue;
           }
@@ -180,7 +138,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
             if (pend) atomicMin(&tag[slot], (unsigned)lane);
             wave_lds_sync();
             const bool win = pend && tag[slot] == (unsigned)lane;
-            if (win) fr_add<true>(fr_bm, acc, k, lf);        // (winners hold distinct slots, so distinct columns)
+            if (win) ws_add(fr_bm, acc, k, lf);              // (winners hold distinct slots, so distinct columns)
             wave_lds_sync();
             if (win) { tag[slot] = FR_FREE; pend = false; }
             wave_lds_sync();
@@ -188,42 +146,13 @@ __global__ __launch_bounds__(OCN_BLOCK) void frontier_kernel(
         }
       }
       __syncthreads();
-      const i64 lo_m = w0 > 0 ? fr_lower_bound(colM + m0, dm, w0) : 0;
-      for (i64 p = lo_m + threadIdx.x; p < dm; p += OCN_BLOCK) {
-        const i64 c = colM[m0 + p];
-        if (c >= w1) break;
-        if (c >= w0) {
-          const unsigned k = (unsigned)(c - w0);
-          atomicAnd(&fr_bm[k >> 5], ~(1u << (k & 31u)));
-        }
-      }
-      if (drop_self && threadIdx.x == 0 && s >= w0 && s < w1) {
-        const unsigned k = (unsigned)(s - w0);
-        atomicAnd(&fr_bm[k >> 5], ~(1u << (k & 31u)));
-      }
+      ws_mask(fr_bm, colM, m0, dm, s, drop_self, w0, w1);
       __syncthreads();
-      const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;   // contiguous words per thread: ascending columns in thread order
-      const int t0 = (int)threadIdx.x * wpt < words ? (int)threadIdx.x * wpt : words;
-      const int t1 = (t0 + wpt) < words ? (t0 + wpt) : words;
-      i64 c = 0;
-      for (int t = t0; t < t1; ++t) c += __popc(fr_bm[t]);
+      int t0, t1;                                            // contiguous words per thread: ascending columns in thread order
+      const i64 c = th_thread_bits(fr_bm, words, t0, t1);
       i64 tot;
       const i64 ex = block_excl_scan(c, sh, &tot);
-      if (FILL) {
-        i64 at = base + ex;
-        for (int t = t0; t < t1; ++t) {
-          unsigned bits = fr_bm[t];
-          while (bits) {
-            const int b = __ffs((int)bits) - 1;
-            bits &= bits - 1;
-            if (at < end) {                                  // (at < end: offsets of another input write nothing past their own segment)
-              edges[at] = make_longlong2(s, w0 + ((i64)t << 5) + b);
-              if (VAL) val[at] = acc[(t << 5) + b];
-            }
-            ++at;
-          }
-        }
-      }
+      if (FILL) ws_emit<VAL>(fr_bm, acc, t0, t1, s, w0, base + ex, end, edges, val);
       base += tot;
       __syncthreads();                                       // the next window's clear stays behind this one's reads
     }
@@ -244,12 +173,9 @@ static int frontier_launch(int mode, const int64_t* rowptrA, const int32_t* colA
   if ((ptrS != nullptr) != (nodeS != nullptr)) return OCN_EINVAL;
   if (mode == 0 ? !count : (!off || !edges)) return OCN_EINVAL;
   if (mode == 2 && ptrS && !valS) return OCN_EINVAL;
-  if (n_cols <= 0 || n_cols >= ((int64_t)1 << 31)) return OCN_EINVAL;
-  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > FR_WINDOW) return OCN_EINVAL;
+  i64 window, span;
+  if (ws_resolve_window(n_cols, window_cols, FR_WINDOW, &window, &span)) return OCN_EINVAL;
   if (Q == 0) return 0;
-  const i64 window = window_cols ? (i64)window_cols : FR_WINDOW;
-  const i64 padded = (n_cols + 63) / 64 * 64;
-  const i64 span = window < padded ? window : padded;                         // a small graph keeps several workgroups per CU
   const size_t lds = (size_t)(span / 8 + (mode == 2 ? span * 4 : 0));         // the bitmap, then the accumulators
   // at most 16 workgroups per CU's worth of queries in flight; a longer list is taken grid-stride
   const dim3 grid((unsigned)grid_for(Q, 256 * 16));
@@ -258,19 +184,10 @@ static int frontier_launch(int mode, const int64_t* rowptrA, const int32_t* colA
       (const i64*)ptrF, (const longlong2*)nodeF, valF, (const i64*)ptrS, (const longlong2*)nodeS, valS, count, (const i64*)off, \
       (longlong2*)edges, val
   if (mode == 2) {
-    // The LDS limit of the valued kernel is raised ONCE per device, to what the default window takes, never per launch to that
-    // launch's size: two host threads that launch graphs of different widths would race between the set and the launch.  (The
-    // bitmap alone, 4 776 bytes at the most, stays below the limit every kernel has.)
+    // only the valued kernel needs its limit raised: the bitmap alone, 4 776 bytes at the most, stays below the limit every kernel has
     static std::atomic<unsigned long long> lds_raised{0ull};
-    int dev = 0;
-    hipError_t err = hipGetDevice(&dev);
-    if (err != hipSuccess) return (int)err;
-    if (dev >= 64 || !((lds_raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
-      err = hipFuncSetAttribute((const void*)frontier_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(FR_WINDOW / 8 + FR_WINDOW * 4));
-      if (err != hipSuccess) return (int)err;
-      if (dev < 64) lds_raised.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    const size_t lds_max = (size_t)(FR_WINDOW / 8 + FR_WINDOW * 4);
+    if (const int rc = ws_raise_lds_once((const void*)frontier_kernel<true, true>, lds_max, lds_raised)) return rc;
     hipLaunchKernelGGL((frontier_kernel<true, true>), grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, FR_ARGS);
   } else if (mode == 1) {
     hipLaunchKernelGGL((frontier_kernel<true, false>), grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, FR_ARGS);

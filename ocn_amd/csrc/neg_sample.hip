@@ -7,10 +7,8 @@
 // See include/ocn_hip.h (ocn_philox4x32, ocn_complement_count, ocn_sample_complement_rows, ocn_sample_complement_pairs).
 // Hard negatives are drawn the same way from the candidate set that is served: the r-th smallest member of a source's 2-hop row
 // difference, selected in the LDS bitmap the 2-hop expansion builds, without ever listing the set (ocn_sample_two_hop).
-#include <atomic>
-
 #include "common.h"
-#include "two_hop_window.h"
+#include "window_sweep.h"
 
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants)
@@ -230,8 +228,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void sample_two_hop_kernel(
     i64 cq = 0;
     if (!one_window) {                                       // the counting sweep: two_hop_diff_kernel<false>
       for (i64 w0 = 0; w0 < n_cols; w0 += window) {
-        const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
-        const int words = (int)((w1 - w0 + 31) >> 5);
+        const i64 w1 = ws_window_end(w0, window, n_cols);
+        const int words = ws_words(w0, w1);
         th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);
         int t0, t1;
         i64 tot;
@@ -242,8 +240,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void sample_two_hop_kernel(
     if (one_window || (cq > 0 && slot1 > slot0)) {           // the selecting sweep (the same in every thread)
       i64 base = 0;
       for (i64 w0 = 0; w0 < n_cols; w0 += window) {
-        const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
-        const int words = (int)((w1 - w0 + 31) >> 5);
+        const i64 w1 = ws_window_end(w0, window, n_cols);
+        const int words = ws_words(w0, w1);
         th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);
         int t0, t1;
         i64 tot;
@@ -334,25 +332,14 @@ int ocn_sample_two_hop(const int64_t* rowptrA, const int32_t* colA, const int64_
                        const int64_t* sid, int64_t q0, uint64_t seed, int32_t* count, int64_t* out, void* stream) {
   if (!rowptrA || !colA || !rowptrM || !colM || !rows || !sptr || !out || !ns_cols_ok(n_cols)) return OCN_EINVAL;
   if (Q < 0 || q0 < 0 || q0 > INT64_MAX - Q) return OCN_EINVAL;             // (the query counter q0 + q stays a non-negative int64)
-  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > S2_WINDOW) return OCN_EINVAL;
+  i64 window, span;
+  if (ws_resolve_window(n_cols, window_cols, S2_WINDOW, &window, &span)) return OCN_EINVAL;
   if (Q == 0) return 0;
-  const i64 window = window_cols ? (i64)window_cols : S2_WINDOW;
-  const i64 padded = (n_cols + 63) / 64 * 64;
-  const size_t lds = (size_t)((window < padded ? window : padded) / 8);       // a small graph keeps several workgroups per CU
-  // The LDS limit of the kernel is raised ONCE per device, to what the default window takes — never per launch to that launch's
-  // size: two host threads that launch graphs of different widths would race between the set and the launch.
   static std::atomic<unsigned long long> lds_raised{0ull};
-  int dev = 0;
-  hipError_t err = hipGetDevice(&dev);
-  if (err != hipSuccess) return (int)err;
-  if (dev >= 64 || !((lds_raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    err = hipFuncSetAttribute((const void*)sample_two_hop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S2_WINDOW / 8));
-    if (err != hipSuccess) return (int)err;
-    if (dev < 64) lds_raised.fetch_or(1ull << dev, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(sample_two_hop_kernel, dim3((unsigned)grid_for(Q, 256 * 16)), dim3(OCN_BLOCK), lds, (hipStream_t)stream,
-                     (const i64*)rowptrA, colA, (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self,
-                     window, (const i64*)sptr, (const i64*)sid, (i64)q0, (u64)seed, count, (i64*)out);
+  if (const int rc = ws_raise_lds_once((const void*)sample_two_hop_kernel, (size_t)(S2_WINDOW / 8), lds_raised)) return rc;
+  hipLaunchKernelGGL(sample_two_hop_kernel, dim3((unsigned)grid_for(Q, 256 * 16)), dim3(OCN_BLOCK), (size_t)(span / 8),
+                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q,
+                     (int)drop_self, window, (const i64*)sptr, (const i64*)sid, (i64)q0, (u64)seed, count, (i64*)out);
   return launch_status();
 }
 

@@ -7,10 +7,8 @@
 // Where A² is not stored (more columns than the A*A pattern takes, or simply too large) the same candidate set is expanded
 // from A itself: a workgroup owns a query and keeps the union of its neighbours' rows as a bitmap in LDS, one window of the
 // column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
-#include <atomic>
-
 #include "common.h"
-#include "two_hop_window.h"
+#include "window_sweep.h"
 
 // ---------------------------------------------------------------------------------------------
 // row difference P[s,:] \ M[s,:]
@@ -87,8 +85,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void row_diff_kernel(
 constexpr i64 TH_WINDOW = (i64)(160 * 1024 - 2048) * 8;
 
 // One body for both passes, so they cannot disagree.  A workgroup owns query q; the column range is swept in windows
-// [w0, w1) of `window` columns, the window's part of the set as a bitmap in LDS (steps 1 - 3: th_window_bitmap of
-// two_hop_window.h, which the 2-hop sampler of neg_sample.hip calls too):
+// [w0, w1) of `window` columns, the window's part of the set as a bitmap in LDS (window_sweep.h: one body per step, shared with
+// the valued sibling below, the frontier expansion and the 2-hop sampler; steps 1 - 3 are its th_window_bitmap):
 //   1. the bitmap is cleared;
 //   2. a wave takes a neighbour m of s, finds where row m enters the window (binary search, skipped for the first window)
 //      and sets a bit per column below w1 — LDS atomicOr: the lanes of a wave, and the waves, do meet in one word;
@@ -112,25 +110,14 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
     i64 base = FILL ? off[q] : 0;
     const i64 end = FILL ? off[q + 1] : 0;
     for (i64 w0 = 0; w0 < n_cols; w0 += window) {
-      const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
-      const int words = (int)((w1 - w0 + 31) >> 5);
+      const i64 w1 = ws_window_end(w0, window, n_cols);
+      const int words = ws_words(w0, w1);
       th_window_bitmap(th_bm, rowptrA, colA, a0, da, colM, m0, dm, s, drop_self, w0, w1, words);   // steps 1 - 3
       int t0, t1;                                            // contiguous words per thread: ascending columns in thread order
       const i64 c = th_thread_bits(th_bm, words, t0, t1);
       i64 tot;
       const i64 ex = block_excl_scan(c, sh, &tot);
-      if (FILL) {
-        i64 at = base + ex;
-        for (int w = t0; w < t1; ++w) {
-          unsigned bits = th_bm[w];
-          while (bits) {
-            const int b = __ffs((int)bits) - 1;
-            bits &= bits - 1;
-            if (at < end) edges[at] = make_longlong2(s, w0 + ((i64)w << 5) + b);   // (at < end: as in the row difference)
-            ++at;
-          }
-        }
-      }
+      if (FILL) ws_emit<false>(th_bm, nullptr, t0, t1, s, w0, base + ex, end, edges, nullptr);
       base += tot;
       __syncthreads();                                       // the next window's clear stays behind this one's reads
     }
@@ -144,29 +131,12 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_diff_kernel(
 // A window column keeps a presence bit and an fp32 accumulator (33 bits) in the LDS the bitmap kernel keeps: 39 168 columns.
 constexpr i64 TS_WINDOW = (i64)(160 * 1024 - 2048) * 8 / 33 / 64 * 64;
 
-// one member of column k (relative to the window): the presence bit, and the accumulator's next partial sum — the first member
-// of a column adds to 0.0f, so no accumulator is ever cleared
-__device__ __forceinline__ void ts_add(unsigned* bm, float* acc, unsigned k, float wm) {
-  const unsigned bit = 1u << (k & 31u);
-  // Read whatever the bit will say, so that a member costs one LDS round trip, not two.  For a column's first member the slot
-  // holds whatever the last window or query left there: that value is only ever SELECTED AWAY below, it never enters the add.
-  // (Reading after the atomicOr instead would be as correct and a round trip slower.)
-  const float prev = acc[k];
-  const unsigned old = atomicOr(&bm[k >> 5], bit);
-  acc[k] = __fadd_rn((old & bit) ? prev : 0.0f, wm);
-}
-
-__device__ __forceinline__ i64 th_readlane(i64 v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), l);
-  return (i64)(((u64)hi << 32) | lo);
-}
-
 // The valued sibling of two_hop_diff_kernel<true>: the same windows, the same bitmap, the same steps 3 and 4 — so the pairs,
 // their order and the `off` protocol are those of the fill pass — and beside every pair its sum.  Step 2 differs, because the
 // sum of a column must add its members in ascending m, whatever the launch:
 //   2. the window's columns are dealt to the four waves in contiguous quarters, and EVERY wave walks ALL neighbours m of s in
 //      ascending order, taking of row m the part inside its own quarter, its lanes on consecutive entries.  (The rows of 64
-//      neighbours are looked up at once, a lane each — here th_lower_bound runs per lane — and the wave then visits, in lane
+//      neighbours are looked up at once, a lane each — here ws_lower_bound runs per lane — and the wave then visits, in lane
 //      order, those that have a column in the quarter.)  An accumulator is therefore only ever touched by one wave, the lanes of one
 //      instruction touch distinct columns, and LDS executes a wave's instructions in order: a plain read-add-write per member
 //      is the ascending-m sum, with no accumulator atomics and no barrier between neighbours.  The presence bit is set by an
@@ -180,8 +150,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_sums_kernel(
     const i64* __restrict__ off, longlong2* __restrict__ edges, float* __restrict__ val) {
   extern __shared__ __attribute__((aligned(16))) unsigned th_bm[];
   __shared__ i64 sh[2 * OCN_WPB];
-  const i64 span = window < (n_cols + 63) / 64 * 64 ? window : (n_cols + 63) / 64 * 64;   // the columns the launch sized LDS for
-  float* acc = reinterpret_cast<float*>(th_bm + (span >> 5));
+  float* acc = ws_accumulators(th_bm, window, n_cols);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (i64 q = blockIdx.x; q < Q; q += gridDim.x) {
     const i64 s = rows[q];
@@ -190,13 +159,12 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_sums_kernel(
     i64 base = off[q];
     const i64 end = off[q + 1];
     for (i64 w0 = 0; w0 < n_cols; w0 += window) {
-      const i64 w1 = (w0 + window) < n_cols ? (w0 + window) : n_cols;
-      const int words = (int)((w1 - w0 + 31) >> 5);
-      for (int t = threadIdx.x; t < words; t += OCN_BLOCK) th_bm[t] = 0u;
+      const i64 w1 = ws_window_end(w0, window, n_cols);
+      const int words = ws_words(w0, w1);
+      ws_clear(th_bm, words);
       __syncthreads();
-      const i64 quarter = (w1 - w0 + OCN_WPB - 1) / OCN_WPB;
-      const i64 q0 = w0 + wave * quarter;
-      const i64 q1 = (q0 + quarter) < w1 ? (q0 + quarter) : w1;            // (an empty quarter: q1 <= q0, nothing passes below)
+      i64 q0, q1;                                            // (an empty quarter: q1 <= q0, nothing passes below)
+      ws_quarter(w0, w1, wave, q0, q1);
       for (i64 t0 = 0; t0 < da; t0 += OCN_WAVE) {
         // 64 neighbours at a time, one per lane: where its row enters the quarter (a search per lane, 64 side by side), where
         // it ends, its weight, and whether it has a column in the quarter at all — most rows miss most quarters of a wide graph
@@ -207,58 +175,31 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_sums_kernel(
           const i64 m = colA[a0 + tt];
           const i64 b0 = rowptrA[m];
           le = rowptrA[m + 1];
-          lb = b0 + (q0 > 0 ? th_lower_bound(colA + b0, le - b0, q0) : 0);
+          lb = b0 + (q0 > 0 ? ws_lower_bound(colA + b0, le - b0, q0) : 0);
           lw = w ? w[m * 4 + wcol] : 1.0f;
         }
         u64 live = __ballot(lb < le && (i64)colA[lb < le ? lb : a0] < q1);   // (a0: in bounds, da > 0 here; the value is not used)
         while (live) {                                       // ascending lanes: ascending m (the same trips in every lane)
           const int j = __ffsll((long long)live) - 1;
           live &= live - 1;
-          const i64 pe = th_readlane(le, j);
+          const i64 pe = wave_readlane64(le, j);
           const float wm = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(lw), j));
-          for (i64 p = th_readlane(lb, j) + lane; p < pe; p += OCN_WAVE) {
+          for (i64 p = wave_readlane64(lb, j) + lane; p < pe; p += OCN_WAVE) {
             const i64 c = colA[p];
             if (c >= q1) break;                              // (sorted: so is every later column of this lane)
-            ts_add(th_bm, acc, (unsigned)(c - w0), wm);
+            ws_add(th_bm, acc, (unsigned)(c - w0), wm);
           }
           wave_lds_sync();                                   // the next neighbour's reads stay behind this one's writes
         }
       }
       __syncthreads();
-      const i64 lo_m = w0 > 0 ? th_lower_bound(colM + m0, dm, w0) : 0;
-      for (i64 p = lo_m + threadIdx.x; p < dm; p += OCN_BLOCK) {
-        const i64 c = colM[m0 + p];
-        if (c >= w1) break;
-        if (c >= w0) {
-          const unsigned k = (unsigned)(c - w0);
-          atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
-        }
-      }
-      if (drop_self && threadIdx.x == 0 && s >= w0 && s < w1) {
-        const unsigned k = (unsigned)(s - w0);
-        atomicAnd(&th_bm[k >> 5], ~(1u << (k & 31u)));
-      }
+      ws_mask(th_bm, colM, m0, dm, s, drop_self, w0, w1);
       __syncthreads();
-      const int wpt = (words + OCN_BLOCK - 1) / OCN_BLOCK;   // contiguous words per thread: ascending columns in thread order
-      const int t0 = (int)threadIdx.x * wpt < words ? (int)threadIdx.x * wpt : words;
-      const int t1 = (t0 + wpt) < words ? (t0 + wpt) : words;
-      i64 c = 0;
-      for (int t = t0; t < t1; ++t) c += __popc(th_bm[t]);
+      int t0, t1;                                            // contiguous words per thread: ascending columns in thread order
+      const i64 c = th_thread_bits(th_bm, words, t0, t1);
       i64 tot;
       const i64 ex = block_excl_scan(c, sh, &tot);
-      i64 at = base + ex;
-      for (int t = t0; t < t1; ++t) {
-        unsigned bits = th_bm[t];
-        while (bits) {
-          const int b = __ffs((int)bits) - 1;
-          bits &= bits - 1;
-          if (at < end) {                                    // (at < end: as in the row difference)
-            edges[at] = make_longlong2(s, w0 + ((i64)t << 5) + b);
-            val[at] = acc[(t << 5) + b];
-          }
-          ++at;
-        }
-      }
+      ws_emit<true>(th_bm, acc, t0, t1, s, w0, base + ex, end, edges, val);
       base += tot;
       __syncthreads();                                       // the next window's clear stays behind this one's reads
     }
@@ -281,11 +222,6 @@ __device__ __forceinline__ u64 topk_key(float x, unsigned rel) {
   unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
   if (x != x) u = 0u;
   return ((u64)u << 32) | (u64)(0xffffffffu - rel);
-}
-
-__device__ __forceinline__ u64 topk_readlane(u64 v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
-  return ((u64)hi << 32) | lo;
 }
 
 __device__ __forceinline__ u64 topk_shfl_up1(u64 v) {
@@ -326,16 +262,16 @@ __global__ __launch_bounds__(OCN_BLOCK) void segment_topk_kernel(
         while (m) {                                          // (the same trip count in every lane)
           const int sl = __ffsll((long long)m) - 1;
           m &= m - 1;
-          const u64 nk = topk_readlane(key, sl);
+          const u64 nk = wave_readlane64(key, sl);
           if (nk <= thr) continue;
           u64 up[NS];
 #pragma unroll
           for (int r = 0; r < NS; ++r) up[r] = topk_shfl_up1(v[r]);
-          if (NS == 2) { const u64 carry = topk_readlane(v[0], 63); if (lane == 0) up[NS - 1] = carry; }
+          if (NS == 2) { const u64 carry = wave_readlane64(v[0], 63); if (lane == 0) up[NS - 1] = carry; }
           if (lane == 0) up[0] = ~0ull;
 #pragma unroll
           for (int r = 0; r < NS; ++r) v[r] = v[r] > nk ? v[r] : (up[r] > nk ? nk : up[r]);
-          thr = topk_readlane(v[NS - 1], kl);
+          thr = wave_readlane64(v[NS - 1], kl);
         }
       }
     }
@@ -374,11 +310,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void segment_rank_kernel(
     }
     const i64 b = ptr[q], n = ptr[q + 1] - b;
     const i64 node = tnode[j];
-    i64 lo = 0, hi = n;                                      // the first entry whose id is not below node
-    while (lo < hi) {
-      const i64 mid = lo + ((hi - lo) >> 1);
-      if (edges[b + mid].y < node) lo = mid + 1; else hi = mid;
-    }
+    const i64 lo = ws_pair_lower_bound(edges, b, n, node);  // the first entry whose id is not below node
     if (lo >= n || edges[b + lo].y != node) {                // any int64 that is no id of the segment, an empty segment
       if (lane == 0) { rank[j] = 0; pos[j] = -1; }
       continue;
@@ -404,6 +336,25 @@ __global__ __launch_bounds__(OCN_BLOCK) void segment_rank_kernel(
 }
 
 static inline unsigned wave_grid(i64 items) { return (unsigned)grid_for((items + OCN_WPB - 1) / OCN_WPB, 256 * 8); }
+
+// both passes of the 2-hop row difference (a template: outside the C linkage block).  Each instance of the kernel has its own
+// LDS limit, raised once; the LDS a launch asks for is that launch's span / 8.
+template <bool FILL>
+static int two_hop_launch(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
+                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, int32_t* count,
+                          const int64_t* off, int64_t* edges, void* stream) {
+  if (Q < 0 || !rowptrA || !colA || !rowptrM || !colM || !rows) return OCN_EINVAL;
+  if (FILL ? (!off || !edges) : !count) return OCN_EINVAL;
+  i64 window, span;
+  if (ws_resolve_window(n_cols, window_cols, TH_WINDOW, &window, &span)) return OCN_EINVAL;
+  if (Q == 0) return 0;
+  static std::atomic<unsigned long long> lds_raised{0ull};
+  if (const int rc = ws_raise_lds_once((const void*)two_hop_diff_kernel<FILL>, (size_t)(TH_WINDOW / 8), lds_raised)) return rc;
+  hipLaunchKernelGGL(two_hop_diff_kernel<FILL>, dim3((unsigned)grid_for(Q)), dim3(OCN_BLOCK), (size_t)(span / 8),
+                     (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows,
+                     (i64)Q, (int)drop_self, window, count, (const i64*)off, (longlong2*)edges);
+  return launch_status();
+}
 
 extern "C" {
 
@@ -439,47 +390,18 @@ int ocn_row_diff_fill(const int64_t* rowptrP, const int32_t* colP, const int64_t
 
 int64_t ocn_two_hop_window_cols(void) { return TH_WINDOW; }
 
-static int two_hop_launch(bool fill, const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
-                          int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, int32_t* count,
-                          const int64_t* off, int64_t* edges, void* stream) {
-  if (Q < 0 || !rowptrA || !colA || !rowptrM || !colM || !rows) return OCN_EINVAL;
-  if (fill ? (!off || !edges) : !count) return OCN_EINVAL;
-  if (n_cols <= 0 || n_cols >= ((int64_t)1 << 31)) return OCN_EINVAL;
-  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > TH_WINDOW) return OCN_EINVAL;
-  if (Q == 0) return 0;
-  const i64 window = window_cols ? (i64)window_cols : TH_WINDOW;
-  const i64 padded = (n_cols + 63) / 64 * 64;
-  const size_t lds = (size_t)((window < padded ? window : padded) / 8);       // a small graph keeps several workgroups per CU
-  const dim3 grid((unsigned)grid_for(Q));
-  hipError_t err;
-  if (fill) {
-    err = hipFuncSetAttribute((const void*)two_hop_diff_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return (int)err;
-    hipLaunchKernelGGL(two_hop_diff_kernel<true>, grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, (const i64*)rowptrA, colA,
-                       (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self, window,
-                       (int32_t*)nullptr, (const i64*)off, (longlong2*)edges);
-  } else {
-    err = hipFuncSetAttribute((const void*)two_hop_diff_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return (int)err;
-    hipLaunchKernelGGL(two_hop_diff_kernel<false>, grid, dim3(OCN_BLOCK), lds, (hipStream_t)stream, (const i64*)rowptrA, colA,
-                       (const i64*)rowptrM, colM, (i64)n_cols, (const i64*)rows, (i64)Q, (int)drop_self, window, count,
-                       (const i64*)nullptr, (longlong2*)nullptr);
-  }
-  return launch_status();
-}
-
 int ocn_two_hop_diff_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
                            int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols,
                            int32_t* count, void* stream) {
-  return two_hop_launch(false, rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, count, nullptr, nullptr,
-                        stream);
+  return two_hop_launch<false>(rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, count, nullptr, nullptr,
+                               stream);
 }
 
 int ocn_two_hop_diff_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM,
                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols,
                           const int64_t* off, int64_t* edges, void* stream) {
-  return two_hop_launch(true, rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, nullptr, off, edges,
-                        stream);
+  return two_hop_launch<true>(rowptrA, colA, rowptrM, colM, n_cols, rows, Q, drop_self, window_cols, nullptr, off, edges,
+                              stream);
 }
 
 int64_t ocn_two_hop_sums_window_cols(void) { return TS_WINDOW; }
@@ -488,27 +410,14 @@ int ocn_two_hop_sums_fill(const int64_t* rowptrA, const int32_t* colA, const int
                           int64_t n_cols, const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols, const float* w,
                           int32_t wcol, const int64_t* off, int64_t* edges, float* val, void* stream) {
   if (Q < 0 || !rowptrA || !colA || !rowptrM || !colM || !rows || !off || !edges || !val) return OCN_EINVAL;
-  if (n_cols <= 0 || n_cols >= ((int64_t)1 << 31)) return OCN_EINVAL;
-  if (window_cols < 0 || window_cols % 64 != 0 || window_cols > TS_WINDOW) return OCN_EINVAL;
+  i64 window, span;
+  if (ws_resolve_window(n_cols, window_cols, TS_WINDOW, &window, &span)) return OCN_EINVAL;
   if (w && (wcol < 0 || wcol > 3)) return OCN_EINVAL;
   if (Q == 0) return 0;
-  const i64 window = window_cols ? (i64)window_cols : TS_WINDOW;
-  const i64 padded = (n_cols + 63) / 64 * 64;
-  const i64 span = window < padded ? window : padded;                         // a small graph keeps several workgroups per CU
   const size_t lds = (size_t)(span / 8 + span * 4);                           // the bitmap, then the accumulators
-  // The LDS limit of the kernel is raised ONCE per device, to what the default window takes — never per launch to that launch's
-  // size: two host threads that launch graphs of different widths would race between the set and the launch.  (Setting the
-  // same value twice, by two first callers, is harmless.)
   static std::atomic<unsigned long long> lds_raised{0ull};
-  int dev = 0;
-  hipError_t err = hipGetDevice(&dev);
-  if (err != hipSuccess) return (int)err;
-  if (dev >= 64 || !((lds_raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    err = hipFuncSetAttribute((const void*)two_hop_sums_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(TS_WINDOW / 8 + TS_WINDOW * 4));
-    if (err != hipSuccess) return (int)err;
-    if (dev < 64) lds_raised.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  const size_t lds_max = (size_t)(TS_WINDOW / 8 + TS_WINDOW * 4);
+  if (const int rc = ws_raise_lds_once((const void*)two_hop_sums_kernel, lds_max, lds_raised)) return rc;
   // at most 16 workgroups per CU's worth of queries in flight: a request of a few thousand sources is dealt a workgroup per
   // source by the hardware, a longer list is taken grid-stride
   hipLaunchKernelGGL(two_hop_sums_kernel, dim3((unsigned)grid_for(Q, 256 * 16)), dim3(OCN_BLOCK), lds, (hipStream_t)stream,

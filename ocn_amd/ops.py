@@ -128,6 +128,12 @@ def _scan_total(ptrs: Tensor, n: int, total: Optional[int], name: str, what: str
     return _total(ptrs[-1]) if total is None else int(total)
 
 
+def _fill_pairs(off: Tensor, Q: int, total: Optional[int], device) -> Tuple[int, Tensor]:
+    """The total of the ``off`` scan of ``Q`` queries and the int64 [T, 2] pair list a fill pass writes."""
+    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
+    return T, torch.empty(T, 2, dtype=torch.int64, device=device)
+
+
 def status_message(bits: int) -> str:
     return "; ".join(m for b, m in ((ST_CAP, "CN flag buffer capacity exceeded"),
                                     (ST_SCAN, "a scan workspace was not zero on entry: the batch's offsets are void")) if bits & b)
@@ -834,8 +840,7 @@ def row_diff_fill(rowptrP: Tensor, colP: Tensor, rowptrM: Tensor, colM: Tensor, 
     ocn_row_diff_fill).  ``off``: ``scan_i32(row_diff_count(...))`` of the same operands; ``total`` = ``off[-1]`` where the
     caller has read it already (else it is read here: one host sync for the output size)."""
     Q = _row_diff_args(rowptrP, colP, rowptrM, colM, rows)
-    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
-    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    T, edges = _fill_pairs(off, Q, total, rows.device)
     if Q and T:
         check(_lib.lib().ocn_row_diff_fill(ptr(rowptrP), ptr(colP), ptr(rowptrM), ptr(colM), ptr(rows), Q, int(bool(drop_self)),
                                            ptr(off), ptr(edges), stream_ptr()), "ocn_row_diff_fill")
@@ -884,8 +889,7 @@ def two_hop_diff_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tens
     """The pairs (s, c) of every query's set, ascending in c, row-major in int64 [T, 2] from ``off[q]`` on (ocn_hip.h:
     ocn_two_hop_diff_fill).  ``off``, ``total``: as for ``row_diff_fill``."""
     Q, n = _two_hop_args(rowptrA, colA, rowptrM, colM, rows, window_cols)
-    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
-    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    T, edges = _fill_pairs(off, Q, total, rows.device)
     if Q and T:
         check(_lib.lib().ocn_two_hop_diff_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
                                                int(bool(drop_self)), int(window_cols), ptr(off), ptr(edges), stream_ptr()),
@@ -917,8 +921,7 @@ def two_hop_sums_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tens
         wcol = int(wcol)
         if not 0 <= wcol <= 3:
             raise ValueError(f"wcol must be a column 0..3 of the node table, got {wcol}")
-    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
-    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    T, edges = _fill_pairs(off, Q, total, rows.device)
     val = torch.empty(T, dtype=torch.float32, device=rows.device)
     if Q and T:
         check(_lib.lib().ocn_two_hop_sums_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,
@@ -1006,8 +1009,7 @@ def frontier_sums_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Ten
                                               valF if values else None, ptrS, nodeS, valS if values else None)
     if values and ptrS is not None and valS is None:
         raise ValueError("valS: seeds need their values where val is written")
-    T = _scan_total(off, Q, total, "off", "off: one entry per query and the total")
-    edges = torch.empty(T, 2, dtype=torch.int64, device=rows.device)
+    T, edges = _fill_pairs(off, Q, total, rows.device)
     val = torch.empty(T, dtype=torch.float32, device=rows.device) if values else None
     if Q and T:
         check(_lib.lib().ocn_frontier_sums_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q,

@@ -247,6 +247,36 @@ def test_graph_wider_than_the_default_window(hiplib):
         ops.spgemm_pattern(adj._rowptr, adj._col, adj._rowptr, adj._col, n)
 
 
+# ---- 4b. one LDS limit for launches of any width, in any order ----------------------------------------------------------
+def test_narrow_wide_narrow_launches_in_one_process(small):
+    """The dynamic LDS limit of the kernel is raised once per device, not per launch: a 300-column launch, then one whose bitmap
+    (600 000 columns: 75 000 bytes) is larger than the 65 536 bytes a kernel may ask for without the raised limit, then the
+    300-column one again.  The wide graph: 2 000 random links among 1 500 nodes drawn from the whole column range (so that the
+    2-hop sets are not empty); its sources are seven of those nodes and one isolated node."""
+    c = small
+    n = 600_000
+    assert n // 8 > 65536
+    g = torch.Generator().manual_seed(21)
+    nodes = torch.randperm(n, generator=g)[:1500]
+    ends = nodes[torch.randint(0, nodes.numel(), (2000, 2), generator=g)]
+    a_rows = rows_of(n, [(a, b) for a, b in ends.tolist() if a != b], sparse=True)
+    linked = sorted(a_rows)
+    isolated = next(v for v in range(n - 1, -1, -1) if v not in a_rows)
+    sources = linked[::len(linked) // 6][:6] + [linked[-1], isolated]
+    assert len(sources) == 8
+    wide = csr_of(a_rows, n)
+    rptr, redges = ref_two_hop(a_rows, a_rows, sources)
+    sizes = (rptr[1:] - rptr[:-1]).tolist()
+    assert sum(1 for x in sizes if x > 0) >= 4 and sizes[-1] == 0 and int(redges[:, 1].max()) > 65536 * 8
+    first = two_hop(c.adj, c.adj, c.sources)
+    ptr, edges = two_hop(wide, wide, sources)
+    assert torch.equal(ptr, rptr) and torch.equal(edges, redges)
+    again = two_hop(c.adj, c.adj, c.sources)
+    for ptr, edges in (first, again):
+        assert torch.equal(ptr, c.ptr) and torch.equal(edges, c.edges)
+    assert torch.equal(first[0], again[0]) and torch.equal(first[1], again[1])
+
+
 # ---- 5. known differs from adj ------------------------------------------------------------------------------------------
 def test_known_superset_long_row_and_an_empty_segment_between_full_ones(hiplib):
     from ocn_amd import ops
