@@ -54,7 +54,8 @@ extern "C" {
  *    local path index); ocn_segment_rank (the place of held-out links among a source's candidates, in the order of
  *    ocn_segment_topk: ranking metrics); ocn_sample_two_hop_window_cols, ocn_sample_two_hop (hard negatives: draws from the
  *    2-hop candidate set that is served, selected in the expansion's LDS bitmap without listing the set); ocn_sddmm_csr (the sampled
- *    dense-dense product on the pattern of an encoder operator: the gradient of a layer with respect to its messages). */
+ *    dense-dense product on the pattern of an encoder operator: the gradient of a layer with respect to its messages);
+ *    ocn_cn_gather_pair_min_batch (the H = 256 pooling takes two slots per wave at large batches; same bits). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -624,6 +625,14 @@ int ocn_sample_two_hop(const int64_t* rowptrA, const int32_t* colA, const int64_
  * eighth — the sources in flight on an XCD then stay within a narrow range of the source order (what their rows' L2
  * residency depends on) while every segment still starts with its longest jobs; 0 = whole eighths. */
 int ocn_gather_schedule(const int32_t* gcost, int64_t n_groups, int64_t segment, int32_t* perm, void* stream);
+/* H = 256 batches of at least `min_rows` candidates, fed by slot records on the pattern route without `rowsum`, are pooled with
+ * TWO neighbouring slots of one group per wave (cn_pool.hip: cn_gather_pair_kernel): both slots' records, chunks of N(src), flag
+ * bytes, column weights, embedding rows and endpoint rows are in flight together, and a pair of one source loads each row
+ * once.  A workgroup is then two groups: `perm` is followed where an XCD's eighth holds an even number of groups (an odd one
+ * keeps the one-slot form); without `perm` the pairs are consecutive groups.  Every output is bit for bit what the one-slot
+ * form writes (tests/test_pool_pairs_gpu.py).  Sets the bound (process-wide; default 32768) and returns the previous one; a
+ * negative argument only queries. */
+int64_t ocn_cn_gather_pair_min_batch(int64_t min_rows);
 
 /* The 3-hop predictor cn6 (model.py:2535-2951), pattern route.  Two intersection passes over the same
  * candidate batch — (A, A, A²) into flagsA / histA and (A, A³) into flagsB / histB (bit 0 = cn3 entry,

@@ -12,6 +12,16 @@
 // ascending position (= column) order.  LPE lanes cooperate; each lane owns NV float4 of the
 // H = LPE*NV*4 features; four embedding rows are in flight per group.
 constexpr int GATHER_UNR = 4;
+
+// The accumulate step of one embedding row: the {xcn1, xcn2} pairs of a lane's four features take w * x, component by component
+// in the order x, y, z, w (pool_range and the pair form share it).
+__device__ __forceinline__ void axpy_pair4(f32x2 (&a)[4], const f32x2 w, const float x0, const float x1, const float x2,
+                                           const float x3) {
+  axpy_pair(a[0], w, x0);
+  axpy_pair(a[1], w, x1);
+  axpy_pair(a[2], w, x2);
+  axpy_pair(a[3], w, x3);
+}
 // (eight for the one-wave-per-candidate layout of H >= 256 — one candidate's gathers are all a wave has in flight:
 // 0.214 -> 0.206 ms at the collab shape; four where several candidates share a wave)
 template <int LPE, int NV, int UNR = (LPE >= 64 ? 2 * GATHER_UNR : GATHER_UNR)>
@@ -82,12 +92,7 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
           if (bsel[u] >= 0) {
             const f32x2 w = {wwa[u], wwb[u]};
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-              axpy_pair(acc[v][0], w, x[u][v].x);
-              axpy_pair(acc[v][1], w, x[u][v].y);
-              axpy_pair(acc[v][2], w, x[u][v].z);
-              axpy_pair(acc[v][3], w, x[u][v].w);
-            }
+            for (int v = 0; v < NV; ++v) axpy_pair4(acc[v], w, x[u][v].x, x[u][v].y, x[u][v].z, x[u][v].w);
           }
         }
       }
@@ -98,6 +103,16 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
     acc1[v] = make_float4(acc[v][0].x, acc[v][1].x, acc[v][2].x, acc[v][3].x);
     acc2[v] = make_float4(acc[v][0].y, acc[v][1].y, acc[v][2].y, acc[v][3].y);
   }
+}
+
+// One float4 of a candidate's three output rows: the pooled pair (where the heads read them) and x_i * x_j from the endpoint
+// rows' quads a, b.
+__device__ __forceinline__ void pool_emit(float4* __restrict__ o1, float4* __restrict__ o2, float4* __restrict__ o3,
+                                          const float4& acc1, const float4& acc2, const float4& a, const float4& b, bool st1,
+                                          bool st2) {
+  if (st1) *o1 = acc1;
+  if (st2) *o2 = acc2;
+  *o3 = make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
 }
 
 template <int LPE, int NV>
@@ -113,10 +128,7 @@ __device__ __forceinline__ void pool_store(i64 e, i64 i, i64 j, int gl, const fl
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const float4 a = hi[v * LPE], b = hj[v * LPE];
-    if (st1) o1[v * LPE] = acc1[v];
-    if (st2) o2[v * LPE] = acc2[v];
-    o3[v * LPE] = make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z),
-                              __fmul_rn(a.w, b.w));
+    pool_emit(o1 + v * LPE, o2 + v * LPE, o3 + v * LPE, acc1[v], acc2[v], a, b, st1, st2);
   }
 }
 
@@ -191,6 +203,261 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
   }
   pool_store<LPE, NV>(out_row ? out_row[e] : e, i, j, gl, h4, rowq, acc1, acc2, xcn1, xcn2, xij,
                       !out_row || has1, !out_row || has1 || has2);
+}
+
+// lane l's float in every lane, as a scalar (l wave-uniform)
+__device__ __forceinline__ float lane_f32(float v, int l) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+// The pair form of cn_gather_kernel<64, 1> (H = 256, record-fed, pattern route without the row-sum shortcut; large batches:
+// ocn_cn_gather_pair_min_batch): a wave owns TWO neighbouring slots of one schedule group and makes every trip to memory
+// for both at once — one load of both records, both chunks of N(src) and of the flag bytes, both column-weight lookups,
+// PAIR_UNR embedding rows per slot (eight per wave, the lone candidate's figure), both candidates' endpoint rows — so that a
+// light candidate's chain of dependent trips is filled with its neighbour's.  Two HEAVY slots (more than PAIR_UNR live entries
+// each in a round, more than eight in a shared source's union) take sixteen rows per trip: a trip is one round of latency, and
+// at eight the pair made twice the trips of its heavier member alone and ended the launch as its straggler.
+// A slot that has positions left beside one that has none walks on alone, eight rows wide.  A workgroup is two schedule groups: workgroup
+// b of the XCD-contiguous order takes groups perm[2b] and perm[2b + 1] (2b and 2b + 1 without a schedule), wave w the slots
+// 2(w & 1) and 2(w & 1) + 1 of group w >> 1.  Slots are in source order, so a pair mostly shares its source: the positions
+// then coincide, the union of the two live masks is walked in ascending position, each row is loaded once and added into
+// whichever of the two accumulator sets flagged it.  A slot that is finished, empty, past the batch's end or cn_gather_long_kernel's
+// is skipped by wave-uniform branches; every load inside them is unconditional, from a clamped index, and its use is
+// predicated (compiler lessons).  Each slot's sums are the strictly ascending-column sums of separately
+// rounded products that the one-slot form makes: every output bit is the same.
+constexpr int PAIR_UNR = 4;                  // embedding rows in flight per slot where both slots have some
+template <int V> struct pair_const { static constexpr int value = V; };
+
+// The index of a lane's column-weight lookup: its own column where it has an entry, else the column of the first lane that
+// has one — a line the wave fetches anyway (lane 0's where none has: the loads are unconditional).
+__device__ __forceinline__ int32_t pair_weight_index(unsigned f, int32_t k) {
+  const unsigned long long any = __ballot(f != 0);
+  const int32_t kd = __builtin_amdgcn_readlane(k, any ? __ffsll((long long)any) - 1 : 0);
+  return f ? k : kd;
+}
+// a lane's entry weights (0, 0 without an entry) and the wave's mask of the entries to pool
+__device__ __forceinline__ unsigned long long pair_live(unsigned f, const float4& cw, float& wa, float& wb) {
+  float a = 0.f, b = 0.f;
+  entry_weights(f, cw, 1.0f, a, b);
+  wa = f ? a : 0.f; wb = f ? b : 0.f;
+  return __ballot((wa != 0.f) | (wb != 0.f));
+}
+// the next W set bits of m, ascending (-1 past its last); the caller knows of at least LIVE
+template <int W, int LIVE>
+__device__ __forceinline__ void pair_take(unsigned long long& m, int (&sel)[W]) {
+#pragma unroll
+  for (int t = 0; t < W; ++t) {
+    sel[t] = m ? (__ffsll((long long)m) - 1) : -1;
+    if (t < LIVE) __builtin_assume(sel[t] >= 0);
+    m &= m - 1;                              // no-op once m == 0
+  }
+}
+// A trip is straight-line code — W requests, then the adds — in an instance per width, so that a light candidate's trip
+// requests what it adds and nothing else (a request past the last entry, in the widest instances only, repeats the trip's
+// first row, in flight already, and is not added).
+// ... of one slot:
+template <int W, int LIVE>
+__device__ __forceinline__ void pair_trip_one(unsigned long long& m, int32_t k, float wa, float wb, const float4* __restrict__ h4,
+                                              int lane, f32x2 (&acc)[4]) {
+  int sel[W];
+  pair_take<W, LIVE>(m, sel);
+  float4 x[W];
+#pragma unroll
+  for (int t = 0; t < W; ++t) x[t] = h4[(i64)__builtin_amdgcn_readlane(k, sel[t] < 0 ? sel[0] : sel[t]) * OCN_WAVE + lane];
+#pragma unroll
+  for (int t = 0; t < W; ++t)                // (the entry's weights are read from its lane here, behind the requests)
+    if (sel[t] >= 0) axpy_pair4(acc, f32x2{lane_f32(wa, sel[t]), lane_f32(wb, sel[t])}, x[t].x, x[t].y, x[t].z, x[t].w);
+}
+__device__ __forceinline__ void pair_rows_one(unsigned long long m, int32_t k, float wa, float wb, const float4* __restrict__ h4,
+                                              int lane, f32x2 (&acc)[4]) {
+  while (m) {
+    const int c = __popcll(m);
+    if (c > 4) pair_trip_one<2 * PAIR_UNR, 5>(m, k, wa, wb, h4, lane, acc);
+    else if (c == 4) pair_trip_one<4, 4>(m, k, wa, wb, h4, lane, acc);
+    else if (c == 3) pair_trip_one<3, 3>(m, k, wa, wb, h4, lane, acc);
+    else if (c == 2) pair_trip_one<2, 2>(m, k, wa, wb, h4, lane, acc);
+    else pair_trip_one<1, 1>(m, k, wa, wb, h4, lane, acc);
+  }
+}
+// ... of two slots of one source: the union mu of their masks m0, m1; a row is loaded once and added where it is flagged
+template <int W, int LIVE>
+__device__ __forceinline__ void pair_trip_same(unsigned long long& mu, unsigned long long m0, unsigned long long m1, int32_t k,
+                                               float wa0, float wb0, float wa1, float wb1, const float4* __restrict__ h4, int lane,
+                                               f32x2 (&acc0)[4], f32x2 (&acc1)[4]) {
+  int sel[W];
+  pair_take<W, LIVE>(mu, sel);
+  float4 x[W];
+#pragma unroll
+  for (int t = 0; t < W; ++t) x[t] = h4[(i64)__builtin_amdgcn_readlane(k, sel[t] < 0 ? sel[0] : sel[t]) * OCN_WAVE + lane];
+#pragma unroll
+  for (int t = 0; t < W; ++t)
+    if (sel[t] >= 0) {
+      if ((m0 >> sel[t]) & 1ull) axpy_pair4(acc0, f32x2{lane_f32(wa0, sel[t]), lane_f32(wb0, sel[t])}, x[t].x, x[t].y, x[t].z, x[t].w);
+      if ((m1 >> sel[t]) & 1ull) axpy_pair4(acc1, f32x2{lane_f32(wa1, sel[t]), lane_f32(wb1, sel[t])}, x[t].x, x[t].y, x[t].z, x[t].w);
+    }
+}
+// ... of two slots of two sources: W0 + W1 requests
+template <int W0, int LIVE0, int W1, int LIVE1>
+__device__ __forceinline__ void pair_trip_two(unsigned long long& m0, unsigned long long& m1, int32_t k0, int32_t k1, float wa0,
+                                              float wb0, float wa1, float wb1, const float4* __restrict__ h4, int lane,
+                                              f32x2 (&acc0)[4], f32x2 (&acc1)[4]) {
+  int s0[W0], s1[W1];
+  pair_take<W0, LIVE0>(m0, s0);
+  pair_take<W1, LIVE1>(m1, s1);
+  float4 x0[W0], x1[W1];
+#pragma unroll
+  for (int t = 0; t < W0; ++t) x0[t] = h4[(i64)__builtin_amdgcn_readlane(k0, s0[t] < 0 ? s0[0] : s0[t]) * OCN_WAVE + lane];
+#pragma unroll
+  for (int t = 0; t < W1; ++t) x1[t] = h4[(i64)__builtin_amdgcn_readlane(k1, s1[t] < 0 ? s1[0] : s1[t]) * OCN_WAVE + lane];
+#pragma unroll
+  for (int t = 0; t < W0; ++t)
+    if (s0[t] >= 0) axpy_pair4(acc0, f32x2{lane_f32(wa0, s0[t]), lane_f32(wb0, s0[t])}, x0[t].x, x0[t].y, x0[t].z, x0[t].w);
+#pragma unroll
+  for (int t = 0; t < W1; ++t)
+    if (s1[t] >= 0) axpy_pair4(acc1, f32x2{lane_f32(wa1, s1[t]), lane_f32(wb1, s1[t])}, x1[t].x, x1[t].y, x1[t].z, x1[t].w);
+}
+template <int W0, int LIVE0>
+__device__ __forceinline__ void pair_trip_two_pick(unsigned long long& m0, unsigned long long& m1, int32_t k0, int32_t k1,
+                                                   float wa0, float wb0, float wa1, float wb1, const float4* __restrict__ h4,
+                                                   int lane, f32x2 (&acc0)[4], f32x2 (&acc1)[4]) {
+  const int c = __popcll(m1);
+  if (c > 2) pair_trip_two<W0, LIVE0, PAIR_UNR, 3>(m0, m1, k0, k1, wa0, wb0, wa1, wb1, h4, lane, acc0, acc1);
+  else if (c == 2) pair_trip_two<W0, LIVE0, 2, 2>(m0, m1, k0, k1, wa0, wb0, wa1, wb1, h4, lane, acc0, acc1);
+  else pair_trip_two<W0, LIVE0, 1, 1>(m0, m1, k0, k1, wa0, wb0, wa1, wb1, h4, lane, acc0, acc1);
+}
+
+__global__ __launch_bounds__(OCN_BLOCK) void cn_gather_pair_kernel(
+    const int32_t* __restrict__ colA, i64 B, const uint8_t* __restrict__ flags, const float4* __restrict__ weights,
+    const float* __restrict__ h, float* __restrict__ xcn1, float* __restrict__ xcn2, float* __restrict__ xij,
+    const i64* __restrict__ out_row, const u64* __restrict__ rec, const int32_t* __restrict__ perm) {
+  constexpr int NS = 2;
+  constexpr i64 rowq = OCN_WAVE;             // float4 per row: one per lane
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  i64 bid = blockIdx.x;
+  if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);      // (xcd_block(): an XCD's eighth of the pairs of groups)
+  i64 grp = 2 * bid + (w >> 1);
+  if (perm) grp = perm[grp];                 // (the launch passes a schedule only where an eighth is whole pairs of groups)
+  const i64 slot0 = grp * SCHED_GROUP + 2 * (w & 1);
+  if (slot0 >= B) return;                    // whole wave leaves together
+  // both records in one load: lane l holds word l of the eight
+  u64 recw = 0;
+  if (lane < 4 * NS && slot0 + (lane >> 2) < B) recw = rec[4 * slot0 + lane];
+  // A slot that takes no part (past the batch's end, or a row of cn_gather_long_kernel's, which writes all three output
+  // rows) keeps zeros: the endpoint rows loaded for it below are row 0's and are never stored.
+  i64 e[NS], i[NS], j[NS], a0[NS], base[NS], n[NS];
+  bool live[NS], has1[NS], has2[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    u64 q[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      q[t] = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)recw, 4 * s + t) |
+             ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(recw >> 32), 4 * s + t) << 32);
+    const i64 da = (i64)(q[2] >> REC_LEN_SHIFT);
+    live[s] = slot0 + s < B && da <= LONG_ROW;
+    e[s] = live[s] ? (i64)q[0] : 0;
+    i[s] = live[s] ? (i64)(q[1] & 0xffffffffull) : 0; j[s] = live[s] ? (i64)(q[1] >> 32) : 0;
+    a0[s] = (i64)(q[2] & ((1ull << REC_LEN_SHIFT) - 1));
+    base[s] = (i64)(q[3] & ((1ull << REC_FULL2_BIT) - 1)); has1[s] = (q[3] >> 62) & 1ull; has2[s] = q[3] >> 63;
+    n[s] = live[s] && (has1[s] | has2[s]) ? da : 0;       // positions to walk: none for a candidate without CN entries
+  }
+  const bool same = live[0] && live[1] && i[0] == i[1];   // one source: one row of A (its start and length agree)
+  const float4* h4 = reinterpret_cast<const float4*>(h);
+  f32x2 acc[NS][4];                          // {acc1, acc2} component pairs of the lane's four features
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[s][c] = f32x2{0.f, 0.f};
+  // A round of 64 positions comes in an instance per case — both slots have positions left (one source / two sources), or
+  // one of them has — picked by wave-uniform tests, so that each instance is straight-line code down to the rows' trips and
+  // every load in it is unconditional: a lane past the row's end reads the last position and its flag byte is dropped.
+  auto round_two = [&](auto one_source, const i64 p0) {
+    constexpr bool SAME = decltype(one_source)::value != 0;
+    const i64 p = p0 + lane;
+    int32_t k[NS];
+    unsigned f[NS];
+    k[0] = colA[a0[0] + (p < n[0] ? p : n[0] - 1)];
+    k[1] = k[0];
+    if (!SAME) k[1] = colA[a0[1] + (p < n[1] ? p : n[1] - 1)];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) f[s] = flags[base[s] + (p < n[s] ? p : n[s] - 1)];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      if (p >= n[s]) f[s] = 0;
+    int32_t wi[NS] = {pair_weight_index(SAME ? (f[0] | f[1]) : f[0], k[0]), SAME ? 0 : pair_weight_index(f[1], k[1])};
+    asm volatile("" : "+v"(wi[0]), "+v"(wi[1]));      // both indices before the first lookup: left alone, the compiler forms the second
+                                                      // in the first one's unused w register and waits for that load to do so
+    float4 cw[NS];
+    cw[0] = weights[wi[0]];
+    cw[1] = cw[0];
+    if (!SAME) cw[1] = weights[wi[1]];
+    float wa[NS], wb[NS];
+    unsigned long long m[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) m[s] = pair_live(f[s], cw[s], wa[s], wb[s]);
+#define PAIR_SAME_TRIP(W, LIVE) pair_trip_same<W, LIVE>(mu, m[0], m[1], k[0], wa[0], wb[0], wa[1], wb[1], h4, lane, acc[0], acc[1])
+#define PAIR_TWO_TRIP(W, LIVE) pair_trip_two_pick<W, LIVE>(m[0], m[1], k[0], k[1], wa[0], wb[0], wa[1], wb[1], h4, lane, acc[0], acc[1])
+    if constexpr (SAME) {
+      unsigned long long mu = m[0] | m[1];   // the union of the live positions, ascending
+      while (mu) {
+        const int c = __popcll(mu);
+        if (c > 8) PAIR_SAME_TRIP(4 * PAIR_UNR, 9);          // a heavy pair: as many trips as one heavy candidate alone makes
+        else if (c > 4) PAIR_SAME_TRIP(2 * PAIR_UNR, 5);
+        else if (c == 4) PAIR_SAME_TRIP(4, 4);
+        else if (c == 3) PAIR_SAME_TRIP(3, 3);
+        else if (c == 2) PAIR_SAME_TRIP(2, 2);
+        else PAIR_SAME_TRIP(1, 1);
+      }
+    } else {
+      while (m[0] && m[1]) {
+        const int c = __popcll(m[0]);
+        if (c > 4 && __popcll(m[1]) > 4)                      // a heavy pair: as many trips as one heavy candidate alone makes
+          pair_trip_two<2 * PAIR_UNR, 5, 2 * PAIR_UNR, 5>(m[0], m[1], k[0], k[1], wa[0], wb[0], wa[1], wb[1], h4, lane, acc[0], acc[1]);
+        else if (c > 2) PAIR_TWO_TRIP(PAIR_UNR, 3);
+        else if (c == 2) PAIR_TWO_TRIP(2, 2);
+        else PAIR_TWO_TRIP(1, 1);
+      }
+      pair_rows_one(m[0], k[0], wa[0], wb[0], h4, lane, acc[0]);      // what one slot has beyond the other: on its own, eight wide
+      pair_rows_one(m[1], k[1], wa[1], wb[1], h4, lane, acc[1]);
+    }
+#undef PAIR_SAME_TRIP
+#undef PAIR_TWO_TRIP
+  };
+  auto round_one = [&](auto which, const i64 p0) {
+    constexpr int S = decltype(which)::value;
+    const i64 p = p0 + lane;
+    const int32_t k = colA[a0[S] + (p < n[S] ? p : n[S] - 1)];
+    unsigned f = flags[base[S] + (p < n[S] ? p : n[S] - 1)];
+    if (p >= n[S]) f = 0;
+    const float4 cw = weights[pair_weight_index(f, k)];
+    float wa, wb;
+    const unsigned long long m = pair_live(f, cw, wa, wb);
+    pair_rows_one(m, k, wa, wb, h4, lane, acc[S]);
+  };
+  const i64 n_max = n[0] > n[1] ? n[0] : n[1];
+  for (i64 p0 = 0; p0 < n_max; p0 += OCN_WAVE) {
+    const bool on0 = p0 < n[0], on1 = p0 < n[1];
+    if (on0 && on1) {
+      if (same) round_two(pair_const<1>{}, p0);
+      else round_two(pair_const<0>{}, p0);
+    } else if (on0) round_one(pair_const<0>{}, p0);
+    else round_one(pair_const<1>{}, p0);
+  }
+  // both output rows and the endpoint rows, then the stores
+  i64 oe[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) oe[s] = out_row ? out_row[e[s]] : e[s];
+  float4 xi[NS], xj[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) { xi[s] = h4[i[s] * rowq + lane]; xj[s] = h4[j[s] * rowq + lane]; }      // (one source: its row twice, one line)
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+    if (live[s])
+      pool_emit(reinterpret_cast<float4*>(xcn1) + oe[s] * rowq + lane, reinterpret_cast<float4*>(xcn2) + oe[s] * rowq + lane,
+                reinterpret_cast<float4*>(xij) + oe[s] * rowq + lane,
+                make_float4(acc[s][0].x, acc[s][1].x, acc[s][2].x, acc[s][3].x),
+                make_float4(acc[s][0].y, acc[s][1].y, acc[s][2].y, acc[s][3].y), xi[s], xj[s], !out_row || has1[s],
+                !out_row || has1[s] || has2[s]);
 }
 
 // The sequential sum of ranks [0, nr) of a compacted round: acc += w[r] * x[r], one multiply and one add per entry and
@@ -647,6 +914,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_generic(
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
+// H = 256 batches of at least this many candidates take the pair form (cn_gather_pair_kernel): B / 2 waves must still fill
+// the chip's wave slots several times over.  Process-wide; see ocn_hip.h.
+static int64_t g_gather_pair_min_batch = 32768;
+
 template <int LPE, int NV>
 static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int64_t* src, const int64_t* dst,
                           const int64_t* order, int64_t B, const int64_t* off, const uint8_t* flags,
@@ -670,6 +941,18 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
 #define PACKED_ARGS (const i64*)rowptrA, colA, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B, \
                     (const i64*)off, flags, wc, (const float4*)weights, h, (int)H, xcn1, xcn2, xij,           \
                     (const i64*)out_row, cnt1, cnt2, (const u64*)rec
+  if constexpr (LPE == OCN_WAVE && NV == 1) {
+    // two slots per wave (cn_gather_pair_kernel): record-fed pattern batches without the row-sum shortcut, from the bound on.
+    // A workgroup is two schedule groups, so a schedule is followed only where an XCD's eighth is whole pairs of groups — an odd
+    // eighth keeps the one-slot form; without a schedule the pairs are consecutive groups of the source order.
+    const i64 n_groups = (B + epb - 1) / epb;
+    if (rec && !wc && !rowsum && B >= g_gather_pair_min_batch && (!sched || (n_groups >> 3) % 2 == 0)) {
+      hipLaunchKernelGGL(cn_gather_pair_kernel, dim3((unsigned)((n_groups + 1) / 2)), dim3(OCN_BLOCK), 0, st, colA, (i64)B, flags,
+                         (const float4*)weights, h, xcn1, xcn2, xij, (const i64*)out_row, (const u64*)rec,
+                         sched ? perm : (const int32_t*)nullptr);
+      packed = false;
+    }
+  }
   if (packed)
     hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,
                        PACKED_ARGS, sched ? perm : (const int32_t*)nullptr, rowsum);
@@ -738,7 +1021,13 @@ int ocn_cn_gather(const int64_t* rowptrA, const int32_t* colA, const int64_t* sr
   return launch_status();
 }
 
-#define LAUNCH_GATHER3(LPE, NV)                                                                      \
+int64_t ocn_cn_gather_pair_min_batch(int64_t min_rows) {
+  const int64_t prev = g_gather_pair_min_batch;
+  if (min_rows >= 0) g_gather_pair_min_batch = min_rows;
+  return prev;
+}
+
+#define LAUNCH_GATHER3(LPE, NV)                                                                     \
   hipLaunchKernelGGL((cn_gather3_kernel<LPE, NV>),                                                   \
                      dim3((unsigned)((B + (i64)OCN_WPB * (OCN_WAVE / (LPE)) - 1) / ((i64)OCN_WPB * (OCN_WAVE / (LPE))))), \
                      dim3(OCN_BLOCK), 0, (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)src,      \

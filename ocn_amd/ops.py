@@ -1967,6 +1967,12 @@ def flags_pair_min_batch(min_rows: int = -1) -> int:
     return int(_lib.lib().ocn_cn_flags_pair_min_batch(int(min_rows)))
 
 
+def gather_pair_min_batch(min_rows: int = -1) -> int:
+    """ocn_hip.h: ocn_cn_gather_pair_min_batch — record-fed H = 256 batches of at least ``min_rows`` candidates are pooled with
+    two slots per wave (same bits); returns the previous bound, a negative argument only queries."""
+    return int(_lib.lib().ocn_cn_gather_pair_min_batch(int(min_rows)))
+
+
 @_on_device
 def heads_fused(x1: Tensor, x2: Tensor, xij: Tensor, pack: dict, ranges: Optional[Tensor], y_row_map: Optional[Tensor],
                 b_on_union: bool, scratch: Tensor, dump: Optional[Tensor] = None) -> Optional[Tensor]:

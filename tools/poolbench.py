@@ -1,6 +1,7 @@
 """The pooling kernel alone on the bench workload, variants interleaved in ONE process (run-to-run and box-to-box noise is
 larger than most effects worth keeping):  python tools/poolbench.py [--iters 30]
-Variants: the visiting order of the slot groups (ops.heavy_first / ops.sched_segment).  Medians of HIP-event times of
+Variants: the pair form against the one-slot form (ops.gather_pair_min_batch: 0 / past any batch), then the visiting order
+of the slot groups (ops.heavy_first / ops.sched_segment) at the library's own bound.  Medians of HIP-event times of
 `ocn_gather_schedule` + `ocn_cn_gather` on 4 distinct batches; results must agree bit for bit."""
 import argparse
 import os
@@ -27,12 +28,15 @@ def main():
     wl = bench.build_workload(args, dev, 0, 1)
     adj, adj2, h = wl["adj"], wl["adj2"], wl["h"]
     ops.validate_indices = False
-    variants = [("longest first", True, 0), ("source order", False, 0)] + [(f"segments of {s}", True, s) for s in (a.segments or [])]
+    own = ops.gather_pair_min_batch()
+    variants = [("pairs", True, 0, 0), ("one slot", True, 0, 1 << 40), ("longest first", True, 0, own), ("source order", False, 0, own)] + \
+               [(f"segments of {s}", True, s, own) for s in (a.segments or [])]
     times = {v[0]: [] for v in variants}
     ref = {}
     for rep in range(a.iters):
-        for name, heavy, seg in variants:
+        for name, heavy, seg, bound in variants:
             ops.heavy_first, ops.sched_segment = heavy, seg
+            ops.gather_pair_min_batch(bound)
             for bi, e in enumerate(wl["edges"]):
                 st = CNState(adj, adj, adj2, e)                    # (sched allocated only when heavy_first)
                 w = st.weights_cn5(torch.zeros(1, device=dev))
@@ -47,7 +51,8 @@ def main():
                 if rep == 0:
                     key = tuple(float(o.double().sum()) for o in out)
                     assert a.no_check or ref.setdefault(bi, key) == key, (name, bi)
-    for name, _, _ in variants:
+    ops.gather_pair_min_batch(own)
+    for name, _, _, _ in variants:
         t = sorted(times[name])
         print(f"{name:22s} median {t[len(t) // 2]:7.1f} us  min {t[0]:7.1f}  p90 {t[int(len(t) * 0.9)]:7.1f}  (n={len(t)})")
 
