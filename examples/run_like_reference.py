@@ -16,6 +16,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32 --recommend-eval 200   # ... and where the test links rank
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-rw 32:256:2 --recommend-eval 200   # ... a short list from random walks instead
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain-edges 10 # ... down to the edges: the 10 strongest messages
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
@@ -42,7 +43,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
-from ocn_amd.recommend import (prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
+from ocn_amd.recommend import (RandomWalks, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import (negative_edges, negative_targets, two_hop_negative_edges,  # noqa: E402
@@ -173,6 +174,10 @@ def test_heuristic(kind, data, split_edge, evaluator, batch_size, args):
     return out
 
 
+def rw_name(rw):
+    return f"random walks {rw.m}:{rw.walks}:{rw.length}" + (f":{rw.decay:g}" if rw.decay is not None else "")
+
+
 @torch.no_grad()
 def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5):
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
@@ -184,6 +189,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
     --recommend-hops 3: the candidates within three hops (every target with a non-empty cn1 or cn2), expanded from the adjacency;
     the prefilter is then KIND:M:DECAY and ranks them by the local path index P2 + DECAY * P3.
+    --recommend-rw M:W:L[:DECAY]: the short list comes from W random walks of L steps per source instead (the M most visited nodes,
+    ranked by c2 + DECAY * c3; ocn_amd.recommend.RandomWalks): a sample of the candidates at a cost that no hub source raises.
     --recommend-eval Q: the held-out test links of the first Q distinct test sources are ranked among the candidates of the selected
     route (ocn_amd.ranking) and recall / NDCG / hit rate @K, MRR, coverage and retention are printed; with a prefilter the
     unfiltered run stands beside it.
@@ -243,7 +250,11 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             # trained model supports no claim about the quality of a prefilter
             full, _ = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, hops=args.recommend_hops)
             kept = int(((dst[:, :, None] == full[:, None, :]) & (full[:, None, :] >= 0)).any(1).sum())
-            if args.recommend_hops == 3:
+            if isinstance(args.recommend_prefilter, RandomWalks):
+                n_all = int((three_hop_candidates(adj, sources) if args.recommend_hops == 3 else two_hop_candidates(adj, adj2, sources))[0][-1])
+                n_short = int(random_walk_short_list(adj, sources, args.recommend_prefilter)[0][-1])
+                name = rw_name(args.recommend_prefilter)
+            elif args.recommend_hops == 3:
                 kind, m, decay = args.recommend_prefilter
                 n_all = int(three_hop_candidates(adj, sources)[0][-1])
                 n_short = int(prefilter_candidates(adj, sources, kind, m, hops=3, decay=decay)[0][-1])
@@ -278,7 +289,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             h = state.h if state is not None else model(data.x, adj)
             route = f"{args.predictor} over {args.recommend_hops} hops" + (" (walk route)" if adj2 is None else "")
             if args.recommend_prefilter:
-                show(route + " prefilter " + ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in args.recommend_prefilter),
+                show(route + " prefilter " + (rw_name(args.recommend_prefilter) if isinstance(args.recommend_prefilter, RandomWalks) else
+                                              ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in args.recommend_prefilter)),
                      rank_links(predictor, h, adj, adj2, first, truth, args.testbs, args, prefilter=args.recommend_prefilter,
                                 hops=args.recommend_hops))
             show(route + (" unfiltered" if args.recommend_prefilter else ""),
@@ -398,6 +410,10 @@ def main(argv=None):
     ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M[:DECAY]",
                     help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
                          "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
+    ap.add_argument("--recommend-rw", default=None, metavar="M:W:L[:DECAY]",
+                    help="with --recommend and a model, instead of --recommend-prefilter: short-list the M most visited nodes of W "
+                         "random walks of L = --recommend-hops steps per source (ocn_amd.recommend.RandomWalks; DECAY with L = 3) and "
+                         "let the model rank only those; with --recommend-eval, coverage reads 'visited at all'")
     ap.add_argument("--recommend-eval", type=int, default=0, metavar="Q",
                     help="with --recommend: rank the held-out test links of the first Q distinct test sources among the candidates of "
                          "the selected route (ocn_amd.ranking) and print recall / NDCG / hit rate @K, MRR, coverage and, with "
@@ -453,6 +469,23 @@ def main(argv=None):
             if not (math.isfinite(d) and d >= 0):
                 ap.error("--recommend-prefilter KIND:M:DECAY: DECAY is a finite number >= 0")
             args.recommend_prefilter += (d,)
+    if args.recommend_rw:
+        if args.recommend_prefilter:
+            ap.error("--recommend-rw and --recommend-prefilter are two short lists: give one")
+        if args.heuristic or not args.recommend:
+            ap.error("--recommend-rw M:W:L[:DECAY]: needs a model and --recommend K")
+        parts = args.recommend_rw.split(":")
+        try:
+            if not 3 <= len(parts) <= 4:
+                raise ValueError("M:W:L with --recommend-hops 2, M:W:L:DECAY with --recommend-hops 3")
+            rw = RandomWalks(int(parts[0]), int(parts[1]), int(parts[2]), float(parts[3]) if len(parts) == 4 else None)
+            if rw.length != args.recommend_hops:
+                raise ValueError(f"L = {rw.length} steps, --recommend-hops {args.recommend_hops}: the two must be equal")
+            if args.recommend > rw.m:
+                raise ValueError(f"M = {rw.m} is fewer than K = {args.recommend}")
+        except ValueError as e:
+            ap.error(f"--recommend-rw M:W:L[:DECAY]: {e}")
+        args.recommend_prefilter = rw            # (one short list per request: the calls below pass it as prefilter=)
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

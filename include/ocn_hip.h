@@ -55,7 +55,9 @@ extern "C" {
  *    ocn_segment_topk: ranking metrics); ocn_sample_two_hop_window_cols, ocn_sample_two_hop (hard negatives: draws from the
  *    2-hop candidate set that is served, selected in the expansion's LDS bitmap without listing the set); ocn_sddmm_csr (the sampled
  *    dense-dense product on the pattern of an encoder operator: the gradient of a layer with respect to its messages);
- *    ocn_cn_gather_pair_min_batch (the H = 256 pooling takes two slots per wave at large batches; same bits). */
+ *    ocn_cn_gather_pair_min_batch (the H = 256 pooling takes two slots per wave at large batches; same bits);
+ *    ocn_rw_max_walks, ocn_rw_visits_count, ocn_rw_visits_fill (random-walk retrieval: a source's candidates and their visit
+ *    counts from W walks of 2 or 3 steps, at a cost that does not depend on its degree). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -616,6 +618,41 @@ int ocn_sample_two_hop(const int64_t* rowptrA, const int32_t* colA, const int64_
                        const int64_t* rows, int64_t Q, int32_t drop_self, int64_t window_cols /* 0: the default */,
                        const int64_t* sptr /* [Q + 1] */, const int64_t* sid /* [sptr[Q]] or NULL */, int64_t q0, uint64_t seed,
                        int32_t* count /* [Q] or NULL */, int64_t* out /* [sptr[Q]] */, void* stream);
+
+/* Random-walk retrieval: the candidates of a source from W short uniform walks, not from its whole neighbourhood.  The visit
+ * counts are a Monte-Carlo estimate of the "ra" path index that ocn_two_hop_sums_fill / ocn_frontier_sums_fill compute
+ * exactly: E[c2(t)] / W = RA(s, t) / deg s and E[c3(t)] / W = P3_ra(s, t) / deg s.  The cost is
+ * W * L dependent row reads per source, whatever its degree.
+ *
+ * A, M: CSR, sorted duplicate-free int32 columns, n_cols rows and columns (1 <= n_cols < 2^31); the walk follows the rows of A
+ * as they are given (a directed A is legal), M is the exclusion.  sources[]: valid row ids (a source may repeat).
+ * Walk w (0 <= w < walks) of source s starts at p_0 = s.  Step t = 1 .. length: where row p_{t-1} of A is empty the walk ends;
+ * else p_t = colA[rowptrA[p_{t-1}] + floor(u_t * deg(p_{t-1}) / 2^64)].  Random words (Philox4x32-10 and the key rule of the
+ * samplers above): u_1 = out[0] | out[1] << 32 and u_2 = out[2] | out[3] << 32 of the counter (w, s & 0xffffffff, s >> 32, 5),
+ * u_3 = out[0] | out[1] << 32 of the counter (w, s & 0xffffffff, s >> 32, 6).  The counter carries the SOURCE id, not the query
+ * index: a source's walks depend on (seed, s, A, walks, length) alone, not on the other queries or their order.
+ * c2[v] = the walks with p_2 = v, c3[v] = those with p_3 = v (length 3 only); p_1 is never counted.  The candidates of s are
+ * the nodes with c2 + c3 > 0 that are neither s nor in row s of M.
+ *
+ * ocn_rw_visits_count: count[q] = the candidates of sources[q]; ocn_scan_i32 of it gives ptr.
+ * ocn_rw_visits_fill: the same walks again; from ptr[q] on, in ASCENDING node id, edges = (s, v), visits = (c2, c3) and
+ *   val = (float)c2 + decay * (float)c3 — one rounded product, one rounded add; (float)c2 at length 2, where decay is not read.
+ *   Nothing is written at or past ptr[q + 1].  edges 16-byte aligned, visits 8-byte aligned.
+ * One workgroup per query.  The visits are counted in an open-addressing table in LDS (a compare-and-swap claims a node's slot,
+ * an integer add counts), sized from walks * (length - 1) so that it cannot overflow: no status, no fallback, and the counts
+ * depend on neither the schedule nor the launch geometry.  The survivors are sorted by node id in LDS.  No global atomics, no
+ * workspace.  ocn_rw_max_walks(): the largest `walks` the LDS of a CU holds at length 3 (at least 1024, at most 65535: the
+ * counts are 16-bit fields of one word).
+ * NULL pointers, Q < 0, n_cols outside 1 .. 2^31 - 1, walks outside 1 .. ocn_rw_max_walks(), length outside {2, 3}, a decay that
+ * is negative or not finite, a misaligned edges / visits: OCN_EINVAL before any HIP call.  Q == 0 returns 0 (after the checks). */
+int32_t ocn_rw_max_walks(void);
+int ocn_rw_visits_count(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM, int64_t n_cols,
+                        const int64_t* sources, int64_t Q, int32_t walks, int32_t length, uint64_t seed,
+                        int32_t* count /* [Q] */, void* stream);
+int ocn_rw_visits_fill(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrM, const int32_t* colM, int64_t n_cols,
+                       const int64_t* sources, int64_t Q, int32_t walks, int32_t length, uint64_t seed,
+                       const int64_t* ptr /* [Q + 1] */, float decay, int64_t* edges /* [ptr[Q]][2] */, float* val /* [ptr[Q]] */,
+                       int32_t* visits /* [ptr[Q]][2] */, void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

@@ -85,6 +85,10 @@ SIGNATURES = {
     "ocn_sample_two_hop_window_cols": (c_int64, []),
     "ocn_sample_two_hop": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P, _P, c_int64, ctypes.c_uint64, _P, _P,
                                      _P]),
+    "ocn_rw_max_walks": (c_int32, []),
+    "ocn_rw_visits_count": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int32, ctypes.c_uint64, _P, _P]),
+    "ocn_rw_visits_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int32, ctypes.c_uint64, _P, c_float, _P, _P,
+                                     _P, _P]),
     "ocn_gather_schedule": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "ocn_cn_gather_pair_min_batch": (c_int64, [c_int64]),
     "ocn_coo_to_csr_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),

@@ -8,33 +8,8 @@
 // Hard negatives are drawn the same way from the candidate set that is served: the r-th smallest member of a source's 2-hop row
 // difference, selected in the LDS bitmap the 2-hop expansion builds, without ever listing the set (ocn_sample_two_hop).
 #include "common.h"
+#include "philox.h"       // the generator, sample_rank and the counter streams
 #include "window_sweep.h"
-
-// ---------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants)
-// ---------------------------------------------------------------------------------------------
-constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
-constexpr unsigned PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-constexpr unsigned SAMPLE_STREAM_PAIRS = 1u, SAMPLE_STREAM_ROWS = 2u;      // counter word 3: the samplers never share a word
-constexpr unsigned SAMPLE_STREAM_TWO_HOP = 3u, SAMPLE_STREAM_TWO_HOP_ID = 4u;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned hi0 = __umulhi(PHILOX_M0, c.x), lo0 = PHILOX_M0 * c.x;
-    const unsigned hi1 = __umulhi(PHILOX_M1, c.z), lo1 = PHILOX_M1 * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-  return c;
-}
-
-// r = floor(u * m / 2^64) for the 64-bit word of a counter: uniform over [0, m) up to a bias below m / 2^64
-__device__ __forceinline__ u64 sample_rank(uint4 ctr, u64 seed, u64 m) {
-  const uint4 w = philox4x32_10(ctr, (unsigned)seed, (unsigned)(seed >> 32));
-  return __umul64hi((u64)w.x | ((u64)w.y << 32), m);
-}
 
 // ---------------------------------------------------------------------------------------------
 // selection in the complement of a sorted row

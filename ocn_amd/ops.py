@@ -1216,6 +1216,73 @@ def sample_two_hop(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor,
     return (out, count) if want_count else out
 
 
+def rw_max_walks() -> int:
+    """The largest ``walks`` of ``rw_visits_count`` / ``rw_visits_fill`` (ocn_hip.h: ocn_rw_max_walks): what the LDS of a CU
+    holds at ``length=3``."""
+    return int(_lib.lib().ocn_rw_max_walks())
+
+
+def _rw_args(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, walks: int, length: int,
+             seed: int) -> Tuple[int, int, int, int, int]:
+    """The operand checks of both random-walk passes: those of the row difference (A and M of one size; M's columns sorted and
+    duplicate-free, which this layer cannot see), ``walks`` in 1 .. ``rw_max_walks()``, ``length`` 2 or 3, the seed.
+    Returns (Q, n, walks, length, seed)."""
+    Q = _row_diff_args(rowptrA, colA, rowptrM, colM, rows)
+    n = rowptrA.numel() - 1
+    if not 0 < n < (1 << 31):
+        raise ValueError(f"A has {n} rows: int32 columns serve 1 .. 2^31 - 1")
+    if isinstance(walks, bool) or isinstance(length, bool):
+        raise ValueError(f"walks and length must be ints, got {walks!r}, {length!r}")
+    walks, length = int(walks), int(length)
+    if not 1 <= walks <= rw_max_walks():
+        raise ValueError(f"walks must be in 1..{rw_max_walks()}, got {walks}")
+    if length not in (2, 3):
+        raise ValueError(f"length must be 2 or 3, got {length}")
+    return Q, n, walks, length, _seed(seed)
+
+
+@_on_device
+def rw_visits_count(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, walks: int, length: int,
+                    seed: int) -> Tensor:
+    """count[q] = the nodes that the second or third step of one of ``walks`` uniform walks of ``length`` steps from
+    s = rows[q] reaches and that are neither s nor in row s of M (ocn_hip.h: ocn_rw_visits_count): int32 [Q].  ``scan_i32`` of
+    it gives the offsets ``rw_visits_fill`` writes at.  A source's walks are fixed by (seed, s, A, walks, length)."""
+    Q, n, walks, length, seed = _rw_args(rowptrA, colA, rowptrM, colM, rows, walks, length, seed)
+    count = torch.empty(Q, dtype=torch.int32, device=rows.device)
+    if Q:
+        check(_lib.lib().ocn_rw_visits_count(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q, walks, length, seed,
+                                             ptr(count), stream_ptr()), "ocn_rw_visits_count")
+        _mark("rw_visits_count")
+    return count
+
+
+@_on_device
+def rw_visits_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor, rows: Tensor, walks: int, length: int,
+                   seed: int, off: Tensor, decay: float = 0.0, total: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The same walks again, written (ocn_hip.h: ocn_rw_visits_fill): (edges int64 [T, 2], val float32 [T], visits int32 [T, 2]).
+    From ``off[q]`` on, in ascending node id: the pair (s, v), ``visits`` = (c2, c3) — the walks whose second / third step ends
+    in v — and ``val = float32(c2) + float32(decay) * float32(c3)``, two roundings (``float32(c2)`` at ``length=2``, where
+    ``decay`` must stay 0).  ``off``: ``scan_i32(rw_visits_count(...))`` of the same operands; ``total`` as for
+    ``row_diff_fill``."""
+    import math
+    Q, n, walks, length, seed = _rw_args(rowptrA, colA, rowptrM, colM, rows, walks, length, seed)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not math.isfinite(decay) or decay < 0:
+        raise ValueError(f"decay must be a finite number >= 0, got {decay!r}")
+    decay = float(torch.tensor(float(decay), dtype=torch.float32).item())          # (rounded to fp32 here, not by the ABI)
+    if not math.isfinite(decay):
+        raise ValueError("decay is not finite in float32")
+    if length == 2 and decay != 0.0:
+        raise ValueError("decay belongs to length=3")
+    T, edges = _fill_pairs(off, Q, total, rows.device)
+    val = torch.empty(T, dtype=torch.float32, device=rows.device)
+    visits = torch.empty(T, 2, dtype=torch.int32, device=rows.device)
+    if Q and T:
+        check(_lib.lib().ocn_rw_visits_fill(ptr(rowptrA), ptr(colA), ptr(rowptrM), ptr(colM), n, ptr(rows), Q, walks, length, seed,
+                                            ptr(off), decay, ptr(edges), ptr(val), ptr(visits), stream_ptr()), "ocn_rw_visits_fill")
+        _mark("rw_visits_fill")
+    return edges, val, visits
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 

@@ -37,8 +37,8 @@ class RankResult:
     ``tptr`` int64 [Q + 1] and ``target`` int64 [P]: the targets of source ``q`` are ``target[tptr[q]:tptr[q + 1]]``; ``n_cand``
     int64 [Q]: the lengths of the segments that were ranked; ``rank`` int64 [P]: 0 = not ranked, else the 1-based place among the
     scored candidates of its source; ``retrieval_rank`` int64 [P], None without a short list: the place by the short-list heuristic
-    among ALL candidates within ``hops`` (0 = no candidate: beyond ``hops``, the source itself, or in ``known``); ``m``: the size
-    of the short list or None.  ``rank > 0`` exactly when ``1 <= retrieval_rank <= m``."""
+    among ALL candidates within ``hops`` (0 = no candidate: beyond ``hops``, the source itself, or in ``known`` — or, under a
+    random-walk short list, not visited by any walk); ``m``: the size of the short list or None.  ``rank > 0`` exactly when ``1 <= retrieval_rank <= m``."""
     sources: Tensor
     tptr: Tensor
     target: Tensor
@@ -108,7 +108,10 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     sync (its size).  Targets that are no candidates (already in ``known``, the source itself, beyond ``hops``) get rank 0.
 
     ``prefilter``: the model ranks the short list only, and ``retrieval_rank`` tells where the heuristic put every target among
-    all the candidates within ``hops`` — taken in the retrieval pass itself, chunk by chunk under ``hops=3``."""
+    all the candidates within ``hops`` — taken in the retrieval pass itself, chunk by chunk under ``hops=3``.
+
+    ``prefilter=recommend.RandomWalks(...)``: ``retrieval_rank`` is the place by the walks' ``val`` among all VISITED candidates
+    of the source, before the cut to ``m`` — 0 means that no walk reached the target (or that it is no candidate at all)."""
     if predictor.training:
         raise RuntimeError("rank_links is the eval path; call predictor.eval() first")
     hops, prefilter = R._check_request(predictor, adj2, 1, prefilter, hops)
@@ -116,7 +119,8 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     ptr, edges, scores, rrank = R._score_request(predictor, h, adj, adj2, sources, batch_size, args, known, run_ahead, prefilter,
                                                  hops, targets if prefilter is not None else None)
     rank, _ = ops.segment_rank(scores, ptr, edges, *targets)
-    return RankResult(sources, targets[0], targets[1], ptr[1:] - ptr[:-1], rank, rrank, None if prefilter is None else prefilter[1])
+    return RankResult(sources, targets[0], targets[1], ptr[1:] - ptr[:-1], rank, rrank,
+                      None if prefilter is None else (prefilter.m if isinstance(prefilter, R.RandomWalks) else prefilter[1]))
 
 
 @torch.no_grad()
@@ -173,8 +177,9 @@ def ranking_metrics(res: RankResult, ks: Sequence[int] = (10, 20, 50, 100)) -> d
     * ``pair_hits@k``: the share of (source, target) pairs that are hits;
 
     and once: ``mrr`` (the mean of 1 / best rank of a source, 0 where none of its targets is ranked), ``coverage`` (the share
-    of pairs that are candidates at all: ``retrieval_rank > 0`` with a short list, else ``rank > 0``), with a short list
-    ``retention`` (the share of candidate pairs the short list kept) and ``m``; ``n_eval``, ``n_sources``, ``n_pairs``.  A share
+    of pairs that are candidates at all: ``retrieval_rank > 0`` with a short list, else ``rank > 0``; under a random-walk short
+    list, ``recommend.RandomWalks``, that reads "visited by a walk at all": a sampled stage misses candidates the exact
+    expansions list), with a short list ``retention`` (the share of candidate pairs the short list kept) and ``m``; ``n_eval``, ``n_sources``, ``n_pairs``.  A share
     of nothing is 0.0.
 
     Plain torch on the host: ``tptr`` and the ranks are copied there once (a result on the CPU is read where it is), counts are

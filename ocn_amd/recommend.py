@@ -23,12 +23,19 @@ made and return a flat score vector.  This module makes the pairs and picks from
   ``ops.frontier_sums_fill``: a per-query list of nodes and weights, and seeds) chains: the unexcluded 2-hop list of ``s``,
   weighted by ``decay · w[c] · P₂(s, c)`` and seeded with ``P₂``, expands into the candidates within three hops and their
   local path index ``P₂ + decay · P₃`` in ordered fp32 (``three_hop_candidates``, ``path_scored_candidates``).  ``hops=3`` in
-  ``recommend_links`` takes its candidates from there, with ``prefilter=(kind, m, decay)`` through a short list.  Opt-in.
+  ``recommend_links`` takes its candidates from there, with ``prefilter=(kind, m, decay)`` through a short list.  Opt-in;
+* random-walk retrieval: the expansions above enumerate every candidate within ``hops`` before they keep ``m``, so a request
+  costs what the neighbourhood of its worst source holds.  ``W`` uniform walks of 2 or 3 steps from a source cost ``W · L``
+  dependent row reads whatever its degree, and their visit counts estimate the "ra" path index: ``E[c₂(t)] / W = RA(s, t) /
+  deg s``, ``E[c₃(t)] / W = P₃(s, t) / deg s`` (``random_walk_candidates``, ``ops.rw_visits_count`` / ``_fill``).
+  ``random_walk_short_list`` keeps the ``m`` most visited and ``prefilter=RandomWalks(m, walks, length[, decay, seed])`` lets the
+  model rank only those.  A sample, not the exact list: ``ranking.rank_links`` measures what it keeps.  Opt-in.
 
 Everything runs on one GPU; dealing the sources over several is not built here.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -310,8 +317,106 @@ def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, 
     return _path_index_pass(adj, sources, kind, _check_m(m), known, hops, decay, budget)[0]
 
 
+# ---------------------------------------------------------------------------------------------
+# random-walk retrieval
+# ---------------------------------------------------------------------------------------------
+def _check_rw(walks, length, decay, seed) -> Tuple[int, int, float, int]:
+    """(walks, length, decay32-to-be, seed) of a random-walk stage: ``walks`` in 1 .. ``ops.rw_max_walks()``, ``length`` 2 or 3,
+    ``decay`` required with ``length=3`` (``_check_decay``) and refused with ``length=2``, ``seed`` in 0 .. 2^64 - 1."""
+    if isinstance(length, bool) or length not in (2, 3):
+        raise ValueError(f"length must be 2 or 3 (the steps of a walk), got {length!r}")
+    if isinstance(walks, bool) or not isinstance(walks, int) or not 1 <= walks <= ops.rw_max_walks():
+        raise ValueError(f"walks must be an int in 1..{ops.rw_max_walks()}, got {walks!r}")
+    if length == 3:
+        decay = _check_decay(decay)
+    elif decay is not None:
+        raise ValueError("decay belongs to length=3")
+    else:
+        decay = 0.0
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+        raise ValueError(f"seed must be an int in 0 .. 2^64 - 1, got {seed!r}")
+    return int(walks), int(length), decay, int(seed)
+
+
+@dataclass(frozen=True)
+class RandomWalks:
+    """A random-walk retrieval stage, the ``prefilter`` of ``recommend_links`` / ``ranking.rank_links``: the ``m`` most visited
+    candidates of ``walks`` uniform walks of ``length`` steps per source, ranked by ``c₂ + decay · c₃`` (``decay`` with
+    ``length=3`` only, no default there).  Checked on construction: ``1 <= m <= ops.segment_topk_max_k()``, ``1 <= walks <=
+    ops.rw_max_walks()``, ``length`` in (2, 3), ``decay`` finite and >= 0, ``seed`` in 0 .. 2^64 - 1."""
+    m: int
+    walks: int
+    length: int
+    decay: Optional[float] = None
+    seed: int = 0
+
+    def __post_init__(self):
+        if isinstance(self.m, bool) or not isinstance(self.m, int):
+            raise ValueError(f"m must be an int, got {self.m!r}")
+        _check_m(self.m)
+        _check_rw(self.walks, self.length, self.decay, self.seed)
+
+
+def random_walk_candidates(adj: SparseTensor, sources: Tensor, walks: int, length: int, decay: Optional[float] = None,
+                           known: Optional[SparseTensor] = None, seed: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The nodes that ``walks`` uniform random walks of ``length`` (2 or 3) steps from every source visit, in the layout of
+    ``path_scored_candidates`` with the counts beside it: (``ptr`` int64 [Q + 1], ``edges`` int64 [T, 2], ``val`` float32 [T],
+    ``visits`` int32 [T, 2]).  Walk ``w`` of source ``s`` starts at ``s`` and takes, at every step, the ``floor(u · deg / 2⁶⁴)``-th
+    entry of the row of ``adj`` it stands on (a walk that meets an empty row ends); ``visits[:, 0] = c₂`` counts the walks whose
+    second step ends in the node, ``visits[:, 1] = c₃`` those whose third does (``length=3``; the first step is never counted),
+    and ``val = float32(c₂) + float32(decay) · float32(c₃)``, two roundings (``float32(c₂)`` for ``length=2``).  A source's
+    segment holds every visited node that is neither the source nor in its row of ``known`` (``adj`` by default), ascending, at
+    most ``walks · (length - 1)`` of them.
+
+    With uniform steps ``E[c₂(t)] / walks = RA(s, t) / deg s`` and ``E[c₃(t)] / walks = P₃(s, t) / deg s`` with ``P₃`` the
+    3-walk sum of ``path_scored_candidates(kind="ra", hops=3)``: ``val`` estimates ``deg s · walks`` times the "ra" path index
+    ``P₂ + decay · P₃``, and a source's ranking by it estimates the exact one.  The random words are Philox4x32-10 blocks whose
+    counter carries the SOURCE id (ocn_hip.h: ocn_rw_visits_count): a source's segment is fixed bit for bit by (``seed``, the
+    source, ``adj``, ``known``, ``walks``, ``length``) — not by the other sources, their order, or the launch — and a repeated
+    source repeats its segment.  ``decay``: required for ``length=3``, refused for ``length=2``.  ``adj`` may be directed.
+    The cost is ``walks · length`` dependent row reads per source, whatever its degree.  Two host syncs, as the other builders."""
+    walks, length, decay, seed = _check_rw(walks, length, decay, seed)
+    known = adj if known is None else known
+    sources = _check_sources(adj, sources, known)
+    n = adj.size(0)
+    rpa, cola, rpk, colk = adj._rowptr, adj._col, known._rowptr, known._col
+    with ops.prevalidated(sources, sources, n, n):
+        count = ops.rw_visits_count(rpa, cola, rpk, colk, sources, walks, length, seed)
+        ptr = ops.scan_i32(count)
+        edges, val, visits = ops.rw_visits_fill(rpa, cola, rpk, colk, sources, walks, length, seed, ptr, decay)
+    return ptr, edges, val, visits
+
+
+def _rw_pass(adj: SparseTensor, sources: Tensor, rw: RandomWalks, known: Optional[SparseTensor],
+             targets: Optional[Tuple[Tensor, Tensor]] = None):
+    """``_path_index_pass`` for a random-walk stage: (``short``, ``rank``, ``count``) — the ``m`` most visited per source, the
+    place of every target among ALL visited candidates of its source by ``val`` (``ops.segment_rank``: 0 = not visited), the
+    visited candidates of every source."""
+    if not isinstance(rw, RandomWalks):
+        raise ValueError(f"rw must be a RandomWalks, got {rw!r}")
+    ptr, edges, val, _ = random_walk_candidates(adj, sources, rw.walks, rw.length, rw.decay, known, rw.seed)
+    rank = ops.segment_rank(val, ptr, edges, *targets)[0] if targets is not None else None
+    return _keep_m_best(ptr, edges, val, rw.m), rank, ptr[1:] - ptr[:-1]
+
+
+def random_walk_short_list(adj: SparseTensor, sources: Tensor, rw: RandomWalks,
+                           known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor]:
+    """The ``rw.m`` most visited candidates of every source: (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2]), the contract
+    of ``prefilter_candidates`` — the candidates of ``random_walk_candidates`` ranked by ``val`` in the total order of
+    ``segment_topk`` (ties, which integer counts make often, go to the lower node id), the first ``m`` kept and returned in
+    ASCENDING node id."""
+    return _rw_pass(adj, sources, rw, known)[0]
+
+
 def _check_prefilter(prefilter, k: int, hops: int = 2):
-    """(kind, m) for ``hops=2``, (kind, m, decay) for ``hops=3``: the other arity is refused."""
+    """(kind, m) for ``hops=2``, (kind, m, decay) for ``hops=3``: the other arity is refused.  A ``RandomWalks`` (checked when
+    it was made) passes as it is where it keeps at least ``k`` and walks ``hops`` steps."""
+    if isinstance(prefilter, RandomWalks):
+        if k > prefilter.m:
+            raise ValueError(f"prefilter keeps m = {prefilter.m} candidates per source, fewer than k = {k}")
+        if hops != prefilter.length:
+            raise ValueError(f"prefilter walks length = {prefilter.length} steps, hops = {hops}: the two must be equal")
+        return prefilter
     form = "(kind, m)" if hops == 2 else "(kind, m, decay) under hops=3,"
     if not isinstance(prefilter, (tuple, list)) or len(prefilter) != hops or not isinstance(prefilter[0], str) \
             or isinstance(prefilter[1], bool) or not isinstance(prefilter[1], int):
@@ -327,6 +432,9 @@ def _candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor
     """The candidate list of a request: the short list where ``prefilter`` (checked) is given, else every candidate within
     ``hops`` hops.  A segment of the top-k takes fewer than 2^32 - 1 entries, and so does the flat list.  Third: with a short
     list and ``targets``, the retrieval rank of every target (``_path_index_pass``), else None."""
+    if isinstance(prefilter, RandomWalks):
+        short, rank, _ = _rw_pass(adj, sources, prefilter, known, targets)
+        return short[0], short[1], rank
     if prefilter is not None:
         short, rank, _ = _path_index_pass(adj, sources, prefilter[0], prefilter[1], known, hops,
                                           None if hops == 2 else prefilter[2], None, targets)
@@ -424,7 +532,13 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     the one scoring call on the flat list; ValueError if that list has 2^32 - 1 entries or more.  Under a power law it is tens
     of times the 2-hop list, so the form to serve is ``hops=3`` with ``prefilter=(kind, m, decay)``: the short list is then
     taken over three hops by ``P₂ + decay · P₃`` (``prefilter_candidates(..., hops=3, decay=decay)``).  A 2-tuple with
-    ``hops=3`` or a 3-tuple with ``hops=2`` is refused.  cn6 is served over these <= 3 hops; its own evidence reaches four."""
+    ``hops=3`` or a 3-tuple with ``hops=2`` is refused.  cn6 is served over these <= 3 hops; its own evidence reaches four.
+
+    ``prefilter=RandomWalks(m, walks, length[, decay, seed])``: the short list is ``random_walk_short_list(adj, sources,
+    prefilter, known)`` — the ``m`` most visited nodes of ``walks`` random walks per source, at a cost that does not grow with
+    the neighbourhood — and the contract is the same sentence: the scores are exactly those the scoring loop returns for the
+    flat retained list at this ``batch_size``.  ``k <= m``; ``hops`` must equal ``length`` (ValueError otherwise).  The list is
+    a sample: a candidate no walk reached is not in it, however the model would have ranked it."""
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
