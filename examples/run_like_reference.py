@@ -17,6 +17,8 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32 --recommend-eval 200   # ... and where the test links rank
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-rw 32:256:2 --recommend-eval 200   # ... a short list from random walks instead
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-emb 32 --recommend-eval 200        # ... the nearest embeddings over ALL nodes instead
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-prefilter ra:32 --recommend-emb 32:cos --recommend-union --recommend-eval 200   # ... or the union of the two
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain 3       # ... and why: each link's top-3 common neighbours
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-explain-edges 10 # ... down to the edges: the 10 strongest messages
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5 --recommend-accept 3 --recommend-undo
@@ -43,7 +45,7 @@ from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic            
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
 from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
 from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
-from ocn_amd.recommend import (RandomWalks, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
+from ocn_amd.recommend import (EmbeddingNeighbours, RandomWalks, ShortListUnion, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import (negative_edges, negative_targets, two_hop_negative_edges,  # noqa: E402
@@ -178,6 +180,16 @@ def rw_name(rw):
     return f"random walks {rw.m}:{rw.walks}:{rw.length}" + (f":{rw.decay:g}" if rw.decay is not None else "")
 
 
+def prefilter_name(pf):
+    if isinstance(pf, RandomWalks):
+        return rw_name(pf)
+    if isinstance(pf, EmbeddingNeighbours):
+        return f"embedding {pf.m}" + (":cos" if pf.normalize else "")
+    if isinstance(pf, ShortListUnion):
+        return "union of " + " + ".join(prefilter_name(st) for st in pf.stages)
+    return ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in pf)
+
+
 @torch.no_grad()
 def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5):
     """--recommend K: the K best predicted new links of the first few test sources (ocn_amd.recommend), by the heuristic or by
@@ -191,6 +203,10 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     the prefilter is then KIND:M:DECAY and ranks them by the local path index P2 + DECAY * P3.
     --recommend-rw M:W:L[:DECAY]: the short list comes from W random walks of L steps per source instead (the M most visited nodes,
     ranked by c2 + DECAY * c3; ocn_amd.recommend.RandomWalks): a sample of the candidates at a cost that no hub source raises.
+    --recommend-emb M[:cos]: the short list is the M nodes nearest to the source's embedding by int8 inner product (cosine with
+    :cos), over ALL nodes (ocn_amd.recommend.EmbeddingNeighbours): a source without neighbours gets targets too.
+    --recommend-union: beside --recommend-prefilter or --recommend-rw, the model ranks the union of that short list and the
+    --recommend-emb one (ocn_amd.recommend.ShortListUnion).
     --recommend-eval Q: the held-out test links of the first Q distinct test sources are ranked among the candidates of the selected
     route (ocn_amd.ranking) and recall / NDCG / hit rate @K, MRR, coverage and retention are printed; with a prefilter the
     unfiltered run stands beside it.
@@ -250,7 +266,10 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             # trained model supports no claim about the quality of a prefilter
             full, _ = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, hops=args.recommend_hops)
             kept = int(((dst[:, :, None] == full[:, None, :]) & (full[:, None, :] >= 0)).any(1).sum())
-            if isinstance(args.recommend_prefilter, RandomWalks):
+            if isinstance(args.recommend_prefilter, (EmbeddingNeighbours, ShortListUnion)):
+                n_all = n_short = None                       # (an embedding list is not a subset of the candidates within the hops)
+                name = prefilter_name(args.recommend_prefilter)
+            elif isinstance(args.recommend_prefilter, RandomWalks):
                 n_all = int((three_hop_candidates(adj, sources) if args.recommend_hops == 3 else two_hop_candidates(adj, adj2, sources))[0][-1])
                 n_short = int(random_walk_short_list(adj, sources, args.recommend_prefilter)[0][-1])
                 name = rw_name(args.recommend_prefilter)
@@ -264,8 +283,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
                 n_all = int(two_hop_candidates(adj, adj2, sources)[0][-1])
                 n_short = int(prefilter_candidates(adj, sources, kind, m)[0][-1])
                 name = f"{kind}:{m}"
-            print(f"prefilter {name} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links "
-                  f"(the model ranked {n_short} of {n_all} candidates)", flush=True)
+            print(f"prefilter {name} kept {kept} of the {int((full >= 0).sum())} unfiltered top-{k} links"
+                  + (f" (the model ranked {n_short} of {n_all} candidates)" if n_all is not None else ""), flush=True)
     if args.recommend_eval:
         # --recommend-eval Q: where the held-out test links land in the ranking served above (ocn_amd.ranking).  The first Q distinct
         # test sources; truth = the test edges, both ways, on the graph the candidates come from.  Printed only: a synthetic graph
@@ -289,8 +308,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             h = state.h if state is not None else model(data.x, adj)
             route = f"{args.predictor} over {args.recommend_hops} hops" + (" (walk route)" if adj2 is None else "")
             if args.recommend_prefilter:
-                show(route + " prefilter " + (rw_name(args.recommend_prefilter) if isinstance(args.recommend_prefilter, RandomWalks) else
-                                              ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in args.recommend_prefilter)),
+                show(route + " prefilter " + prefilter_name(args.recommend_prefilter),
                      rank_links(predictor, h, adj, adj2, first, truth, args.testbs, args, prefilter=args.recommend_prefilter,
                                 hops=args.recommend_hops))
             show(route + (" unfiltered" if args.recommend_prefilter else ""),
@@ -414,6 +432,13 @@ def main(argv=None):
                     help="with --recommend and a model, instead of --recommend-prefilter: short-list the M most visited nodes of W "
                          "random walks of L = --recommend-hops steps per source (ocn_amd.recommend.RandomWalks; DECAY with L = 3) and "
                          "let the model rank only those; with --recommend-eval, coverage reads 'visited at all'")
+    ap.add_argument("--recommend-emb", default=None, metavar="M[:cos]",
+                    help="with --recommend and a model: short-list the M nodes nearest to the source's embedding by exact int8 inner "
+                         "product over ALL nodes (ocn_amd.recommend.EmbeddingNeighbours; ':cos' normalises the rows first) and let the "
+                         "model rank only those; alone, or with --recommend-union beside another short list")
+    ap.add_argument("--recommend-union", action="store_true",
+                    help="with --recommend-emb and one of --recommend-prefilter / --recommend-rw: the model ranks the per-source union "
+                         "of the two short lists (ocn_amd.recommend.ShortListUnion); with --recommend-eval, coverage reads 'in the union'")
     ap.add_argument("--recommend-eval", type=int, default=0, metavar="Q",
                     help="with --recommend: rank the held-out test links of the first Q distinct test sources among the candidates of "
                          "the selected route (ocn_amd.ranking) and print recall / NDCG / hit rate @K, MRR, coverage and, with "
@@ -486,6 +511,24 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"--recommend-rw M:W:L[:DECAY]: {e}")
         args.recommend_prefilter = rw            # (one short list per request: the calls below pass it as prefilter=)
+    if args.recommend_union and not (args.recommend_emb and args.recommend_prefilter):
+        ap.error("--recommend-union: needs --recommend-emb and one of --recommend-prefilter / --recommend-rw")
+    if args.recommend_emb:
+        if args.heuristic or not args.recommend:
+            ap.error("--recommend-emb M[:cos]: needs a model and --recommend K")
+        if args.recommend_prefilter and not args.recommend_union:
+            ap.error("--recommend-emb beside another short list: give --recommend-union to rank their union")
+        parts = args.recommend_emb.split(":")
+        try:
+            if not 1 <= len(parts) <= 2 or (len(parts) == 2 and parts[1] != "cos"):
+                raise ValueError("M, or M:cos")
+            emb = EmbeddingNeighbours(int(parts[0]), normalize=len(parts) == 2)
+            if args.recommend > max(emb.m, 0 if not args.recommend_union else
+                                    (args.recommend_prefilter.m if isinstance(args.recommend_prefilter, RandomWalks) else args.recommend_prefilter[1])):
+                raise ValueError(f"M = {emb.m} is fewer than K = {args.recommend}")
+        except ValueError as e:
+            ap.error(f"--recommend-emb M[:cos]: {e}")
+        args.recommend_prefilter = ShortListUnion(args.recommend_prefilter, emb) if args.recommend_union else emb
     dev = torch.device("cuda:0")
     evaluator = Evaluator(name='ogbl-ppa' if args.dataset in ("cora", "citeseer", "pubmed") else f'ogbl-{args.dataset}')
     data, split_edge = loaddataset_like(args.dataset, args.use_valedges_as_input, scale=args.scale, feat=args.feat)

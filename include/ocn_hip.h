@@ -57,7 +57,9 @@ extern "C" {
  *    dense-dense product on the pattern of an encoder operator: the gradient of a layer with respect to its messages);
  *    ocn_cn_gather_pair_min_batch (the H = 256 pooling takes two slots per wave at large batches; same bits);
  *    ocn_rw_max_walks, ocn_rw_visits_count, ocn_rw_visits_fill (random-walk retrieval: a source's candidates and their visit
- *    counts from W walks of 2 or 3 steps, at a cost that does not depend on its degree). */
+ *    counts from W walks of 2 or 3 steps, at a cost that does not depend on its degree); ocn_mips_max_m, ocn_mips_h_align,
+ *    ocn_mips_workspace_bytes, ocn_mips_topm_i8 (embedding retrieval: the m largest int8 inner products of every query over all
+ *    nodes, exact, on the integer matrix cores — a short list that is not bound to the graph neighbourhood). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -653,6 +655,46 @@ int ocn_rw_visits_fill(const int64_t* rowptrA, const int32_t* colA, const int64_
                        const int64_t* sources, int64_t Q, int32_t walks, int32_t length, uint64_t seed,
                        const int64_t* ptr /* [Q + 1] */, float decay, int64_t* edges /* [ptr[Q]][2] */, float* val /* [ptr[Q]] */,
                        int32_t* visits /* [ptr[Q]][2] */, void* stream);
+
+/* Embedding retrieval: for every query the m nodes with the largest inner product against it, over ALL nodes — brute force,
+ * exact, without a [Q][N] score matrix.  The other retrieval stages are graph-local (a target beyond three hops is never
+ * proposed, a source without neighbours gets nothing); this one reads the embeddings alone ("Embedding
+ * retrieval").
+ *
+ * query int8 [Q][H], keys int8 [N][H] (row-major, 16-byte aligned, operands expected in [-127, 127]: -128 is not validated),
+ * kscale fp32 [N].  dot[q][n] = sum_f query[q][f] * keys[n][f] in int32 on v_mfma_i32_32x32x32_i8, exact: H <= 1024, so
+ * |dot| <= 1024 * 127^2 < 2^24.  val[q][n] = (float)dot[q][n] * kscale[n] — the conversion is exact, the one fp32 multiply is the
+ * only rounding.  H must be a positive multiple of ocn_mips_h_align() (64) — zero padding changes no dot product.
+ * Eligibility: with rows [Q] (the node id of every query, a source may repeat), node n is eligible for query q unless
+ * drop_self != 0 and n == rows[q], or colM is given and n is in row rows[q] of M (CSR over the N nodes, sorted duplicate-free
+ * int32 columns, as for ocn_row_diff_*; a rows[q] outside [0, N) has no row of M and excludes nothing).  Without rows every
+ * node is eligible and drop_self is not read.
+ * Order: the eligible nodes of a query in the total order of ocn_segment_topk with the NODE ID as the position — the higher val
+ * first, +0.0 == -0.0, equal values to the lower node id, NaN (a kscale that is not finite) after every number.  top_val [Q][m] /
+ * top_node [Q][m] are the first m, best first, padded with -inf / -1 where fewer than m nodes are eligible, 1 <= m <=
+ * ocn_mips_max_m() (= ocn_segment_topk_max_k()).  top_val is the value as ordered: a -0.0 is returned as +0.0.
+ * A wave owns 32 queries (the B operand, fragments in registers for H = 64, 128, 256) and keeps their sorted lists of m 64-bit
+ * keys in LDS; the four waves of a workgroup stream the same contiguous slice of the key range, 32 keys (the A operand) at a
+ * time.  An accumulator tile is converted, scaled and tested against the m-th best of its query — one compare per element where
+ * nothing passes; the few that pass are checked for eligibility (a binary search in the row of M) and inserted, one round trip
+ * to LDS each.  n_split slices
+ * (0 = chosen from Q, N and m to fill the device; no more slices than there are 32-key tiles) leave partial lists in the
+ * workspace, which a second kernel merges per query in the same order.  Keys are distinct, so the output is fixed by the inputs
+ * alone: not by n_split, the grid, the tile shape or the other queries.  No float atomics, no allocation, no host sync, no
+ * global state.  workspace: ocn_mips_workspace_bytes(Q, N, m, n_split) bytes (-1 for arguments the entry refuses), 8-byte
+ * aligned, any content.
+ * NULL query / keys / kscale / top_val / top_node / workspace, Q < 0, N outside 1 .. 2^31 - 1, H no positive multiple of
+ * ocn_mips_h_align() or above 1024, m outside 1 .. ocn_mips_max_m(), n_split < 0, rowptrM without colM or the reverse, M
+ * without rows, a query, keys or kscale that is not 16-byte aligned, a workspace that is not 8-byte aligned: OCN_EINVAL before
+ * any HIP call.  Q == 0 returns 0 (after the checks). */
+int32_t ocn_mips_max_m(void);
+int32_t ocn_mips_h_align(void);
+int64_t ocn_mips_workspace_bytes(int64_t Q, int64_t N, int32_t m, int32_t n_split);
+int ocn_mips_topm_i8(const int8_t* query /* [Q][H] */, const int8_t* keys /* [N][H] */, const float* kscale /* [N] */,
+                     int64_t Q, int64_t N, int32_t H, const int64_t* rows /* [Q] source ids, or NULL */,
+                     const int64_t* rowptrM, const int32_t* colM /* exclusion CSR, or both NULL */, int32_t drop_self,
+                     int32_t m, int32_t n_split /* 0 = auto */, float* top_val /* [Q][m] */, int64_t* top_node /* [Q][m] */,
+                     void* workspace, void* stream);
 
 /* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the

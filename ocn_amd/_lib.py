@@ -89,6 +89,10 @@ SIGNATURES = {
     "ocn_rw_visits_count": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int32, ctypes.c_uint64, _P, _P]),
     "ocn_rw_visits_fill": (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, c_int32, ctypes.c_uint64, _P, c_float, _P, _P,
                                      _P, _P]),
+    "ocn_mips_max_m": (c_int32, []),
+    "ocn_mips_h_align": (c_int32, []),
+    "ocn_mips_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    "ocn_mips_topm_i8": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "ocn_gather_schedule": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "ocn_cn_gather_pair_min_batch": (c_int64, [c_int64]),
     "ocn_coo_to_csr_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),

@@ -9,6 +9,7 @@
 // column range at a time (ocn_two_hop_diff_count / ocn_two_hop_diff_fill).
 #include "common.h"
 #include "window_sweep.h"
+#include "topk_key.h"
 
 // ---------------------------------------------------------------------------------------------
 // row difference P[s,:] \ M[s,:]
@@ -209,25 +210,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void two_hop_sums_kernel(
 // ---------------------------------------------------------------------------------------------
 // segmented top-k
 // ---------------------------------------------------------------------------------------------
-constexpr int TOPK_MAX = 2 * OCN_WAVE;                       // two slots per lane
 constexpr int TOPK_AHEAD = 4;                                // chunks of 64 scores loaded ahead of their tests
-
-// The order of the contract as ONE unsigned comparison (larger = better): the high word is the score's monotone image —
-// -0.0 is folded onto +0.0 first, every NaN goes to 0, below -inf (0x007fffff) — the low word is ~(position in the segment),
-// so that among equal scores (and among NaNs) the lower position wins.  A segment has fewer than 2^32 - 1 entries: no entry
-// has the key 0, which marks an empty slot.
-__device__ __forceinline__ u64 topk_key(float x, unsigned rel) {
-  unsigned b = __float_as_uint(x);
-  if (b == 0x80000000u) b = 0u;
-  unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  if (x != x) u = 0u;
-  return ((u64)u << 32) | (u64)(0xffffffffu - rel);
-}
-
-__device__ __forceinline__ u64 topk_shfl_up1(u64 v) {
-  const unsigned lo = __shfl_up((unsigned)v, 1, OCN_WAVE), hi = __shfl_up((unsigned)(v >> 32), 1, OCN_WAVE);
-  return ((u64)hi << 32) | lo;
-}
 
 // A wave keeps the best keys of its segment sorted, best first, across its lanes: slot j lives in lane j & 63, register
 // j >> 6 (NS registers: one for k <= 64, two up to 128).  The segment is consumed 64 scores at a time; a chunk none of whose

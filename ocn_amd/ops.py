@@ -1283,6 +1283,111 @@ def rw_visits_fill(rowptrA: Tensor, colA: Tensor, rowptrM: Tensor, colM: Tensor,
     return edges, val, visits
 
 
+def mips_max_m() -> int:
+    """The largest ``m`` of ``mips_topm_i8`` (ocn_hip.h: ocn_mips_max_m) — ``segment_topk_max_k()``."""
+    return int(_lib.lib().ocn_mips_max_m())
+
+
+def mips_h_align() -> int:
+    """The width of ``mips_topm_i8`` operands is a multiple of this (ocn_hip.h: ocn_mips_h_align): the K step of the int8 MFMA
+    pair.  ``quantize_rows_i8`` pads to it."""
+    return int(_lib.lib().ocn_mips_h_align())
+
+
+MIPS_H_MAX = 1024                # include/ocn_hip.h, ocn_mips_topm_i8: |dot| <= 1024 * 127^2 < 2^24 stays exact in fp32
+
+
+def quantize_rows_i8(x: Tensor, normalize: bool = False) -> Tuple[Tensor, Tensor]:
+    """Symmetric per-row int8 quantisation of an fp32 matrix ``x`` [R, H], in plain torch on ``x``'s device: (``q`` int8
+    [R, Hp], ``scale`` float32 [R]) with ``q * scale[:, None]`` ~ ``x``.  ``normalize``: every row is divided by its L2 norm
+    first (cosine retrieval; an all-zero row stays zero).  ``scale = amax(|row|) / 127`` (1 for an all-zero row), ``q =
+    clamp(round(x / scale), -127, 127)`` — ``|x - q * scale| <= scale / 2`` up to the rounding of the division.  ``Hp`` is ``H``
+    padded with zeros up to a multiple of ``mips_h_align()``: padding changes no dot product.  A non-finite ``x`` raises
+    ValueError (one host sync)."""
+    if not isinstance(x, Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("x must be a float32 [R, H] matrix")
+    R, H = x.shape
+    if H < 1:
+        raise ValueError("x must have at least one column")
+    if R and not bool(torch.isfinite(x).all()):
+        raise ValueError("x holds values that are not finite: they have no int8 image")
+    if normalize:
+        nrm = torch.linalg.vector_norm(x, dim=1, keepdim=True)
+        x = x / torch.where(nrm > 0, nrm, torch.ones_like(nrm))
+    amax = x.abs().amax(dim=1) if R else x.new_zeros(0)
+    scale = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.round(x / scale[:, None]).clamp_(-127, 127).to(torch.int8)
+    align = mips_h_align()
+    Hp = (H + align - 1) // align * align
+    if Hp != H:
+        q = torch.nn.functional.pad(q, (0, Hp - H))
+    return q.contiguous(), scale.contiguous()
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    """``t``, or a copy where its storage offset leaves it off a 16-byte boundary (the kernel reads 16 bytes at a time)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+@_on_device
+def mips_topm_i8(query_q: Tensor, keys_q: Tensor, kscale: Tensor, m: int, rows: Optional[Tensor] = None,
+                 excl: Optional[Tuple[Tensor, Tensor]] = None, drop_self: bool = True, n_split: int = 0,
+                 wsd=None) -> Tuple[Tensor, Tensor]:
+    """For every query the ``m`` nodes with the largest ``float32(dot) * kscale[n]`` (ocn_hip.h: ocn_mips_topm_i8): (``val``
+    float32 [Q, m], ``node`` int64 [Q, m]), best first, padded with -inf / -1.  ``query_q`` int8 [Q, H], ``keys_q`` int8
+    [N, H], ``kscale`` float32 [N] — ``quantize_rows_i8`` makes them; ``dot`` is the exact int32 inner product, the multiply
+    the only rounding.  ``rows`` int64 [Q]: the node id of every query; then ``drop_self`` excludes it and ``excl`` =
+    (rowptr int64 [N + 1], col int32), a CSR with sorted duplicate-free columns, excludes the nodes of its row.  Without ``rows``
+    every node is eligible.  Order: higher value first, +0.0 == -0.0, equal values to the lower node id.  ``n_split`` (0 = auto)
+    slices the key range over workgroups; the result does not depend on it."""
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= mips_max_m():
+        raise ValueError(f"m must be in 1..{mips_max_m()}, got {m!r}")
+    if isinstance(n_split, bool) or not isinstance(n_split, int) or n_split < 0:
+        raise ValueError(f"n_split must be an int >= 0 (0 = automatic), got {n_split!r}")
+    _req(query_q, torch.int8, "query_q", 2); _req(keys_q, torch.int8, "keys_q", 2); _req(kscale, torch.float32, "kscale", 1)
+    Q, H = query_q.shape
+    N = keys_q.shape[0]
+    if keys_q.shape[1] != H:
+        raise ValueError(f"query_q has {H} columns, keys_q {keys_q.shape[1]}")
+    if H < 1 or H % mips_h_align() or H > MIPS_H_MAX:
+        raise ValueError(f"the width must be a multiple of {mips_h_align()} up to {MIPS_H_MAX}, got {H} (quantize_rows_i8 pads)")
+    if not 0 < N < (1 << 31):
+        raise ValueError(f"keys_q has {N} rows: node ids serve 1 .. 2^31 - 1")
+    if kscale.numel() != N:
+        raise ValueError(f"kscale: one scale per key ({N}), got {kscale.numel()}")
+    rp = col = None
+    if rows is None:
+        if excl is not None:
+            raise ValueError("excl needs rows: the exclusion is the row of a query's node id")
+    else:
+        if _req(rows, torch.int64, "rows", 1).numel() != Q:
+            raise ValueError(f"rows: one node id per query ({Q}), got {rows.numel()}")
+        check_edges(rows, rows, N, N)
+        if excl is not None:
+            rp, col = excl
+            _req(rp, torch.int64, "excl rowptr", 1); _req(col, torch.int32, "excl col", 1)
+            if rp.numel() != N + 1:
+                raise ValueError(f"excl has {rp.numel() - 1} rows, the keys {N}")
+            if not col.numel():
+                col = torch.zeros(1, dtype=torch.int32, device=col.device)
+    dev = query_q.device
+    for name, t in (("keys_q", keys_q), ("kscale", kscale), ("rows", rows), ("excl rowptr", rp), ("excl col", col)):
+        if t is not None and t.device != dev:            # (rows is a keyword and excl a tuple: _on_device does not see them)
+            raise RuntimeError(f"mips_topm_i8: {name} is on {t.device}, query_q on {dev}")
+    val = torch.empty(Q, m, dtype=torch.float32, device=dev)
+    node = torch.empty(Q, m, dtype=torch.int64, device=dev)
+    if Q:
+        nbytes = int(_lib.lib().ocn_mips_workspace_bytes(Q, N, m, n_split))
+        if nbytes < 0:
+            raise _lib.OcnHipError("ocn_mips_workspace_bytes refused its arguments")
+        ws = buf(wsd, "mips_ws", (nbytes + 7) // 8, torch.int64, dev)
+        qa, ka, sa = _aligned16(query_q), _aligned16(keys_q), _aligned16(kscale)
+        check(_lib.lib().ocn_mips_topm_i8(ptr(qa), ptr(ka), ptr(sa), Q, N, H, ptr(rows), ptr(rp), ptr(col), 1 if drop_self else 0,
+                                          m, n_split, ptr(val), ptr(node), ptr(ws), stream_ptr()), "ocn_mips_topm_i8")
+        _mark("mips_topm_i8", 2.0 * Q * N * H)
+    return val, node
+
+
 CLASS_RANGES = 7                 # include/ocn_hip.h: OCN_CLASS_RANGES
 R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES)
 

@@ -12,6 +12,8 @@ order of ``recommend``:
 * with a short list (``prefilter``) the same kernel ranks the targets by the short-list heuristic among ALL candidates, inside the
   retrieval pass — under ``hops=3`` chunk by chunk, before a chunk is reduced to its ``m`` best — so a miss is told apart: not a
   candidate, dropped by the short list, or ranked;
+* an embedding short list (``recommend.EmbeddingNeighbours``) ranks the targets among ALL eligible nodes by an independent torch
+  restatement of the int8 order; a ``recommend.ShortListUnion`` has no single order and reports membership only;
 * ``rank_path_index`` is that retrieval stage alone, without a model: the cheap way to sweep ``kind``, ``decay`` and ``m``;
 * ``ranking_metrics`` turns a result into the usual figures.
 
@@ -111,7 +113,18 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     all the candidates within ``hops`` — taken in the retrieval pass itself, chunk by chunk under ``hops=3``.
 
     ``prefilter=recommend.RandomWalks(...)``: ``retrieval_rank`` is the place by the walks' ``val`` among all VISITED candidates
-    of the source, before the cut to ``m`` — 0 means that no walk reached the target (or that it is no candidate at all)."""
+    of the source, before the cut to ``m`` — 0 means that no walk reached the target (or that it is no candidate at all).
+
+    ``prefilter=recommend.EmbeddingNeighbours(...)``: ``retrieval_rank`` is the place of every target among ALL eligible nodes
+    of its source — every node but the source and its row of ``known`` — in the stage's order, ``float32(dot) * kscale`` with
+    ties to the lower id (``recommend.embedding_retrieval_rank``: an independent restatement in plain torch on the device —
+    chunks of queries, a float64 matmul of the int8 matrices, a count of the keys that precede; the arithmetic is exact
+    integers, so it is the kernel's order).  ``rank > 0`` exactly when ``1 <= retrieval_rank <= m``.  Evaluation only: the
+    restatement forms [chunk, N] matrices.
+
+    ``prefilter=recommend.ShortListUnion(...)``: a union has no single retrieval order — ``retrieval_rank`` and ``m`` are None,
+    ``rank > 0`` exactly for the targets in the union, and that membership is what ``ranking_metrics`` reports as
+    ``coverage`` (no ``retention``)."""
     if predictor.training:
         raise RuntimeError("rank_links is the eval path; call predictor.eval() first")
     hops, prefilter = R._check_request(predictor, adj2, 1, prefilter, hops)
@@ -119,8 +132,7 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     ptr, edges, scores, rrank = R._score_request(predictor, h, adj, adj2, sources, batch_size, args, known, run_ahead, prefilter,
                                                  hops, targets if prefilter is not None else None)
     rank, _ = ops.segment_rank(scores, ptr, edges, *targets)
-    return RankResult(sources, targets[0], targets[1], ptr[1:] - ptr[:-1], rank, rrank,
-                      None if prefilter is None else (prefilter.m if isinstance(prefilter, R.RandomWalks) else prefilter[1]))
+    return RankResult(sources, targets[0], targets[1], ptr[1:] - ptr[:-1], rank, rrank, R._prefilter_m(prefilter))
 
 
 @torch.no_grad()

@@ -29,7 +29,13 @@ made and return a flat score vector.  This module makes the pairs and picks from
   dependent row reads whatever its degree, and their visit counts estimate the "ra" path index: ``E[c₂(t)] / W = RA(s, t) /
   deg s``, ``E[c₃(t)] / W = P₃(s, t) / deg s`` (``random_walk_candidates``, ``ops.rw_visits_count`` / ``_fill``).
   ``random_walk_short_list`` keeps the ``m`` most visited and ``prefilter=RandomWalks(m, walks, length[, decay, seed])`` lets the
-  model rank only those.  A sample, not the exact list: ``ranking.rank_links`` measures what it keeps.  Opt-in.
+  model rank only those.  A sample, not the exact list: ``ranking.rank_links`` measures what it keeps.  Opt-in;
+* embedding retrieval: every stage above is graph-local — a target beyond three hops is never proposed and a source without
+  neighbours gets nothing — while the model scores any pair.  ``EmbeddingIndex`` quantises the node embeddings to int8 once,
+  ``embedding_candidates`` takes, per source, the ``m`` nodes with the largest inner product over ALL nodes
+  (``ops.mips_topm_i8``: an exact int8 GEMM on the matrix cores whose epilogue keeps ``m`` keys per query — no [Q, N] matrix),
+  ``prefilter=EmbeddingNeighbours(m)`` lets the model rank those, and ``prefilter=ShortListUnion(...)`` the per-source union
+  of several stages' lists: graph evidence where there is some, embeddings for the cold sources.  Opt-in.
 
 Everything runs on one GPU; dealing the sources over several is not built here.
 """
@@ -408,9 +414,232 @@ def random_walk_short_list(adj: SparseTensor, sources: Tensor, rw: RandomWalks,
     return _rw_pass(adj, sources, rw, known)[0]
 
 
+# ---------------------------------------------------------------------------------------------
+# embedding retrieval
+# ---------------------------------------------------------------------------------------------
+class EmbeddingIndex:
+    """The int8 image of a node-embedding matrix, made once: ``keys_q`` int8 [N, Hp] and ``kscale`` float32 [N] of
+    ``ops.quantize_rows_i8(keys, normalize)`` (``Hp``: the width ``H`` padded to ``ops.mips_h_align()``), with ``n = N``,
+    ``width = H`` and ``normalize`` (rows scaled to unit L2 norm first: cosine retrieval).  A plain object of two tensors and
+    three Python values: ``torch.save`` stores it, ``to(device)`` moves it.  Quantisation is one pass over [N, H]: after
+    ``insert_edges`` and a refresh of ``h`` the index is simply made again."""
+
+    def __init__(self, keys: Tensor, normalize: bool = False):
+        if not isinstance(normalize, bool):
+            raise ValueError(f"normalize must be a bool, got {normalize!r}")
+        if not isinstance(keys, Tensor) or keys.dim() != 2 or keys.dtype != torch.float32:
+            raise ValueError("keys must be a float32 [N, H] matrix of node embeddings")
+        if keys.shape[0] < 1 or keys.shape[1] < 1 or keys.shape[1] > ops.MIPS_H_MAX:
+            raise ValueError(f"keys must have at least one row and 1..{ops.MIPS_H_MAX} columns, got {tuple(keys.shape)}")
+        self.n, self.width, self.normalize = int(keys.shape[0]), int(keys.shape[1]), normalize
+        self.keys_q, self.kscale = ops.quantize_rows_i8(keys.detach(), normalize)
+
+    def to(self, device) -> "EmbeddingIndex":
+        other = object.__new__(EmbeddingIndex)
+        other.n, other.width, other.normalize = self.n, self.width, self.normalize
+        other.keys_q, other.kscale = self.keys_q.to(device), self.kscale.to(device)
+        return other
+
+
+def _check_queries(index: EmbeddingIndex, queries: Tensor, sources: Tensor, known: Optional[SparseTensor]) -> Tensor:
+    if not isinstance(index, EmbeddingIndex):
+        raise ValueError(f"index must be an EmbeddingIndex, got {type(index).__name__}")
+    if not isinstance(sources, Tensor) or sources.dim() != 1 or sources.dtype != torch.int64:
+        raise ValueError("sources must be a 1-d int64 tensor of node ids")
+    if not isinstance(queries, Tensor) or queries.dim() != 2 or queries.dtype != torch.float32 or \
+            tuple(queries.shape) != (sources.numel(), index.width):
+        raise ValueError(f"queries must be float32 [{sources.numel()}, {index.width}]: one row of the index's width per source")
+    if known is not None and tuple(known.sparse_sizes()) != (index.n, index.n):
+        raise ValueError(f"known is {tuple(known.sparse_sizes())}, expected the square size ({index.n}, {index.n}) of the index")
+    return sources.contiguous()
+
+
+def embedding_candidates(index: EmbeddingIndex, queries: Tensor, sources: Tensor, m: int,
+                         known: Optional[SparseTensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The ``m`` nearest nodes of every source by inner product, over ALL nodes of the index: (``ptr`` int64 [Q + 1], ``edges``
+    int64 [T, 2], ``val`` float32 [T]) in the layout of ``path_scored_candidates``.  ``queries`` float32 [Q, H] — for instance
+    ``h[sources]`` — are quantised per call as the index was (``ops.quantize_rows_i8`` with the index's ``normalize``); source
+    ``q`` is offered every node but ``sources[q]`` itself and, with ``known`` (a square ``SparseTensor`` of the index's size;
+    default: no further exclusion — the recommendation paths pass ``adj``), the nodes of its row there.  The eligible nodes are
+    ranked by ``val = float32(dot) * kscale[node]`` — ``dot`` the exact int32 inner product of the int8 rows, the multiply the
+    only rounding (``ops.mips_topm_i8``) — in the total order of ``segment_topk`` with the node id as the position (higher
+    first, ties to the lower id); the first ``m`` are kept (all where fewer are eligible) and returned in ASCENDING node id, as
+    every short list is.  ``val`` is the kernel's value: ``val * qscale[q]``, with ``qscale`` the query's own quantisation
+    scale, approximates the inner product ``<queries[q], keys[node]>`` (the cosine under ``normalize``); a source's order does
+    not need that factor, so it is not applied.  Quantising the retrieval stage is the usual trade: the model re-ranks the list
+    in fp32.  ``1 <= m <= ops.mips_max_m()``.  One host sync for the sources' bounds, one for the output size."""
+    m = _check_m(m)
+    sources = _check_queries(index, queries, sources, known)
+    qq, _ = ops.quantize_rows_i8(queries, index.normalize)
+    val, node = ops.mips_topm_i8(qq, index.keys_q, index.kscale, m, rows=sources,
+                                 excl=None if known is None else (known._rowptr, known._col), drop_self=True)
+    Q = sources.numel()
+    have = node >= 0
+    ptr = torch.zeros(Q + 1, dtype=torch.int64, device=sources.device)
+    torch.cumsum(have.sum(1), 0, out=ptr[1:])
+    big = torch.iinfo(torch.int64).max
+    ids, at = torch.where(have, node, torch.full_like(node, big)).sort(dim=1)          # ascending id, the pads last
+    keep = ids < big
+    dst = ids[keep]
+    src = sources[:, None].expand(Q, m)[keep]
+    return ptr, torch.stack([src, dst], 1), val.gather(1, at)[keep]
+
+
+def embedding_retrieval_rank(index: EmbeddingIndex, queries: Tensor, sources: Tensor, known: Optional[SparseTensor],
+                             tptr: Tensor, tnode: Tensor, chunk_elems: int = 1 << 24) -> Tensor:
+    """The place of given nodes in the order ``embedding_candidates`` cuts: rank int64 [P], 1 + the eligible nodes that precede
+    target ``tnode[j]`` of its source, 0 where the target is not eligible (the source itself, in ``known``, no node id).  An
+    independent restatement in plain torch on the device — the kernel is not called: the integer dot products are exact, so a
+    float64 matmul of the int8 matrices, ``float32(dot) * kscale`` and a count of the keys that precede give the kernel's order.
+    Chunks of queries (and of targets) of about ``chunk_elems`` matrix entries; evaluation only."""
+    sources = _check_queries(index, queries, sources, known)
+    n, dev, Q, P = index.n, sources.device, sources.numel(), tnode.numel()
+    ops.check_edges(sources, sources, n, n)
+    rank = torch.zeros(P, dtype=torch.int64, device=dev)
+    if not (Q and P):
+        return rank
+    qq, _ = ops.quantize_rows_i8(queries, index.normalize)
+    kd = index.keys_q.double()
+    ids = torch.arange(n, device=dev)
+    tp = tptr.tolist()
+    step = max(1, int(chunk_elems) // n)
+    for a in range(0, Q, step):
+        b = min(Q, a + step)
+        if tp[b] == tp[a]:
+            continue
+        val = (qq[a:b].double() @ kd.t()).float() * index.kscale[None, :]
+        elig = torch.ones(b - a, n, dtype=torch.bool, device=dev)
+        elig[torch.arange(b - a, device=dev), sources[a:b]] = False
+        if known is not None:
+            rp, col = known._rowptr, known._col
+            start = rp[sources[a:b]]
+            cnt = rp[sources[a:b] + 1] - start
+            seg = torch.repeat_interleave(torch.arange(b - a, device=dev), cnt)
+            first = torch.cumsum(cnt, 0) - cnt
+            at = torch.arange(seg.numel(), device=dev) - first[seg] + start[seg]
+            elig[seg, col[at].long()] = False
+        counts = (tptr[a + 1:b + 1] - tptr[a:b])
+        tq = torch.repeat_interleave(torch.arange(b - a, device=dev), counts)
+        for c in range(tp[a], tp[b], step):
+            d = min(tp[b], c + step)
+            ql, t = tq[c - tp[a]:d - tp[a]], tnode[c:d]
+            ok = (t >= 0) & (t < n)
+            tc = t.clamp(0, n - 1)
+            ok &= elig[ql, tc]
+            tv = val[ql, tc][:, None]
+            rows_v = val[ql]
+            ahead = ((rows_v > tv) | ((rows_v == tv) & (ids[None, :] < tc[:, None]))) & elig[ql]
+            rank[c:d] = torch.where(ok, ahead.sum(1) + 1, torch.zeros_like(tc))
+    return rank
+
+
+@dataclass(frozen=True, eq=False)
+class EmbeddingNeighbours:
+    """An embedding retrieval stage, a ``prefilter`` of ``recommend_links`` / ``ranking.rank_links``: per source the ``m``
+    nodes with the largest int8 inner product against its embedding, over all nodes (``embedding_candidates``).  ``keys``:
+    None — the ``h`` given to the call is quantised per call — or a float32 [N, H] matrix, or a ready ``EmbeddingIndex`` (what a
+    caller who serves many requests passes; its ``normalize`` must be this stage's).  The queries are ``h[sources]`` either
+    way.  Checked on construction: ``1 <= m <= ops.mips_max_m()``, ``normalize`` a bool.  ``hops`` is not read by this stage."""
+    m: int
+    normalize: bool = False
+    keys: Optional[object] = None
+
+    def __post_init__(self):
+        if isinstance(self.m, bool) or not isinstance(self.m, int):
+            raise ValueError(f"m must be an int, got {self.m!r}")
+        _check_m(self.m)
+        if not isinstance(self.normalize, bool):
+            raise ValueError(f"normalize must be a bool, got {self.normalize!r}")
+        k = self.keys
+        if isinstance(k, EmbeddingIndex):
+            if k.normalize != self.normalize:
+                raise ValueError(f"keys was indexed with normalize = {k.normalize}, the stage asks for {self.normalize}")
+        elif k is not None and not (isinstance(k, Tensor) and k.dim() == 2 and k.dtype == torch.float32):
+            raise ValueError("keys must be None, a float32 [N, H] matrix or an EmbeddingIndex")
+
+
+class ShortListUnion:
+    """A ``prefilter`` whose short list is, per source, the union (ascending, duplicate-free) of the short lists of its
+    ``stages``: each a ``(kind, m[, decay])`` tuple (``prefilter_candidates``; the arity goes with ``hops``), a ``RandomWalks``
+    (its ``length`` must equal ``hops``) or an ``EmbeddingNeighbours``.  What a mixed request needs: graph evidence where there
+    is some, embeddings for the cold sources.  A source's list holds at most the sum of the stages' ``m``; ``k`` may be at most
+    the largest ``m``.  There is no single retrieval order: ``ranking.rank_links`` reports ``retrieval_rank`` and ``m`` as None,
+    and membership in the union is what ``coverage`` reads."""
+
+    def __init__(self, *stages):
+        if not stages:
+            raise ValueError("ShortListUnion needs at least one stage")
+        for st in stages:
+            if not isinstance(st, (tuple, list, RandomWalks, EmbeddingNeighbours)):
+                raise ValueError(f"a stage must be a (kind, m[, decay]) tuple, a RandomWalks or an EmbeddingNeighbours, got {st!r}")
+        self.stages = tuple(tuple(st) if isinstance(st, list) else st for st in stages)
+
+    def __repr__(self):
+        return f"ShortListUnion{self.stages!r}"
+
+
+def _stage_m(stage) -> int:
+    return stage.m if isinstance(stage, (RandomWalks, EmbeddingNeighbours)) else stage[1]
+
+
+def _prefilter_m(prefilter) -> Optional[int]:
+    """The ``m`` a checked ``prefilter`` cuts at; None without one and for a union (no single cut)."""
+    return None if prefilter is None or isinstance(prefilter, ShortListUnion) else _stage_m(prefilter)
+
+
+def _emb_pass(stage: EmbeddingNeighbours, h: Optional[Tensor], adj: SparseTensor, sources: Tensor, known: Optional[SparseTensor],
+              targets: Optional[Tuple[Tensor, Tensor]] = None):
+    """``_path_index_pass`` for an embedding stage: (``short``, ``rank``, ``count``) — the ``m`` nearest per source, the place of
+    every target among ALL eligible nodes of its source (``embedding_retrieval_rank``), the length of every short list."""
+    if h is None:
+        raise ValueError("an EmbeddingNeighbours stage needs the node embeddings h")
+    known = adj if known is None else known
+    sources = _check_sources(adj, sources, known)
+    n = adj.size(0)
+    if not isinstance(h, Tensor) or h.dim() != 2 or h.shape[0] != n:
+        raise ValueError(f"h must be the [{n}, H] node embeddings of adj")
+    index = stage.keys if isinstance(stage.keys, EmbeddingIndex) else \
+        EmbeddingIndex((h if stage.keys is None else stage.keys).float(), stage.normalize)
+    if index.n != n:
+        raise ValueError(f"the stage's keys hold {index.n} nodes, adj {n}")
+    ops.check_edges(sources, sources, n, n)                  # (before h is indexed)
+    queries = h.detach()[sources].float()
+    ptr, edges, _ = embedding_candidates(index, queries, sources, stage.m, known)
+    rank = embedding_retrieval_rank(index, queries, sources, known, *targets) if targets is not None else None
+    return (ptr, edges), rank, ptr[1:] - ptr[:-1]
+
+
+def _union_pass(union: ShortListUnion, h: Optional[Tensor], adj: SparseTensor, sources: Tensor, known: Optional[SparseTensor],
+                hops: int) -> Tuple[Tensor, Tensor]:
+    """The per-source union of the stages' short lists, formed with ``ops.csr_union`` on their (``ptr``, ids) pairs."""
+    ptr = ids = None
+    for st in union.stages:
+        if isinstance(st, RandomWalks):
+            p, e = _rw_pass(adj, sources, st, known)[0]
+        elif isinstance(st, EmbeddingNeighbours):
+            p, e = _emb_pass(st, h, adj, sources, known)[0]
+        else:
+            p, e = _path_index_pass(adj, sources, st[0], st[1], known, hops, None if hops == 2 else st[2], None)[0]
+        c = e[:, 1].to(torch.int32).contiguous()
+        ptr, ids = (p.contiguous(), c) if ptr is None else ops.csr_union(ptr, ids, p.contiguous(), c)
+    src = torch.repeat_interleave(sources, ptr[1:] - ptr[:-1], output_size=ids.numel())
+    return ptr, torch.stack([src, ids.long()], 1)
+
+
 def _check_prefilter(prefilter, k: int, hops: int = 2):
     """(kind, m) for ``hops=2``, (kind, m, decay) for ``hops=3``: the other arity is refused.  A ``RandomWalks`` (checked when
-    it was made) passes as it is where it keeps at least ``k`` and walks ``hops`` steps."""
+    it was made) passes as it is where it keeps at least ``k`` and walks ``hops`` steps, an ``EmbeddingNeighbours`` where it
+    keeps at least ``k``; the stages of a ``ShortListUnion`` are checked one by one and the largest ``m`` must reach ``k``."""
+    if isinstance(prefilter, EmbeddingNeighbours):
+        if k > prefilter.m:
+            raise ValueError(f"prefilter keeps m = {prefilter.m} candidates per source, fewer than k = {k}")
+        return prefilter
+    if isinstance(prefilter, ShortListUnion):
+        stages = tuple(_check_prefilter(st, 1, hops) for st in prefilter.stages)
+        top = max(_stage_m(st) for st in stages)
+        if k > top:
+            raise ValueError(f"prefilter keeps m = {top} candidates per source in its largest stage, fewer than k = {k}")
+        return ShortListUnion(*stages)
     if isinstance(prefilter, RandomWalks):
         if k > prefilter.m:
             raise ValueError(f"prefilter keeps m = {prefilter.m} candidates per source, fewer than k = {k}")
@@ -428,10 +657,17 @@ def _check_prefilter(prefilter, k: int, hops: int = 2):
 
 
 def _candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, known: Optional[SparseTensor], hops: int,
-                prefilter, targets: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+                prefilter, targets: Optional[Tuple[Tensor, Tensor]] = None,
+                h: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
     """The candidate list of a request: the short list where ``prefilter`` (checked) is given, else every candidate within
     ``hops`` hops.  A segment of the top-k takes fewer than 2^32 - 1 entries, and so does the flat list.  Third: with a short
-    list and ``targets``, the retrieval rank of every target (``_path_index_pass``), else None."""
+    list and ``targets``, the retrieval rank of every target (``_path_index_pass``), else None — and None under a
+    ``ShortListUnion``, which has no single retrieval order.  ``h``: the node embeddings, read by the embedding stages only."""
+    if isinstance(prefilter, EmbeddingNeighbours):
+        short, rank, _ = _emb_pass(prefilter, h, adj, sources, known, targets)
+        return short[0], short[1], rank
+    if isinstance(prefilter, ShortListUnion):
+        return (*_union_pass(prefilter, h, adj, sources, known, hops), None)
     if isinstance(prefilter, RandomWalks):
         short, rank, _ = _rw_pass(adj, sources, prefilter, known, targets)
         return short[0], short[1], rank
@@ -482,7 +718,7 @@ def _score_request(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spars
     (``ptr``, ``edges``, ``scores``, the retrieval rank of ``targets`` under a short list or None).  ``hops`` and ``prefilter``
     come from ``_check_request``."""
     from .pipeline import score_edges, score_edges_walk
-    ptr, edges, rank = _candidates(adj, adj2, sources, known, hops, prefilter, targets)
+    ptr, edges, rank = _candidates(adj, adj2, sources, known, hops, prefilter, targets, h)
     if adj2 is None:
         scores = score_edges_walk(predictor, h, adj, edges, batch_size, args, run_ahead)
     else:
@@ -538,7 +774,18 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     prefilter, known)`` — the ``m`` most visited nodes of ``walks`` random walks per source, at a cost that does not grow with
     the neighbourhood — and the contract is the same sentence: the scores are exactly those the scoring loop returns for the
     flat retained list at this ``batch_size``.  ``k <= m``; ``hops`` must equal ``length`` (ValueError otherwise).  The list is
-    a sample: a candidate no walk reached is not in it, however the model would have ranked it."""
+    a sample: a candidate no walk reached is not in it, however the model would have ranked it.
+
+    ``prefilter=EmbeddingNeighbours(m[, normalize, keys])``: the short list is ``embedding_candidates`` over ``keys`` (default:
+    this call's ``h``, quantised per call; a caller who serves many requests passes ``keys=EmbeddingIndex(...)``) with ``queries
+    = h[sources]`` and ``known`` as given (default ``adj``) — the ``m`` nodes nearest to the source's embedding among ALL nodes,
+    whatever their distance in the graph, so a source without neighbours gets ``k`` targets too.  The contract is the same
+    sentence: the scores are exactly those the scoring loop returns for the flat retained list at this ``batch_size``.
+    ``k <= m``; ``hops`` is not read by this stage.
+
+    ``prefilter=ShortListUnion(stage, ...)``: the short list is the per-source union (ascending, duplicate-free) of the stages'
+    short lists — tuples, ``RandomWalks`` and ``EmbeddingNeighbours``, each checked as above for this ``hops`` — and the
+    contract is the same sentence again.  ``k`` may be at most the largest ``m`` of the stages."""
     if predictor.training:
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
