@@ -59,7 +59,9 @@ extern "C" {
  *    ocn_rw_max_walks, ocn_rw_visits_count, ocn_rw_visits_fill (random-walk retrieval: a source's candidates and their visit
  *    counts from W walks of 2 or 3 steps, at a cost that does not depend on its degree); ocn_mips_max_m, ocn_mips_h_align,
  *    ocn_mips_workspace_bytes, ocn_mips_topm_i8 (embedding retrieval: the m largest int8 inner products of every query over all
- *    nodes, exact, on the integer matrix cores — a short list that is not bound to the graph neighbourhood). */
+ *    nodes, exact, on the integer matrix cores — a short list that is not bound to the graph neighbourhood);
+ *    ocn_cn_flags_cover (the intersection pass with a certificate that T2 is the full A·A of a symmetric A: candidates that are
+ *    stored entries of A read no T2; same bits). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -197,6 +199,22 @@ int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA,
                      int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
                      uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
                      int32_t* status, uint64_t* rec /* [B][4] */, int32_t* gcost /* [ceil(B/4)] or NULL */, void* stream);
+/* Either of the two (rec_in != 0: ocn_cn_flags_rec) with a certificate on T2.  t2_cover != 0 is the caller's word that T2 —
+ * bit rows and CSR alike — is the FULL pattern of A·A and that A (rowptrA / colA, rows sorted) equals its transpose.  Then a
+ * candidate (i, j) that is a stored entry of A has every neighbour k of i in T2 row j (the wedge j - i - k), and its cn2
+ * flags are set without reading T2: no probe, no search.  Whether j is in N(i) is read off the source row the slot loads
+ * anyway (rows of up to 4096 entries; longer ones read T2 as before).  Every output is what t2_cover == 0 leaves whenever
+ * the certificate is true; a false one yields cn2 flags T2 does not hold.  Ignored without T2. */
+int ocn_cn_flags_cover(const int64_t* rowptrA, const int32_t* colA,
+                       const int64_t* rowptrT1, const int32_t* colT1,
+                       const int64_t* rowptrT2, const int32_t* colT2,
+                       const uint32_t* bitmapT1 /* or NULL */, int64_t bm1_stride_words,
+                       const uint32_t* bitmapT2 /* or NULL */, int64_t bm_stride_words,
+                       const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
+                       int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
+                       uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
+                       int32_t* status, uint64_t* rec /* [B][4] or NULL */, int32_t* gcost /* [ceil(B/4)] or NULL */,
+                       int32_t rec_in, int32_t t2_cover, void* stream);
 
 /* The pygho route get_cn1_cn2 (NeighborOverlap_large_ppa.py:147-173, NeighborOverlapCitation2.py:
  * 78-104) without forming Ej·A: cn1 = N(i) ∩ N(j) as above; cn2[e,k] = |N(k) ∩ N(j)| (number of

@@ -61,6 +61,13 @@ __device__ __forceinline__ bool lanes_have(int32_t t, int32_t key) {
 // when the partner's row sits in registers (or needs none), its own half when it fits there, and is searched in memory
 // otherwise.  A workgroup is then NS schedule groups (SCHED_GROUP slots = GPB / NS waves each).  Every output is what NS = 1
 // writes.
+// cover (wave-uniform): T2 is certified as the full pattern of A·A for a symmetric A (ocn_hip.h: ocn_cn_flags_cover).  A candidate
+// (i, j) that is a stored entry of A then has every k of N(i) in T2 row j through the wedge j - i - k: the slot behaves as a
+// full row does (t2_full) — no probe, no search, f2 = in.  Whether j is in N(i) is found beside loads the slot makes anyway: a
+// source row of one chunk answers it with a ballot over the chunk just loaded; a longer one, up to COVER_MAX_ROW entries, with
+// a two-level search of the sorted row (64 samples, then the one segment of at most 64) whose loads fly beside the record's
+// follow-up and the target row's and are back before chunk 0's probes would go out.  Longer rows probe as without it.
+#define COVER_MAX_ROW 4096
 template <bool HAS_T2, bool LH, bool RECIN, int NS>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     const i64* __restrict__ src, const i64* __restrict__ dst, const i64* __restrict__ order, i64 B,
     i64 n_cols, const i64* __restrict__ off, uint8_t* __restrict__ flags, i64 cap,
     u64* __restrict__ hist, int32_t* __restrict__ cnt1, int32_t* __restrict__ cnt2,
-    int32_t* __restrict__ status, u64* rec, int32_t* __restrict__ gcost) {
+    int32_t* __restrict__ status, u64* rec, int32_t* __restrict__ gcost, int cover) {
   constexpr int GPB = OCN_WPB, SPB = GPB * NS;                  // waves, slots per workgroup
   constexpr int T1_PART = T1_CAP / NS, T2_PART = OCN_WAVE / NS;  // a slot's share of its wave's slices when both slots need them
   static_assert(NS == 1 || (NS == 2 && !LH), "slot pairs: large-graph forms only");
@@ -140,6 +147,16 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
         }
         if (void_batch) { da[s] = 0; db[s] = 0; dc[s] = 0; base[s] = 0; }
       }
+    // certified T2: the 64-point sample of a long source row, for the search of j in it (a pair of one source shares it)
+    const bool same = NS > 1 && i[0] == i[NS - 1];   // one source (wave-uniform): one row of A, one chunk load, one histogram add
+    bool seek[NS], skip2[NS];                 // j is looked for in the long row N(i); the slot's cn2 flags are known without T2
+    int32_t smp[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      seek[s] = HAS_T2 && cover && da[s] > OCN_WAVE && da[s] <= COVER_MAX_ROW;
+      smp[s] = 0x7fffffff;
+      if (seek[s]) smp[s] = (s > 0 && same) ? smp[0] : colA[a0[s] + (((i64)gl * da[s]) >> 6)];
+    }
     // the target row: up to 64 entries stay in the wave's registers, one per lane; a longer one, up to T1_CAP (NS = 2: while
     // the partner's sits in registers, else up to T1_PART in the slot's own part), goes to this wave's LDS slice; beyond that
     // the search runs in memory
@@ -161,6 +178,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
     for (int s = 0; s < NS; ++s) {
       const int o = (s + 1) % NS;
       t2_full[s] = HAS_T2 && rowptrT2 && dc[s] == n_cols;   // a full row (dense A², e.g. ddi) contains every column
+      skip2[s] = t2_full[s];
       const bool whole2 = NS == 1 || (HAS_T2 && rowptrT2 && dc[o] == n_cols) || dc[o] == 0;
       t2_lds[s] = whole2 || dc[s] <= T2_PART;
       t2_at[s] = whole2 ? 0 : s * T2_PART;
@@ -169,6 +187,18 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
         else if (gl < dc[s]) s_t2[g][t2_at[s] + gl] = colT2[c0[s] + gl];
       }
     }
+    // ... and the one segment of the row that can hold j: samples <= j number the segment (the row is sorted, its sample
+    // positions (l * da) >> 6 strictly ascending for da > 64), at most ceil(da / 64) <= 64 entries, inside the row
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      if (seek[s]) {
+        const int nle = __popcll(__ballot(smp[s] <= (int32_t)j[s]));
+        if (nle > 0) {
+          const i64 q0 = ((i64)(nle - 1) * da[s]) >> 6, q1 = ((i64)nle * da[s]) >> 6;
+          const int32_t v = q0 + gl < q1 ? colA[a0[s] + q0 + gl] : -1;
+          skip2[s] = skip2[s] || __ballot(v == (int32_t)j[s]) != 0;
+        }
+      }
     wave_lds_sync();
     bool fits[NS];
     int c1[NS], c2[NS];
@@ -179,7 +209,6 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
       c1[s] = c2[s] = 0;
       if (s > 0 && da[s] > da_max) da_max = da[s];
     }
-    const bool same = NS > 1 && i[0] == i[NS - 1];   // one source (wave-uniform): one row of A, one chunk load, one histogram add
     for (i64 p0 = 0; p0 < da_max; p0 += OCN_WAVE) {      // (wave-uniform trips: lanes_have needs every lane)
       const i64 p = p0 + gl;
       bool in[NS], f1[NS], f2[NS];
@@ -191,10 +220,15 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
         if (s > 0 && same) k[s] = k[0];       // (unused where !in[s]: an empty partner of the same source id)
         else k[s] = in[s] ? colA[a0[s] + p] : 0;
       }
+      if (HAS_T2 && cover && p0 == 0) {        // a source row of one chunk: is j in the chunk just loaded?
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+          if (da[s] <= OCN_WAVE) skip2[s] = skip2[s] || __ballot(in[s] && k[s] == (int32_t)j[s]) != 0;
+      }
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         w2[s] = 0;
-        if (HAS_T2 && bmT2 && !t2_full[s] && in[s]) w2[s] = bm_row[s][k[s] >> 5];    // one probe, in flight while the cn1 search runs
+        if (HAS_T2 && bmT2 && !skip2[s] && in[s]) w2[s] = bm_row[s][k[s] >> 5];    // one probe, in flight while the cn1 search runs
       }
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
@@ -206,7 +240,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
       for (int s = 0; s < NS; ++s) {
         f2[s] = false;
         if (HAS_T2 && in[s]) {
-          if (t2_full[s]) f2[s] = true;
+          if (skip2[s]) f2[s] = true;
           else if (bmT2) f2[s] = (w2[s] >> (k[s] & 31)) & 1u;
           else if (!t2_lds[s]) f2[s] = sorted_has(colT2 + c0[s], dc[s], k[s]);
           else f2[s] = dc[s] > OCN_WAVE ? sampled_has(&s_t2[g][0], colT2 + c0[s], dc[s], k[s]) : sorted_has(&s_t2[g][t2_at[s]], dc[s], k[s]);
@@ -300,7 +334,7 @@ static int cn_flags_launch(const int64_t* rowptrA, const int32_t* colA, const in
                            const uint32_t* bitmapT1, int64_t bm1_stride_words, const uint32_t* bitmapT2, int64_t bm_stride_words,
                            const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
                            int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap, uint64_t* hist,
-                           int32_t* cnt1, int32_t* cnt2, int32_t* status, uint64_t* rec, int32_t* gcost, bool rec_in, void* stream) {
+                           int32_t* cnt1, int32_t* cnt2, int32_t* status, uint64_t* rec, int32_t* gcost, bool rec_in, bool cover, void* stream) {
   if (B < 0 || flags_cap < 0 || B > (int64_t)HF_MASK) return OCN_EINVAL;
   if (B == 0) return 0;
   if (!rowptrA || (!rowptrT1 && !bitmapT1) || !src || !dst || !off || !hist || !cnt1 || !status) return OCN_EINVAL;
@@ -334,7 +368,7 @@ static int cn_flags_launch(const int64_t* rowptrA, const int32_t* colA, const in
   (const i64*)rowptrA, colA, (const i64*)rowptrT1, colT1, (const i64*)(T2P), (T2C),                   \
       (const unsigned*)bitmapT1, (i64)bm1_stride_words, (const unsigned*)bitmapT2, (i64)bm_stride_words, (const i64*)src, \
       (const i64*)dst, (const i64*)order, (i64)B, (i64)n_cols, (const i64*)off, flags, (i64)flags_cap, \
-      (u64*)hist, cnt1, cnt2, status, (u64*)rec, gcost
+      (u64*)hist, cnt1, cnt2, status, (u64*)rec, gcost, (int)cover
 #define CN_FLAGS_LAUNCH(T2, LHV, RI, NSV, T2P, T2C)                                                   \
   hipLaunchKernelGGL((cn_flags_kernel<T2, LHV, RI, NSV>), dim3(grid), dim3(OCN_BLOCK), (LHV) ? lds : 0, st, CN_FLAGS_ARGS(T2P, T2C))
 #define CN_FLAGS_PICK(T2, T2P, T2C)                                                                   \
@@ -358,7 +392,7 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* row
                  int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap, uint64_t* hist,
                  int32_t* cnt1, int32_t* cnt2, int32_t* status, uint64_t* rec, int32_t* gcost, void* stream) {
   return cn_flags_launch(rowptrA, colA, rowptrT1, colT1, rowptrT2, colT2, bitmapT1, bm1_stride_words, bitmapT2, bm_stride_words,
-                         src, dst, order, B, n_cols, off, flags, flags_cap, hist, cnt1, cnt2, status, rec, gcost, false, stream);
+                         src, dst, order, B, n_cols, off, flags, flags_cap, hist, cnt1, cnt2, status, rec, gcost, false, false, stream);
 }
 
 int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT1,
@@ -368,7 +402,19 @@ int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA, const int64_t*
                      int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap, uint64_t* hist,
                      int32_t* cnt1, int32_t* cnt2, int32_t* status, uint64_t* rec, int32_t* gcost, void* stream) {
   return cn_flags_launch(rowptrA, colA, rowptrT1, colT1, rowptrT2, colT2, bitmapT1, bm1_stride_words, bitmapT2, bm_stride_words,
-                         src, dst, order, B, n_cols, off, flags, flags_cap, hist, cnt1, cnt2, status, rec, gcost, true, stream);
+                         src, dst, order, B, n_cols, off, flags, flags_cap, hist, cnt1, cnt2, status, rec, gcost, true, false, stream);
+}
+
+int ocn_cn_flags_cover(const int64_t* rowptrA, const int32_t* colA, const int64_t* rowptrT1,
+                       const int32_t* colT1, const int64_t* rowptrT2, const int32_t* colT2,
+                       const uint32_t* bitmapT1, int64_t bm1_stride_words, const uint32_t* bitmapT2, int64_t bm_stride_words,
+                       const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
+                       int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap, uint64_t* hist,
+                       int32_t* cnt1, int32_t* cnt2, int32_t* status, uint64_t* rec, int32_t* gcost, int32_t rec_in,
+                       int32_t t2_cover, void* stream) {
+  return cn_flags_launch(rowptrA, colA, rowptrT1, colT1, rowptrT2, colT2, bitmapT1, bm1_stride_words, bitmapT2, bm_stride_words,
+                         src, dst, order, B, n_cols, off, flags, flags_cap, hist, cnt1, cnt2, status, rec, gcost, rec_in != 0,
+                         t2_cover != 0 && (rowptrT2 || bitmapT2), stream);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@ walk_two_sided = True            # walk route: sweep each candidate from its che
 walk_share_min = 2               # walk route, B <= 4096: candidates sharing a source are swept together from this group size on (0 = never)
 sort_edges_min_batch = 4096      # batches at least this large are processed in src order (L2 reuse of shared rows)
 heavy_first = os.environ.get("OCN_HEAVY_FIRST", "1") != "0"   # ... and the pooling (H = 256) visits its slot groups longest first (ocn_cn_flags' gcost -> ocn_gather_schedule)
+t2_cover = os.environ.get("OCN_T2_COVER", "1") != "0"         # intersection pass: a T2 certified as the full A·A of a symmetric A is not read for candidates that are stored entries of A (ocn_cn_flags_cover; same bits)
 sched_segment = int(os.environ.get("OCN_SCHED_SEG", 0))        # ... inside segments of this many groups of an XCD's eighth (0 = the whole eighth)
 overlap_depth = int(os.environ.get("OCN_OVERLAP_DEPTH", 4))   # scratch sets of a predictor = the most batches a scoring loop keeps in flight (round 4: four, with the pooling in phase A)
 overlap_depth_small = int(os.environ.get("OCN_OVERLAP_DEPTH_SMALL", 8))   # ... and for batches of at most overlap_small_batch candidates (the drivers' 2 048: latency chains, not bandwidth — citation2 shape 5.58 -> 5.83 M edges/s, ppa unchanged)
@@ -331,12 +332,15 @@ def _cn_operands(rowptrA, colA, t1, t2, bm1, bm2, src, dst, order, B: int, n_col
 def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
              t2: Optional[Tuple[Tensor, Tensor]], src: Tensor, dst: Tensor, n_cols: int, max_deg_a: int,
              walk: bool = False, t2_bitmap: Optional[Tensor] = None, wsd=None, nds: Optional[Tensor] = None,
-             t1_bitmap: Optional[Tensor] = None, rec: Optional[Tensor] = None, sched: Optional[Tensor] = None):
+             t1_bitmap: Optional[Tensor] = None, rec: Optional[Tensor] = None, sched: Optional[Tensor] = None,
+             t2_certified: bool = False):
     """Intersection pass.  ``walk=False``: flags of N(src) against the rows of dst in t1 (and t2).
     ``walk=True``: the pygho route on A itself (t1/t2 ignored): cn1 flags + walk counts; with ``nds``
     (``neighbor_degree_sum`` of A) every batch row is swept from its cheaper endpoint.
     ``rec`` (int64 [B, 4], pattern route): receives the per-slot records ``cn_gather`` reads instead of walking
     order -> src / dst / off / counts -> rowptr.
+    ``t2_certified``: t2 is the complete pattern of A·A and A equals its transpose (``SparseTensor.covers``: the caller's
+    word, not checked here) — with ``ops.t2_cover`` on, candidates that are stored entries of A then read no T2; same outputs.
     Returns (order|None, off, flags, wc|None, hist[N,2] int64 packed, cnt1, cnt2|None, status, scal) — ``scal``
     is the zeroed int32[4] statistics scratch the weights stage of the same batch uses."""
     dev = src.device
@@ -407,9 +411,10 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
                                            ptr(wc), cap, ptr(hist), ptr(cnt1), ptr(cnt2), ptr(status),
                                            stream_ptr()), "ocn_cn_walk_flags")
     else:
-        check((_lib.lib().ocn_cn_flags_rec if rec_in else _lib.lib().ocn_cn_flags)(
+        check(_lib.lib().ocn_cn_flags_cover(
             *_cn_operands(rowptrA, colA, csr1, csr2, t1_bitmap, t2_bitmap, src, dst, order, B, n_cols), ptr(off), ptr(flags), cap,
-            ptr(hist), ptr(cnt1), ptr(cnt2), ptr(status), ptr(rec), ptr(sched), stream_ptr()), "ocn_cn_flags")
+            ptr(hist), ptr(cnt1), ptr(cnt2), ptr(status), ptr(rec), ptr(sched), int(rec_in),
+            int(bool(t2_certified) and has_t2 and t2_cover), stream_ptr()), "ocn_cn_flags")
     _mark("cn_flags")
     return order, off, flags, wc, hist, cnt1, cnt2, status, scal
 

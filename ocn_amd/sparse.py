@@ -44,6 +44,12 @@ class _Storage:
 
 
 class SparseTensor:
+    # The certificate of a second operand (``covers``): the adjacency this matrix is the COMPLETE product ``A @ A`` of — set by
+    # the routes of this library that form such a product, by nothing else, and never for a product with rows on demand — and
+    # whether this matrix equals its transpose (None: not established yet).
+    _square_of: Optional["SparseTensor"] = None
+    _symmetric: Optional[bool] = None
+
     def __new__(cls, row=None, rowptr=None, col=None, value=None, sparse_sizes=None, *a, **k):
         # `torch_sparse.SparseTensor(row=row1, col=col1, value=value1, sparse_sizes=(B, N))` at the end of the pygho drivers'
         # get_cn1_cn2 (NeighborOverlap_large_ppa.py:170-171) on the deferred vectors of shims/pygho: the handle itself
@@ -321,6 +327,25 @@ class SparseTensor:
             return self._bitmap
         return self.product_bit_rows()
 
+    def is_symmetric(self) -> bool:
+        """Whether the pattern equals its transpose: established once per matrix (``to_symmetric`` sets it; else the CSR is
+        compared with ``t()``'s — one host sync) and cached.  Never assumed."""
+        if self._symmetric is None:
+            if self._sizes[0] != self._sizes[1]:
+                self._symmetric = False
+            else:
+                at = self.t()
+                self._symmetric = bool(torch.equal(self._rowptr, at._rowptr) and torch.equal(self._col, at._col))
+        return self._symmetric
+
+    def covers(self, adj: "SparseTensor") -> bool:
+        """The certificate the intersection pass acts on (``ops.cn_flags`` ``t2_certified``): this matrix is the complete
+        product of that very ``adj`` object with itself, and ``adj`` equals its transpose.  Every neighbour of ``i`` is then
+        in row ``j`` of this matrix for each stored entry ``(i, j)`` of ``adj``.  A matrix built from arrays or from a torch
+        tensor, a product with rows on demand, an updated product and A³ never are."""
+        return (self._square_of is not None and self._square_of is adj and not self.rows_on_demand()
+                and adj.is_symmetric())
+
     def rows_on_demand(self) -> bool:
         """A product none of whose matrix-level data exists yet (see ``_lazy_product``)."""
         return getattr(self, "_lazy", None) is not None
@@ -338,6 +363,8 @@ class SparseTensor:
             self.neighbor_degree_sum()
         else:
             self.bit_rows()
+            if ops.t2_cover and self._rowptr.is_cuda:
+                self.is_symmetric()                         # (its one host sync: here, not in a batch on a side stream)
 
     # ---- device movement ---------------------------------------------------------------
     def to_device(self, device, non_blocking: bool = False) -> "SparseTensor":
@@ -388,10 +415,13 @@ class SparseTensor:
         if self._value is None and self._col.is_cuda and self._sizes[0] == self._sizes[1]:
             # NeighborOverlap_large.py:63: transposed entries join, duplicates leave — one pass of ocn_coo_to_csr
             rowptr, col = ops.coo_to_csr(r, c, self._sizes[0], self._sizes[1], symmetrize=True, dedupe=True, check_range=False)
-            return SparseTensor(rowptr=rowptr, col=col, sparse_sizes=self._sizes)
-        v = None if self._value is None else torch.cat([self._value, self._value])
-        return SparseTensor(row=torch.cat([r, c]), col=torch.cat([c, r]), value=v,
-                            sparse_sizes=self._sizes, trust_data=True).coalesce(reduce)
+            out = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=self._sizes)
+        else:
+            v = None if self._value is None else torch.cat([self._value, self._value])
+            out = SparseTensor(row=torch.cat([r, c]), col=torch.cat([c, r]), value=v,
+                               sparse_sizes=self._sizes, trust_data=True).coalesce(reduce)
+        out._symmetric = self._sizes[0] == self._sizes[1]
+        return out
 
     def t(self) -> "SparseTensor":
         """Transpose (cached): CSR of Aᵀ with the values carried along — the operator of the SpMM
@@ -503,6 +533,8 @@ class CooView:
             out._bitmap = bitmap               # dense bit rows of the product, probed by the intersection kernel
         if bitmap is not None:
             out._published("bitmap")
+        if a is b:
+            out._square_of = a                 # the complete A @ A of this very object (SparseTensor.covers)
         return CooView(out, is_product=True)
 
     def to_torch(self) -> Tensor:

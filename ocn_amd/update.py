@@ -65,6 +65,7 @@ def _check_args(fn: str, adj: SparseTensor, edges: Tensor, adj2: Optional[Sparse
 def _retire(adj2: SparseTensor) -> None:
     """A donated A² gives up everything it held: any later use fails instead of reading updated bits through a stale thunk."""
     adj2._lazy = adj2._done = None
+    adj2._square_of = None                                   # (and is no longer anybody's certified product)
     adj2._rowptr_v = None
     adj2._col_v = adj2._col_thunk = None
     adj2._bitmap = None

@@ -136,11 +136,13 @@ class CNState(_BatchState):
         if t2 is not None and not walk:
             bm2 = t2.probed_bit_rows(self.dst, row_lengths=True)
             csr2 = (t2.rowptr_formed(), t2._col if (t2.col_materialized() or bm2 is None) else None)
+        # ... and whether T2 is certified as the complete A·A of this symmetric adjacency: stored candidates then read no T2
+        certified = bool(csr2 is not None and ops.t2_cover and t2.covers(adj))
         (self.order, self.off, self.flags, self.wc, self.hist, self.cnt1, self.cnt2, self.status, self.scal) = ops.cn_flags(
             adj._rowptr, adj._col, None if walk else (t1._rowptr, t1._col), csr2, self.src, self.dst, self.N,
             adj.max_rowcount(), walk=walk, t2_bitmap=bm2, wsd=ws,
             nds=adj.neighbor_degree_sum() if (walk and ops.walk_two_sided) else None,
-            t1_bitmap=None if walk else t1.bit_rows(), rec=self.rec, sched=self.sched)
+            t1_bitmap=None if walk else t1.bit_rows(), rec=self.rec, sched=self.sched, t2_certified=certified)
         self._hist_live = True
 
     @classmethod
@@ -564,6 +566,7 @@ def block_matrix_multiply(spadj: SparseTensor, block_size: int, fold_quirk: bool
         if not fold_quirk:
             out._bitmap = bits                   # dense bit rows of A²: one probe per membership test in the intersection
             out._published("bitmap")
+            out._square_of = spadj               # the offset-correct, complete A @ A of this very object (SparseTensor.covers)
         return out
     if fold_quirk:
         raise NotImplementedError("fold_quirk needs the dense block route (n <= ops.dense_adj2_max_nodes, block_size % 32 == 0)")
