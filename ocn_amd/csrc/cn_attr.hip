@@ -4,31 +4,26 @@
 // <g1[e], xcn1[e]> and <g2[e], xcn2[e]>, where xcn1 / xcn2 are what ocn_cn_gather pools with the same flags and table.
 // The entry weights are entry_weights() of common.h and the fetch rule is the pooling's (h[k] is read exactly when wa != 0 or
 // wb != 0).  No atomics, no workspace, no LDS.  See include/ocn_hip.h (ocn_cn_attribution).
-#include "common.h"
+#include "lane_group.h"
 
 constexpr int ATTR_UNR = 4;   // embedding rows in flight per lane group
 
-// The lane-group shape of cn_pool_frozen_kernel: LPE lanes cooperate on one candidate (64 / LPE candidates per wave), a lane owns
-// NV float4 of the H = LPE * NV * 4 features and keeps its part of g1[e] and g2[e] in registers for the whole row.  A round
-// covers LPE * PT positions of the source row: every lane reads the flag byte, the column id and the walk count of its own
-// positions and forms their (wa, wb).  The entries to fetch are walked by the ballot, four embedding rows in flight; every lane
-// forms its partial dots over its own features (ascending, one fused multiply-add each), the group sums them with an xor
-// butterfly — every lane ends with the same bits, and the order of the additions depends on (LPE, NV), that is on H, only —
-// and the lane that owns the position keeps the result.  After the round every lane stores its own positions.  A hub row only
-// takes more rounds.
+// The lane-group walk of lane_group.h; a lane keeps its part of g1[e] and g2[e] in registers for the whole row.  A round covers
+// LPE * PT positions of the source row: every lane reads the flag byte, the column id and the walk count of its own positions
+// and forms their (wa, wb).  For every entry that is fetched, every lane forms its partial dots over its own features (ascending,
+// one fused multiply-add each), the group sums them with an xor butterfly — every lane ends with the same bits, and the order
+// of the additions depends on (LPE, NV), that is on H, only — and the lane that owns the position keeps the result.  After the
+// round every lane stores its own positions.  A hub row only takes more rounds.
 template <int LPE, int NV>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_attr_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA, const i64* __restrict__ src,
     const i64* __restrict__ order, i64 B, const i64* __restrict__ off, const uint8_t* __restrict__ flags,
     const int32_t* __restrict__ wc, i64 flags_cap, const float4* __restrict__ weights, const float* __restrict__ h, int H,
     const float* __restrict__ g1, const float* __restrict__ g2, float2* __restrict__ attr, float* __restrict__ rank) {
-  constexpr int GPW = OCN_WAVE / LPE;
-  constexpr int PT = GPW < 8 ? GPW : 8;
-  const int lane = threadIdx.x & 63;
-  const int gl = lane % LPE;
-  const int gbase = lane - gl;
-  const i64 bid = xcd_block();
-  const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  constexpr int PT = lane_group<LPE>::PT;
+  const lane_group<LPE> g;
+  const int gl = g.gl, gbase = g.gbase;
+  const i64 slot = g.slot(xcd_block());
   if (slot >= B) return;                    // whole group leaves together
   const i64 e = order ? order[slot] : slot;
   const i64 i = src[e];
@@ -70,25 +65,16 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_attr_kernel(
 #pragma unroll
     for (int t = 0; t < PT; ++t) {
       const bool need = (wa[t] != 0.f) | (wb[t] != 0.f);
-      unsigned long long m = __ballot(need);
-      if (LPE < 64) m = (m >> gbase) & ((1ull << (LPE & 63)) - 1ull);
+      unsigned long long m = lane_group_mask<LPE>(need, gbase);
       while (m) {
         int bsel[ATTR_UNR];
-#pragma unroll
-        for (int u = 0; u < ATTR_UNR; ++u) {
-          bsel[u] = m ? (__ffsll((long long)m) - 1) : -1;
-          m &= m - 1;                          // no-op once m == 0
-        }
+        lane_group_take(m, bsel);
         float4 x[ATTR_UNR][NV];
 #pragma unroll
         for (int u = 0; u < ATTR_UNR; ++u) {
-          const int sl = gbase + (bsel[u] < 0 ? 0 : bsel[u]);
+          const int sl = lane_group_src(gbase, bsel[u]);
           const int32_t kk = __shfl(k[t], sl, OCN_WAVE);
-          if (bsel[u] >= 0) {
-            const float4* row = h4 + (i64)kk * rowq + gl;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
-          }
+          lane_group_row<LPE>(bsel[u], kk, h4, rowq, gl, x[u]);
         }
 #pragma unroll
         for (int u = 0; u < ATTR_UNR; ++u) {
@@ -135,20 +121,17 @@ int ocn_cn_attribution(const int64_t* rowptrA, const int32_t* colA, const int64_
                        const int64_t* off, const uint8_t* flags, const int32_t* wc, int64_t flags_cap, const float* weights,
                        const float* h, int32_t H, const float* g1, const float* g2, float* attr, float* rank, void* stream) {
   if (B < 0 || flags_cap < 0) return OCN_EINVAL;
-  if (H != 16 && H != 32 && H != 64 && H != 128 && H != 256 && H != 512) return OCN_EINVAL;
+  if (!lane_group_width(H)) return OCN_EINVAL;
   if (!rowptrA || !colA || !src || !off || !flags || !weights || !h || !g1 || !g2 || !attr || !rank) return OCN_EINVAL;
   if ((((uintptr_t)weights | (uintptr_t)h | (uintptr_t)g1 | (uintptr_t)g2) & 15u) != 0) return OCN_EINVAL;
   if (((uintptr_t)attr & 7u) != 0) return OCN_EINVAL;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_ATTR(LPE, NV)                                                                                              \
-  do {                                                                                                                    \
-    const i64 epb = (i64)OCN_WPB * (OCN_WAVE / LPE);                                                                      \
-    hipLaunchKernelGGL((cn_attr_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,          \
-                       (const i64*)rowptrA, colA, (const i64*)src, (const i64*)order, (i64)B, (const i64*)off, flags, wc, \
-                       (i64)flags_cap, reinterpret_cast<const float4*>(weights), h, (int)H, g1, g2,                       \
-                       reinterpret_cast<float2*>(attr), rank);                                                            \
-  } while (0)
+#define LAUNCH_ATTR(LPE, NV)                                                                                            \
+  hipLaunchKernelGGL((cn_attr_kernel<LPE, NV>), dim3(lane_group_blocks(B, LPE)), dim3(OCN_BLOCK), 0, st,                \
+                     (const i64*)rowptrA, colA, (const i64*)src, (const i64*)order, (i64)B, (const i64*)off, flags, wc, \
+                     (i64)flags_cap, reinterpret_cast<const float4*>(weights), h, (int)H, g1, g2,                       \
+                     reinterpret_cast<float2*>(attr), rank)
   OCN_SWITCH_WIDTH(H, LAUNCH_ATTR)
 #undef LAUNCH_ATTR
   return launch_status();

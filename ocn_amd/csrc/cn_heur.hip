@@ -3,12 +3,10 @@
 // The shape of cn8_pool.hip with a 16-byte node row in place of an embedding row: nothing of a candidate depends on the
 // rest of the batch, so there are no flag bytes, no histogram, no atomics and no workspace.
 // See include/ocn_hip.h (ocn_cn_node_sums).
-#include "common.h"
+#include "lane_group.h"
 
 constexpr int HEUR_LPE = 16;                     // lanes per candidate: four candidates per wave, sixteen per workgroup
-constexpr int HEUR_GPW = OCN_WAVE / HEUR_LPE;
 constexpr int HEUR_PT = 4;                       // positions per lane and round: a round tests 64 positions of N(i)
-constexpr int HEUR_EPB = OCN_WPB * HEUR_GPW;     // candidates per workgroup
 
 // membership of key in the sorted row a[0..n): the largest q with a[q] <= key is found in a number of steps that depends
 // on n alone — the lanes of a group search the same row, so they stay together — and every load is unconditional and in
@@ -44,11 +42,9 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_node_sums_kernel(
     const i64* __restrict__ src, const i64* __restrict__ dst, const i64* __restrict__ order, i64 B,
     const float* __restrict__ w, float* __restrict__ sum1, float* __restrict__ sum2,
     int32_t* __restrict__ cnt1, int32_t* __restrict__ cnt2, float* __restrict__ deg) {
-  const int lane = threadIdx.x & 63;
-  const int gl = lane % HEUR_LPE;
-  const int gbase = lane - gl;
-  const i64 bid = xcd_block();           // an XCD's eighth of the processing order, as cn8_pool_kernel takes
-  const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * HEUR_GPW + lane / HEUR_LPE;
+  const lane_group<HEUR_LPE> g;
+  const int gl = g.gl, gbase = g.gbase;
+  const i64 slot = g.slot(xcd_block());     // an XCD's eighth of the processing order, as cn8_pool_kernel takes
   if (slot >= B) return;                    // whole group leaves together
   const i64 e = order ? order[slot] : slot;
   const i64 i = src[e], j = dst[e];
@@ -87,8 +83,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_node_sums_kernel(
     }
 #pragma unroll
     for (int t = 0; t < HEUR_PT; ++t) {             // ascending position order: tile t, then lane
-      unsigned long long m = __ballot(f[t] != 0);
-      m = (m >> gbase) & ((1ull << HEUR_LPE) - 1ull);
+      unsigned long long m = lane_group_mask<HEUR_LPE>(f[t] != 0, gbase);
       while (m) {                                   // (the same trip count in every lane of the group)
         const int sl = gbase + __ffsll((long long)m) - 1;
         m &= m - 1;
@@ -123,15 +118,14 @@ int ocn_cn_node_sums(const int64_t* rowptrA, const int32_t* colA,
                      const float* w, float* sum1, float* sum2, int32_t* cnt1, int32_t* cnt2, float* deg, void* stream) {
   if (B < 0 || n_cols < 0) return OCN_EINVAL;
   if (!rowptrA || !colA || !src || !dst || !w || !sum1 || !sum2 || !cnt1 || !cnt2) return OCN_EINVAL;
-  if (!bitmapT1 && !(rowptrT1 && colT1)) return OCN_EINVAL;
-  const bool has2 = bitmapT2 || rowptrT2 || colT2;
-  if (has2 && !bitmapT2 && !(rowptrT2 && colT2)) return OCN_EINVAL;
-  if (bitmapT1 && (bm1_stride_words < 0 || bm1_stride_words * 32 < n_cols)) return OCN_EINVAL;
-  if (bitmapT2 && (bm2_stride_words < 0 || bm2_stride_words * 32 < n_cols)) return OCN_EINVAL;
+  const bool has2 = bitmapT2 || rowptrT2 || colT2;                        // T2 is optional here
+  if (!set_operand_ok(bitmapT1, bm1_stride_words, rowptrT1, colT1, n_cols)) return OCN_EINVAL;
+  if (has2 && !set_operand_ok(bitmapT2, bm2_stride_words, rowptrT2, colT2, n_cols)) return OCN_EINVAL;
+  if ((bitmapT1 && bm1_stride_words < 0) || (bitmapT2 && bm2_stride_words < 0)) return OCN_EINVAL;
   if (deg && !rowptrT1) return OCN_EINVAL;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((B + HEUR_EPB - 1) / HEUR_EPB));
+  const dim3 grid(lane_group_blocks(B, HEUR_LPE));
 #define LAUNCH_HEUR(HAS2)                                                                                              \
   hipLaunchKernelGGL((cn_node_sums_kernel<HAS2>), grid, dim3(OCN_BLOCK), 0, st, (const i64*)rowptrA, colA,             \
                      (const i64*)rowptrT1, colT1, (const i64*)rowptrT2, colT2, (const unsigned*)bitmapT1,              \

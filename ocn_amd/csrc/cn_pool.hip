@@ -1,7 +1,7 @@
 // The common-neighbour stage, K3 forward: the pooling of cn5 / cn7 (packed, wave, long-row and generic forms) and the
 // three-vector pooling of cn6.  The slot records it reads are the intersection pass's (cn_flags.hip), the visiting order
 // cn_sched.hip's; common.h fixes their layout.  See include/ocn_hip.h for the reference call sites.
-#include "common.h"
+#include "lane_group.h"
 
 // ---------------------------------------------------------------------------------------------
 // K3: pooling — gather embedding rows over the flagged neighbours
@@ -9,8 +9,8 @@
 // (entry_weights: common.h)
 
 // Pool the flagged neighbours at positions [p_begin, p_end) of the source row into acc1 / acc2, in
-// ascending position (= column) order.  LPE lanes cooperate; each lane owns NV float4 of the
-// H = LPE*NV*4 features; four embedding rows are in flight per group.
+// ascending position (= column) order: the lane-group walk of lane_group.h.  LPE lanes cooperate; each lane owns NV
+// float4 of the H = LPE*NV*4 features; four embedding rows are in flight per group.
 constexpr int GATHER_UNR = 4;
 
 // The accumulate step of one embedding row: the {xcn1, xcn2} pairs of a lane's four features take w * x, component by component
@@ -33,7 +33,7 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
   // Narrow groups (small H) would otherwise pay one dependent load chain (column id -> column weights)
   // per LPE positions: a lane fetches PT positions per round, so a round always covers 64 of them
   // (hub rows of the ppa shape: 101 -> 40 us).
-  constexpr int PT = (OCN_WAVE / LPE) < 8 ? (OCN_WAVE / LPE) : 8;
+  constexpr int PT = lane_group<LPE>::PT;
   f32x2 acc[NV][4];                          // {acc1, acc2} component pairs: one packed multiply + add per pair
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -63,29 +63,20 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
 #pragma unroll
     for (int t = 0; t < PT; ++t) {             // ascending position order: tile t, then lane
       const bool need = (wa[t] != 0.f) | (wb[t] != 0.f);
-      unsigned long long m = __ballot(need);
-      if (LPE < 64) m = (m >> gbase) & ((1ull << (LPE & 63)) - 1ull);
+      unsigned long long m = lane_group_mask<LPE>(need, gbase);
       while (m) {
         int bsel[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-          bsel[u] = m ? (__ffsll((long long)m) - 1) : -1;
-          m &= m - 1;                          // no-op once m == 0
-        }
+        lane_group_take(m, bsel);
         int32_t kk[UNR];
         float wwa[UNR], wwb[UNR];
         float4 x[UNR][NV];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-          const int sl = gbase + (bsel[u] < 0 ? 0 : bsel[u]);
+          const int sl = lane_group_src(gbase, bsel[u]);
           kk[u] = __shfl(k[t], sl, OCN_WAVE);
           wwa[u] = __shfl(wa[t], sl, OCN_WAVE);
           wwb[u] = __shfl(wb[t], sl, OCN_WAVE);
-          if (bsel[u] >= 0) {
-            const float4* row = h4 + (i64)kk[u] * rowq + gl;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
-          }
+          lane_group_row<LPE>(bsel[u], kk[u], h4, rowq, gl, x[u]);
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
@@ -102,33 +93,6 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
   for (int v = 0; v < NV; ++v) {
     acc1[v] = make_float4(acc[v][0].x, acc[v][1].x, acc[v][2].x, acc[v][3].x);
     acc2[v] = make_float4(acc[v][0].y, acc[v][1].y, acc[v][2].y, acc[v][3].y);
-  }
-}
-
-// One float4 of a candidate's three output rows: the pooled pair (where the heads read them) and x_i * x_j from the endpoint
-// rows' quads a, b.
-__device__ __forceinline__ void pool_emit(float4* __restrict__ o1, float4* __restrict__ o2, float4* __restrict__ o3,
-                                          const float4& acc1, const float4& acc2, const float4& a, const float4& b, bool st1,
-                                          bool st2) {
-  if (st1) *o1 = acc1;
-  if (st2) *o2 = acc2;
-  *o3 = make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
-}
-
-template <int LPE, int NV>
-__device__ __forceinline__ void pool_store(i64 e, i64 i, i64 j, int gl, const float4* __restrict__ h4, i64 rowq,
-                                           const float4 (&acc1)[NV], const float4 (&acc2)[NV],
-                                           float* __restrict__ xcn1, float* __restrict__ xcn2,
-                                           float* __restrict__ xij, bool st1 = true, bool st2 = true) {
-  const float4* hi = h4 + i * rowq + gl;
-  const float4* hj = h4 + j * rowq + gl;
-  float4* o1 = reinterpret_cast<float4*>(xcn1) + e * rowq + gl;
-  float4* o2 = reinterpret_cast<float4*>(xcn2) + e * rowq + gl;
-  float4* o3 = reinterpret_cast<float4*>(xij) + e * rowq + gl;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const float4 a = hi[v * LPE], b = hj[v * LPE];
-    pool_emit(o1 + v * LPE, o2 + v * LPE, o3 + v * LPE, acc1[v], acc2[v], a, b, st1, st2);
   }
 }
 
@@ -150,9 +114,9 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
     const u64* __restrict__ rec,         // slot records of the intersection pass (then order/src/dst/off/cnt are not read), or NULL
     const int32_t* __restrict__ perm,    // ocn_gather_schedule's visiting order of the slot groups (longest first per XCD), or NULL
     const float* __restrict__ rowsum) {  // (A h)[i] rows for candidates whose whole source row is cn2 with weight 1 (ocn_hip.h), or NULL
-  constexpr int GPW = OCN_WAVE / LPE;
-  const int lane = threadIdx.x & 63;
-  const int gl = lane % LPE;
+  constexpr int GPW = lane_group<LPE>::GPW;
+  const int lane = threadIdx.x & 63;       // (lane_group<LPE>'s gl, gbase and slot, written out: through the struct the narrow
+  const int gl = lane % LPE;               // instances come out 9 - 15 instructions shorter, and no longer the measured ones)
   const int gbase = lane - gl;
   // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  The batch rows are
   // visited in source-node order, so give every XCD one contiguous eighth of that order: rows
@@ -778,8 +742,8 @@ __global__ __launch_bounds__(LONG_THREADS) void cn_gather_long_kernel(
 // cn6 pooling: three pooled vectors.  flagsA carries the cn1 / cn2 bits, flagsB's bit 0 the cn3 bit (two
 // intersection passes over the same source rows, so the same `off`); per entry
 //   w1 = [cn1]*inv1,  w2 = ([cn2] - t*[cn1])*inv2,  w3 = (([cn3] - t*[cn1]) - nip*w2)*inv3,
-// each product / difference rounded separately, pooled in ascending column order.  LPE lanes per
-// batch row, like cn_gather_kernel (no hub-row split: every row keeps the sequential order).
+// each product / difference rounded separately, pooled in ascending column order.  The walk of lane_group.h,
+// a round of LPE positions; LPE lanes per batch row, like cn_gather_kernel (no hub-row split: every row keeps the sequential order).
 template <int LPE, int NV>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_gather3_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
@@ -788,12 +752,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather3_kernel(
     const float4* __restrict__ wA, const float4* __restrict__ wB, const float* __restrict__ nip_p,
     const float* __restrict__ h, int H, float* __restrict__ xcn1, float* __restrict__ xcn2,
     float* __restrict__ xcn3, float* __restrict__ xij) {
-  constexpr int GPW = OCN_WAVE / LPE;
   constexpr int UNR = 4;
-  const int lane = threadIdx.x & 63;
-  const int gl = lane % LPE;
-  const int gbase = lane - gl;
-  const i64 slot = ((i64)blockIdx.x * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  const lane_group<LPE> g;
+  const int gl = g.gl, gbase = g.gbase;
+  const i64 slot = g.slot((i64)blockIdx.x);
   if (slot >= B) return;
   const i64 e = order ? order[slot] : slot;
   const i64 i = src[e], j = dst[e];
@@ -820,29 +782,20 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather3_kernel(
       w3 = __fmul_rn(__fsub_rn(__fsub_rn(fb ? 1.0f : 0.f, tt), __fmul_rn(nip, w2)), inv3);
     }
     const bool need = (w1 != 0.f) | (w2 != 0.f) | (w3 != 0.f);
-    unsigned long long m = __ballot(need);
-    if (LPE < 64) m = (m >> gbase) & ((1ull << (LPE & 63)) - 1ull);
+    unsigned long long m = lane_group_mask<LPE>(need, gbase);
     while (m) {
       int bsel[UNR];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        bsel[u] = m ? (__ffsll((long long)m) - 1) : -1;
-        m &= m - 1;
-      }
+      lane_group_take(m, bsel);
       float ww1[UNR], ww2[UNR], ww3[UNR];
       float4 x[UNR][NV];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
-        const int sl = gbase + (bsel[u] < 0 ? 0 : bsel[u]);
+        const int sl = lane_group_src(gbase, bsel[u]);
         const int32_t kk = __shfl(k, sl, OCN_WAVE);
         ww1[u] = __shfl(w1, sl, OCN_WAVE);
         ww2[u] = __shfl(w2, sl, OCN_WAVE);
         ww3[u] = __shfl(w3, sl, OCN_WAVE);
-        if (bsel[u] >= 0) {
-          const float4* row = h4 + (i64)kk * rowq + gl;
-#pragma unroll
-          for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
-        }
+        lane_group_row<LPE>(bsel[u], kk, h4, rowq, gl, x[u]);
       }
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
@@ -924,7 +877,7 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
                           const int32_t* wc, const float* weights, const float* h, int32_t H, int64_t max_row_len,
                           float* xcn1, float* xcn2, float* xij, const int64_t* out_row, const int32_t* cnt1,
                           const int32_t* cnt2, const uint64_t* rec, const int32_t* perm, const float* rowsum, hipStream_t st) {
-  const i64 epb = (i64)OCN_WPB * (OCN_WAVE / LPE);
+  const i64 epb = lane_group_epb(LPE);
   // the schedule's groups are the workgroups of the intersection pass: usable where the pooling's workgroups are the same
   const bool sched = perm && rec && epb == SCHED_GROUP && ((B + epb - 1) / epb) % 8 == 0;
   bool packed = true;
@@ -954,7 +907,7 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
     }
   }
   if (packed)
-    hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,
+    hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3(lane_group_blocks(B, LPE)), dim3(OCN_BLOCK), 0, st,
                        PACKED_ARGS, sched ? perm : (const int32_t*)nullptr, rowsum);
 #undef PACKED_ARGS
 #define LONG_ARGS (const i64*)rowptrA, colA, (const i64*)src, (const i64*)dst, (i64)B, (const i64*)off, flags, wc, \
@@ -1029,7 +982,7 @@ int64_t ocn_cn_gather_pair_min_batch(int64_t min_rows) {
 
 #define LAUNCH_GATHER3(LPE, NV)                                                                     \
   hipLaunchKernelGGL((cn_gather3_kernel<LPE, NV>),                                                   \
-                     dim3((unsigned)((B + (i64)OCN_WPB * (OCN_WAVE / (LPE)) - 1) / ((i64)OCN_WPB * (OCN_WAVE / (LPE))))), \
+                     dim3(lane_group_blocks(B, LPE)),                                                \
                      dim3(OCN_BLOCK), 0, (hipStream_t)stream, (const i64*)rowptrA, colA, (const i64*)src,      \
                      (const i64*)dst, (const i64*)order, (i64)B, (const i64*)off, flagsA, flagsB,             \
                      (const float4*)weightsA, (const float4*)weightsB, nip, h, (int)H, xcn1, xcn2, xcn3, xij)

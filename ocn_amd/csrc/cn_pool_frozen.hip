@@ -5,16 +5,14 @@
 // The arithmetic per candidate is that of ocn_cn_gather on the pattern route (entry_weights with c = 1, the fetch rule
 // wa != 0 || wb != 0, product and sum rounded separately, ascending column order).  See include/ocn_hip.h
 // (ocn_cn_pool_frozen).
-#include "common.h"
+#include "lane_group.h"
 
 constexpr int FROZEN_UNR = 4;   // embedding rows in flight per lane group
 
-// The lane-group shape of cn8_pool_kernel: LPE lanes cooperate on one candidate (64 / LPE candidates per wave), a lane owns
-// NV float4 of the H = LPE * NV * 4 features.  A round tests LPE * PT positions of the source row N(i) — one membership
-// probe pair per lane and position — and the lane that holds a member's column id loads that column's weight row with it
-// (one 16-byte load) and forms the entry's (wa, wb).  The entries with a non-zero weight are then walked by the ballot in
-// ascending position, four embedding rows in flight, each adding to BOTH accumulators.  A hub row is walked by the same
-// group in the same order (it only takes more rounds).
+// The lane-group walk of lane_group.h.  A round tests LPE * PT positions of the source row N(i) — one membership probe pair
+// per lane and position — and the lane that holds a member's column id loads that column's weight row with it (one 16-byte
+// load) and forms the entry's (wa, wb).  The entries with a non-zero weight are then walked in ascending position, each
+// adding to BOTH accumulators.  A hub row is walked by the same group in the same order (it only takes more rounds).
 template <int LPE, int NV>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
     const i64* __restrict__ rowptrA, const int32_t* __restrict__ colA,
@@ -25,22 +23,13 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
     const float4* __restrict__ weights, const float* __restrict__ h, int H,
     float* __restrict__ xcn1, float* __restrict__ xcn2, float* __restrict__ xij,
     int32_t* __restrict__ cnt1, int32_t* __restrict__ cnt2) {
-  constexpr int GPW = OCN_WAVE / LPE;
-  constexpr int PT = GPW < 8 ? GPW : 8;
-  const int lane = threadIdx.x & 63;
-  const int gl = lane % LPE;
-  const int gbase = lane - gl;
-  const i64 bid = xcd_block();           // an XCD's eighth of the processing order, as the pooling of the chain takes
-  const i64 slot = (bid * OCN_WPB + (threadIdx.x >> 6)) * GPW + lane / LPE;
+  constexpr int PT = lane_group<LPE>::PT;
+  const lane_group<LPE> g;
+  const int gl = g.gl, gbase = g.gbase;
+  const i64 slot = g.slot(xcd_block());     // an XCD's eighth of the processing order, as the pooling of the chain takes
   if (slot >= B) return;                    // whole group leaves together
-  const i64 e = order ? order[slot] : slot;
-  const i64 i = src[e], j = dst[e];
-  const i64 a0 = rowptrA[i], da = rowptrA[i + 1] - a0;
-  const unsigned* bm1_row = bmT1 ? bmT1 + j * bm1_stride : nullptr;
-  const unsigned* bm2_row = bmT2 ? bmT2 + j * bm2_stride : nullptr;
-  i64 b0 = 0, db = 0, c0 = 0, dc = 0;
-  if (!bmT1) { b0 = rowptrT1[j]; db = rowptrT1[j + 1] - b0; }
-  if (!bmT2) { c0 = rowptrT2[j]; dc = rowptrT2[j + 1] - c0; }
+  const lane_group_pair c(slot, rowptrA, rowptrT1, colT1, rowptrT2, colT2, bmT1, bm1_stride, bmT2, bm2_stride, src, dst, order);
+  const i64 e = c.e, i = c.i, j = c.j, a0 = c.a0, da = c.da;
   const float4* h4 = reinterpret_cast<const float4*>(h);
   const i64 rowq = H >> 2;                  // float4 per row
   f32x4 acc1[NV], acc2[NV];
@@ -58,13 +47,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
 #pragma unroll
     for (int t = 0; t < PT; ++t) {
       f[t] = 0;
-      if (k[t] >= 0) {
-        const bool f1 = bm1_row ? ((bm1_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : sorted_has(colT1 + b0, db, k[t]);
-        const bool f2 = bm2_row ? ((bm2_row[k[t] >> 5] >> (k[t] & 31)) & 1u) : sorted_has(colT2 + c0, dc, k[t]);
-        f[t] = (f1 ? OCN_F_CN1 : 0u) | (f2 ? OCN_F_CN2 : 0u);
-        c1 += f1;                              // the member counts: whatever the weights are
-        c2 += f2;
-      }
+      if (k[t] >= 0) f[t] = c.probe(k[t], c1, c2);      // (the member counts: whatever the weights are)
     }
     float wa[PT], wb[PT];
 #pragma unroll
@@ -75,28 +58,19 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
 #pragma unroll
     for (int t = 0; t < PT; ++t) {             // ascending position order: tile t, then lane
       const bool need = (wa[t] != 0.f) | (wb[t] != 0.f);
-      unsigned long long m = __ballot(need);
-      if (LPE < 64) m = (m >> gbase) & ((1ull << (LPE & 63)) - 1ull);
+      unsigned long long m = lane_group_mask<LPE>(need, gbase);
       while (m) {
         int bsel[FROZEN_UNR];
-#pragma unroll
-        for (int u = 0; u < FROZEN_UNR; ++u) {
-          bsel[u] = m ? (__ffsll((long long)m) - 1) : -1;
-          m &= m - 1;                          // no-op once m == 0
-        }
+        lane_group_take(m, bsel);
         float wwa[FROZEN_UNR], wwb[FROZEN_UNR];
         float4 x[FROZEN_UNR][NV];
 #pragma unroll
         for (int u = 0; u < FROZEN_UNR; ++u) {
-          const int sl = gbase + (bsel[u] < 0 ? 0 : bsel[u]);
+          const int sl = lane_group_src(gbase, bsel[u]);
           const int32_t kk = __shfl(k[t], sl, OCN_WAVE);
           wwa[u] = __shfl(wa[t], sl, OCN_WAVE);
           wwb[u] = __shfl(wb[t], sl, OCN_WAVE);
-          if (bsel[u] >= 0) {
-            const float4* row = h4 + (i64)kk * rowq + gl;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) x[u][v] = row[v * LPE];
-          }
+          lane_group_row<LPE>(bsel[u], kk, h4, rowq, gl, x[u]);
         }
 #pragma unroll
         for (int u = 0; u < FROZEN_UNR; ++u) {
@@ -123,6 +97,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
     c2 += __shfl_xor(c2, o, OCN_WAVE);
   }
   if (gl == 0) { cnt1[e] = c1; cnt2[e] = c2; }
+  // (pool_store's loop, written out: through the call one instance in six gains an s_waitcnt)
   const float4* hi = h4 + i * rowq + gl;
   const float4* hj = h4 + j * rowq + gl;
   float4* o1 = reinterpret_cast<float4*>(xcn1) + e * rowq + gl;
@@ -131,9 +106,8 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_pool_frozen_kernel(
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const float4 a = hi[v * LPE], b = hj[v * LPE];
-    o1[v * LPE] = make_float4(acc1[v].x, acc1[v].y, acc1[v].z, acc1[v].w);
-    o2[v * LPE] = make_float4(acc2[v].x, acc2[v].y, acc2[v].z, acc2[v].w);
-    o3[v * LPE] = make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
+    pool_emit(o1 + v * LPE, o2 + v * LPE, o3 + v * LPE, make_float4(acc1[v].x, acc1[v].y, acc1[v].z, acc1[v].w),
+              make_float4(acc2[v].x, acc2[v].y, acc2[v].z, acc2[v].w), a, b, true, true);
   }
 }
 
@@ -148,24 +122,19 @@ int ocn_cn_pool_frozen(const int64_t* rowptrA, const int32_t* colA,
                        const float* weights, const float* h, int32_t H, float* xcn1, float* xcn2, float* xij,
                        int32_t* cnt1, int32_t* cnt2, void* stream) {
   if (B < 0 || n_cols < 0) return OCN_EINVAL;
-  if (H != 16 && H != 32 && H != 64 && H != 128 && H != 256 && H != 512) return OCN_EINVAL;
+  if (!lane_group_width(H)) return OCN_EINVAL;
   if (!rowptrA || !colA || !src || !dst || !weights || !h || !xcn1 || !xcn2 || !xij || !cnt1 || !cnt2) return OCN_EINVAL;
   if (((uintptr_t)weights & 15u) != 0) return OCN_EINVAL;
-  if (!bitmapT1 && !(rowptrT1 && colT1)) return OCN_EINVAL;
-  if (!bitmapT2 && !(rowptrT2 && colT2)) return OCN_EINVAL;
-  if (bitmapT1 && bm1_stride_words * 32 < n_cols) return OCN_EINVAL;
-  if (bitmapT2 && bm2_stride_words * 32 < n_cols) return OCN_EINVAL;
+  if (!set_operand_ok(bitmapT1, bm1_stride_words, rowptrT1, colT1, n_cols)) return OCN_EINVAL;
+  if (!set_operand_ok(bitmapT2, bm2_stride_words, rowptrT2, colT2, n_cols)) return OCN_EINVAL;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_FROZEN(LPE, NV)                                                                                            \
-  do {                                                                                                                    \
-    const i64 epb = (i64)OCN_WPB * (OCN_WAVE / LPE);                                                                      \
-    hipLaunchKernelGGL((cn_pool_frozen_kernel<LPE, NV>), dim3((unsigned)((B + epb - 1) / epb)), dim3(OCN_BLOCK), 0, st,   \
-                       (const i64*)rowptrA, colA, (const i64*)rowptrT1, colT1, (const i64*)rowptrT2, colT2,               \
-                       (const unsigned*)bitmapT1, (i64)bm1_stride_words, (const unsigned*)bitmapT2,                       \
-                       (i64)bm2_stride_words, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B,                \
-                       reinterpret_cast<const float4*>(weights), h, (int)H, xcn1, xcn2, xij, cnt1, cnt2);                 \
-  } while (0)
+#define LAUNCH_FROZEN(LPE, NV)                                                                                  \
+  hipLaunchKernelGGL((cn_pool_frozen_kernel<LPE, NV>), dim3(lane_group_blocks(B, LPE)), dim3(OCN_BLOCK), 0, st, \
+                     (const i64*)rowptrA, colA, (const i64*)rowptrT1, colT1, (const i64*)rowptrT2, colT2,       \
+                     (const unsigned*)bitmapT1, (i64)bm1_stride_words, (const unsigned*)bitmapT2,               \
+                     (i64)bm2_stride_words, (const i64*)src, (const i64*)dst, (const i64*)order, (i64)B,        \
+                     reinterpret_cast<const float4*>(weights), h, (int)H, xcn1, xcn2, xij, cnt1, cnt2)
   OCN_SWITCH_WIDTH(H, LAUNCH_FROZEN)
 #undef LAUNCH_FROZEN
   return launch_status();

@@ -70,6 +70,16 @@ static inline int grid_for(i64 items_per_block_units, i64 cap = (1 << 20)) {
     default: return OCN_EINVAL;          \
   }
 
+// ... and the host checks that the entries of those kernels share (lane_group.h has the device side)
+static inline bool lane_group_width(int H) { return H == 16 || H == 32 || H == 64 || H == 128 || H == 256 || H == 512; }
+// candidates per workgroup, and the workgroups of a batch of B
+constexpr i64 lane_group_epb(int lpe) { return (i64)OCN_WPB * (OCN_WAVE / lpe); }
+static inline unsigned lane_group_blocks(i64 B, int lpe) { return (unsigned)((B + lane_group_epb(lpe) - 1) / lane_group_epb(lpe)); }
+// a T1 / T2 operand: bit rows that cover n_cols columns, or both CSR arrays
+static inline bool set_operand_ok(const void* bitmap, i64 stride_words, const void* rowptr, const void* col, i64 n_cols) {
+  return bitmap ? stride_words * 32 >= n_cols : (rowptr && col);
+}
+
 // ---------------------------------------------------------------------------------------------
 // wave / block primitives
 // ---------------------------------------------------------------------------------------------
