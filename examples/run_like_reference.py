@@ -9,6 +9,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset collab --scale 0.05 --hiddim 64 --batch_size 8192
     python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
         --gnnedp 0.07 --res --maskinput --batch_size 384
+    python examples/run_like_reference.py --dataset cora --epochs 5 --table-dtype bf16    # test() and --recommend pool from a bf16 table of h
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
@@ -43,7 +44,7 @@ from ocn_amd.explain import explain_link_edges, explain_links                   
 from ocn_amd.frozen import freeze_columns                                           # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
-from ocn_amd.pipeline import score_mrr_split                                        # noqa: E402
+from ocn_amd.pipeline import embedding_table, score_mrr_split                       # noqa: E402
 from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
 from ocn_amd.recommend import (EmbeddingNeighbours, RandomWalks, ShortListUnion, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
@@ -119,17 +120,20 @@ def test(model, predictor, data, split_edge, evaluator, batch_size, use_valedges
     adj = data.adj_t
     h = model(data.x, adj)
     adj2 = build_adj2(adj, args)
+    table = lambda h: embedding_table(h, args.table_dtype)        # --table-dtype: cast once per embedding matrix, never per batch
 
     def score(e, h, adj):
         return torch.cat([predictor(h, adj, adjoverlap(adj, adj, e[perm].t()), adjoverlap(adj, adj2, e[perm].t()),
                                     e[perm].t(), args).squeeze(-1)
                           for perm in PermIterator(e.device, e.shape[0], batch_size, False)], dim=0)
 
-    pred = {k: score(edges[k], h, adj) for k in ("pos_train", "pos_valid", "neg_valid")}
+    t = table(h)
+    pred = {k: score(edges[k], t, adj) for k in ("pos_train", "pos_valid", "neg_valid")}
     if use_valedges_as_input:
         adj = data.full_adj_t
         h = model(data.x, adj)
-    pred.update({k: score(edges[k], h, adj) for k in ("pos_test", "neg_test")})
+        t = table(h)
+    pred.update({k: score(edges[k], t, adj) for k in ("pos_test", "neg_test")})
     results = {}
     for K in [20, 50, 100]:
         evaluator.K = K
@@ -158,7 +162,7 @@ def test_mrr(model, predictor, data, split_edge, evaluator, batch_size, use_vale
             neg = two_hop_negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
         elif args.structured_negatives:
             neg = negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
-        out.append(score_mrr_split(predictor, model(data.x, adj), adj, source, target, neg, batch_size, args, evaluator))
+        out.append(score_mrr_split(predictor, embedding_table(model(data.x, adj), args.table_dtype), adj, source, target, neg, batch_size, args, evaluator))
     return {'MRR': tuple(out)}, None
 
 
@@ -226,6 +230,10 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         if args.recommend_accept > 0:
             state = EncoderState(model, data.x, adj)      # h and its per-layer activations stay resident beside A and A²
 
+    def table(adj):
+        # --table-dtype: the embeddings the model requests pool from, cast once per request (pipeline.embedding_table)
+        return embedding_table(state.h if state is not None else model(data.x, adj), args.table_dtype)
+
     def refreshed(adj, edges, tag):
         rows = state.refresh(adj, edges)                  # only the rows the update can reach are recomputed
         print(f"refreshed {rows.numel()} of {state.n} embedding rows after {tag} ({state.route} route)", flush=True)
@@ -236,7 +244,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         if args.heuristic:
             dst, score = recommend_links_heuristic(adj, adj2, sources, k, args.testbs, args.heuristic, hops=args.recommend_hops)
         else:
-            h = state.h if state is not None else model(data.x, adj)
+            h = table(adj)
             dst, score = recommend_links(predictor, h, adj, adj2, sources, k, args.testbs, args, prefilter=args.recommend_prefilter,
                                          hops=args.recommend_hops)
         for s, d, v in zip(sources.tolist(), dst.tolist(), score.tolist()):
@@ -254,7 +262,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
 
     dst, score = top(adj, adj2, "recommend")
     if args.recommend_frozen:
-        h = state.h if state is not None else model(data.x, adj)
+        h = table(adj)
         _, half = recommend_links(predictor, h, adj, adj2, sources[::2].contiguous(), k, max(args.testbs // 3, 1), args,
                                   prefilter=args.recommend_prefilter, hops=args.recommend_hops)    # (like with like: a source's short list is its own)
         same = torch.allclose(half, score[::2], rtol=1e-5, atol=1e-5)
@@ -305,7 +313,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
             show(f"{args.heuristic} over {args.recommend_hops} hops",
                  rank_links_heuristic(adj, adj2, first, truth, args.testbs, args.heuristic, hops=args.recommend_hops))
         else:
-            h = state.h if state is not None else model(data.x, adj)
+            h = table(adj)
             route = f"{args.predictor} over {args.recommend_hops} hops" + (" (walk route)" if adj2 is None else "")
             if args.recommend_prefilter:
                 show(route + " prefilter " + prefilter_name(args.recommend_prefilter),
@@ -317,7 +325,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
         # --recommend-explain M: why these links — gradient x input on the pooled vectors, per common neighbour.  The winners form one
         # batch of their own: an unfrozen cn5 / cn7 weighs them by THAT batch's column statistics, so only a frozen predictor (or
         # cn8, which has no column weights) is explained at the scores the recommendation printed
-        h = state.h if state is not None else model(data.x, adj)
+        # (gradients want fp32 rows: main() refuses --table-dtype bf16 / f16 beside this option)
+        h = table(adj)
         won = torch.stack([sources.view(-1, 1).expand_as(dst).reshape(-1), dst.reshape(-1)], dim=1)
         listed = won[:, 1] >= 0
         won = won[listed].contiguous()
@@ -457,7 +466,13 @@ def main(argv=None):
     ap.add_argument("--recommend-check-refresh", action="store_true",
                     help="with --recommend-accept and a model: assert that the refreshed node embeddings (ocn_amd.update.EncoderState) "
                          "equal a full encoder pass bit for bit after the insert, and after the undo")
+    ap.add_argument("--table-dtype", choices=("fp32", "bf16", "f16"), default="fp32",
+                    help="the embedding table the predictor pools from in test() and under --recommend (pipeline.embedding_table): "
+                         "bf16 / f16 rows are half the bytes, widened exactly and summed in fp32; training is always fp32")
     args = ap.parse_args(argv)
+    if args.table_dtype != "fp32" and (args.predictor == "cn6" or args.recommend_explain or args.recommend_explain_edges
+                                       or args.recommend_emb):
+        ap.error("--table-dtype bf16 / f16: cn6, --recommend-explain, --recommend-explain-edges and --recommend-emb read fp32 rows")
     if not 0.0 <= args.hard_negatives <= 1.0:
         ap.error("--hard-negatives SHARE: a share in [0, 1]")
     if args.recommend_check_refresh and (args.heuristic or not (args.recommend and args.recommend_accept > 0)):

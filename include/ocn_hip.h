@@ -61,7 +61,8 @@ extern "C" {
  *    ocn_mips_workspace_bytes, ocn_mips_topm_i8 (embedding retrieval: the m largest int8 inner products of every query over all
  *    nodes, exact, on the integer matrix cores — a short list that is not bound to the graph neighbourhood);
  *    ocn_cn_flags_cover (the intersection pass with a certificate that T2 is the full A·A of a symmetric A: candidates that are
- *    stored entries of A read no T2; same bits). */
+ *    stored entries of A read no T2; same bits); ocn_cn_gather_h16 (the pooling from a bf16 / f16 embedding table: half the
+ *    bytes per row, fp32 sums, bit for bit ocn_cn_gather on the widened table). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -341,6 +342,22 @@ int ocn_cn_gather(const int64_t* rowptrA, const int32_t* colA,
                   const int32_t* cnt1, const int32_t* cnt2, const uint64_t* rec /* or NULL */,
                   const int32_t* perm /* ocn_gather_schedule's, or NULL */, const float* rowsum /* or NULL */,
                   void* stream);
+/* The pooling from a half-precision embedding table.  h16 is [N][H] row-major 2-byte elements: bf16 (fmt = 0) or IEEE f16
+ * (fmt = 1); every other argument means what it means for ocn_cn_gather, and the outputs are fp32 [B][H].  Both widenings are
+ * exact, the entry weights, the accumulators and the order are ocn_cn_gather's (each term one fp32 multiply, then one add,
+ * ascending column order, strictly sequential for EVERY row length — a hub row is walked by the same lane group as any other),
+ * and so are the skip rules (cnt1 / cnt2 / rec / out_row).  Hence xcn1, xcn2 and xij are bit for bit what ocn_cn_gather
+ * leaves for the same table widened to fp32.  There is no `rowsum`: the shortcut wants an fp32 A h, and it adds the same
+ * numbers in the same order, so leaving it out changes no bit.  max_row_len is accepted and not used (one form).  rec / perm
+ * change the processing order only.  No allocation, no global state, no host synchronisation: the launch can be captured.
+ * H in {16, 32, 64, 128, 256, 512}; h16 must be 16-byte aligned.  NULL required pointers (rowptrA, src, dst, off, weights, h16,
+ * the outputs), B < 0, another H, fmt outside {0, 1}: OCN_EINVAL before any HIP call.  B == 0 returns 0. */
+int ocn_cn_gather_h16(const int64_t* rowptrA, const int32_t* colA, const int64_t* src, const int64_t* dst,
+                      const int64_t* order, int64_t B, const int64_t* off, const uint8_t* flags, const int32_t* wc,
+                      const float* weights /* [N][4] */, const void* h16 /* [N][H], 2-byte elements */,
+                      int32_t fmt /* 0 = bf16, 1 = f16 */, int32_t H, int64_t max_row_len, float* xcn1, float* xcn2,
+                      float* xij, const int64_t* out_row, const int32_t* cnt1, const int32_t* cnt2,
+                      const uint64_t* rec /* or NULL */, const int32_t* perm /* or NULL */, void* stream);
 /* cn8 (CNLinkPredictorbaselearnablation, model.py:3233-3449; pattern route): intersection and pooling in ONE pass.  cn8
  * pools without column weights, so a candidate's vectors depend on nothing but the candidate:
  *   xcn1[e] = sum_{k in N(i) ∩ T1(j)} h[k]   xcn2[e] = sum_{k in N(i) ∩ T2(j)} h[k]   xij[e] = h[i] (.) h[j]

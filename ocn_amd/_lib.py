@@ -57,6 +57,8 @@ SIGNATURES = {
     "ocn_cn_weights_cn7": (c_int32, [_P, c_int64, c_float, _P, _P, _P]),
     "ocn_cn_gather": (c_int32, [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int64, _P, _P, _P, _P, _P,
                                 _P, _P, _P, _P, _P]),
+    "ocn_cn_gather_h16": (c_int32, [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P,
+                                    _P, _P, _P, _P]),
     "ocn_cn8_pool": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int32, _P, _P,
                                _P, _P, _P, _P]),
     "ocn_cn_pool_frozen": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, c_int32, _P,

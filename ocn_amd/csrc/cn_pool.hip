@@ -96,9 +96,9 @@ __device__ __forceinline__ void pool_range(i64 p_begin, i64 p_end, i64 a0, i64 b
   }
 }
 
-// Source rows longer than this are pooled by a whole workgroup (cn_gather_long_kernel): its lane
-// groups take contiguous segments of the row and the partial sums are added in segment order.
-// Rows up to LONG_ROW keep the strictly sequential ascending-column sum of the reference's spmm.
+// Source rows longer than this are pooled by a whole workgroup (cn_gather_long_kernel; a wave of cn_gather_wave_kernel for
+// narrow embeddings in a large batch): its other lanes only FETCH the rows, one wave adds them in rank order.  So these
+// rows, like the ones up to LONG_ROW, keep the strictly sequential ascending-column sum of the reference's spmm.
 #define LONG_ROW 1024
 
 // LPE lanes cooperate on one edge (64/LPE edges per wave).

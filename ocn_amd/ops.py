@@ -109,7 +109,24 @@ def _req(t: Tensor, dtype, name: str, ndim: Optional[int] = None) -> Tensor:
     return t
 
 
-ST_CAP, ST_SCAN = 1, 2             # include/ocn_hip.h: OCN_ST_CAP, OCN_ST_SCAN (bits of status[0] and of the sticky status[3])
+# A half-precision embedding table (``pipeline.embedding_table``): dtype -> the `fmt` of ocn_cn_gather_h16.  Such a table serves the
+# eval pooling of cn5 / cn7 / cn8 (``cn_gather``) and nothing else; every other consumer of a table refuses it (``refuse_half_table``).
+HALF_TABLE_FMT = {torch.bfloat16: 0, torch.float16: 1}
+
+
+def is_half_table(t) -> bool:
+    return isinstance(t, Tensor) and t.dtype in HALF_TABLE_FMT
+
+
+def refuse_half_table(t, what: str) -> None:
+    """TypeError where ``t`` is a bf16 / f16 table and ``what`` is built for fp32 rows only.  Reads the dtype alone: callable
+    before anything touches the device."""
+    if is_half_table(t):
+        raise TypeError(f"{what} needs an fp32 (torch.float32) embedding table, got {t.dtype}: a bf16 / f16 table serves the "
+                        "eval-mode, no-grad pooling of cn5 / cn7 / cn8 only — pass table.float()")
+
+
+ST_CAP, ST_SCAN = 1, 2           # include/ocn_hip.h: OCN_ST_CAP, OCN_ST_SCAN (bits of status[0] and of the sticky status[3])
 
 
 def _total(t: Tensor) -> int:
@@ -599,11 +616,22 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
               order: Optional[Tensor] = None, max_row_len: int = 0, wsd=None, out_row: Optional[Tensor] = None,
               cnt1: Optional[Tensor] = None, cnt2: Optional[Tensor] = None, rec: Optional[Tensor] = None,
               sched: Optional[Tensor] = None, rowsum: Optional[Tensor] = None, sched_ready: bool = False):
+    """The pooling (ocn_hip.h: ocn_cn_gather).  ``h``: the fp32 embedding table — or a bf16 / f16 one (``pipeline.embedding_table``),
+    which goes to ocn_cn_gather_h16: the same fp32 output buffer, the same schedule and slot records, no ``rowsum`` (it is
+    dropped: the shortcut adds the same numbers in the same order), widths ``LN_WIDTHS`` only.  The three outputs are bit for
+    bit those of the fp32 entry on ``h.float()``."""
     _req(weights, torch.float32, "weights", 2)
-    _req(h, torch.float32, "h", 2)
+    half = is_half_table(h)
+    _req(h, h.dtype if half else torch.float32, "h", 2)
     if weights.shape[0] != h.shape[0] or weights.shape[1] != 4:
         raise ValueError("weights must be [N,4] with N = h.shape[0]")
     B, H = src.numel(), h.shape[1]
+    if half:
+        if H not in LN_WIDTHS:
+            raise NotImplementedError(f"the pooling of a {h.dtype} table supports hidden widths {LN_WIDTHS}, got {H}")
+        if h.data_ptr() % 16:
+            raise ValueError("h must be 16-byte aligned")
+        rowsum = None
     out = buf(wsd, "pooled", (3, B, H), torch.float32, h.device)
     if rowsum is not None and (wc is not None or cnt2 is None or _req(rowsum, torch.float32, "rowsum", 2).shape != h.shape):
         raise ValueError("rowsum: [N, H] row sums of h, pattern route with per-row counts only")
@@ -614,6 +642,13 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
         if not sched_ready:           # (a scoring loop's phase A has run gather_schedule already)
             check(_lib.lib().ocn_gather_schedule(ptr(sched), n_groups, int(sched_segment), ptr(perm), stream_ptr()), "ocn_gather_schedule")
     _mark("cn_pre")                   # (stage timers: what sits between the intersection pass and the pooling on this stream)
+    if half:
+        check(_lib.lib().ocn_cn_gather_h16(ptr(rowptrA), ptr(colA), ptr(src), ptr(dst), ptr(order), B, ptr(off), ptr(flags),
+                                           ptr(wc), ptr(weights), ptr(h), HALF_TABLE_FMT[h.dtype], H, int(max_row_len), ptr(out[0]),
+                                           ptr(out[1]), ptr(out[2]), ptr(out_row), ptr(cnt1), ptr(cnt2), ptr(rec), ptr(perm),
+                                           stream_ptr()), "ocn_cn_gather_h16")
+        _mark("cn_gather")
+        return out[0], out[1], out[2]
     check(_lib.lib().ocn_cn_gather(ptr(rowptrA), ptr(colA), ptr(src), ptr(dst), ptr(order), B, ptr(off), ptr(flags),
                                    ptr(wc), ptr(weights), ptr(h), H, int(max_row_len), ptr(out[0]), ptr(out[1]),
                                    ptr(out[2]), ptr(out_row), ptr(cnt1), ptr(cnt2), ptr(rec), ptr(perm), ptr(rowsum),
@@ -1454,7 +1489,8 @@ def cn_weights_cn6(histA: Tensor, histB: Tensor, innerprod: Tensor, exact=None, 
 @_on_device
 def cn_gather3(rowptrA, colA, src, dst, off, flagsA, flagsB, wA: Tensor, wB: Tensor, nip: Tensor, h: Tensor,
                order: Optional[Tensor] = None):
-    """(xcn1, xcn2, xcn3, x_i * x_j) of the 3-hop predictor."""
+    """(xcn1, xcn2, xcn3, x_i * x_j) of the 3-hop predictor.  fp32 rows only: a bf16 / f16 table raises TypeError."""
+    refuse_half_table(h, "cn6 (cn_gather3)")
     _req(wA, torch.float32, "weightsA", 2); _req(wB, torch.float32, "weightsB", 2)
     _req(h, torch.float32, "h", 2)
     if wA.shape != (h.shape[0], 4) or wB.shape != (h.shape[0], 4):

@@ -23,6 +23,30 @@ from . import ops
 from .utils import PermIterator, scratch_set_count
 
 
+TABLE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+
+
+def embedding_table(h: Tensor, dtype: str) -> Tensor:
+    """The node embeddings ``h`` [N, H] as the table a predictor pools from: ``dtype`` "fp32" (``h`` as given), "bf16" or "f16"
+    — a contiguous table on ``h``'s device, every element rounded to nearest even (``h.to(dtype)``).  A half table has half the
+    bytes per row and half the resident size; the eval-mode scoring of cn5 / cn7 / cn8 (``score_edges``, ``score_edges_walk``,
+    ``score_mrr_split``, ``recommend_links``, ``rank_links``, direct calls under ``no_grad``) takes it in place of ``h``, widens
+    its rows exactly and sums in fp32: the scores are bit for bit those of ``table.float()``, and differ from those of ``h`` by
+    the rounding of the table alone.  ValueError where a finite element of ``h`` would become infinite: |x| above 65 504 for
+    "f16" (bf16 keeps fp32's range: only the last half-step below its overflow is lost).  One reduction and one host sync: call it once per table, not per batch."""
+    if dtype not in TABLE_DTYPES:
+        raise ValueError(f"dtype must be one of {tuple(TABLE_DTYPES)}, got {dtype!r}")
+    if not isinstance(h, Tensor) or h.dim() != 2 or h.dtype != torch.float32:
+        raise ValueError("h must be a float32 [N, H] matrix of node embeddings")
+    if dtype == "fp32":
+        return h
+    t = h.detach().to(TABLE_DTYPES[dtype]).contiguous()
+    if bool((torch.isinf(t) & torch.isfinite(h)).any()):
+        raise ValueError(f"h holds finite values that round to infinity in {dtype}" +
+                         (" (|x| above 65504): use \"bf16\", or scale h" if dtype == "f16" else ""))
+    return t
+
+
 def _graphed(predictor, h, adj, make_handles, batch_size, args, n_batches):
     """A ``GraphedPhases`` for this loop where replaying pays: ``ops.graph_loops``, a GPU, an unsharded predictor and enough
     batches to amortise two eager uses and one capture per scratch set."""
@@ -69,7 +93,7 @@ def _score_batches(predictor, h: Tensor, adj, src_all: Tensor, dst_all: Tensor, 
     [2, b] (any strides), ``make_handles(e)`` -> its (cn1, cn2) handles, ``warm()`` builds what the batches share;
     ``run_ahead``: see ``RunAhead``."""
     if src_all.numel() == 0:
-        return h.new_zeros(0)
+        return h.new_zeros(0, dtype=torch.float32)          # (scores are fp32 whatever the table's dtype)
     # the adjacency's lazy caches (bit rows, longest row, degree sums; a product with rows on demand as a whole) are built HERE,
     # on the caller's stream, before the loop forks its side streams: two phase-A streams must never race on a half-built
     # cache (the caches also carry their own events)
@@ -137,6 +161,7 @@ def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     ``adj`` and the bit rows of ``adj2``, no A³ — so the scores are exactly those of per-batch ``forward`` calls at this batch
     size.  No side streams, no graph replay; the batches' status words are ORed on the device and read once at the end."""
     from .utils import adjoverlap, adjoverlap_3hop
+    ops.refuse_half_table(h, "cn6 (cn_gather3)")
     if group is not None:
         raise ValueError("cn6 is scored on one GPU: score_edges deals batches over a group for the two-handle predictors only")
     if adj2 is None:

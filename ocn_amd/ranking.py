@@ -128,6 +128,7 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     if predictor.training:
         raise RuntimeError("rank_links is the eval path; call predictor.eval() first")
     hops, prefilter = R._check_request(predictor, adj2, 1, prefilter, hops)
+    R._check_table(predictor, h, prefilter)
     sources, targets = _request(adj, sources, truth, known)
     ptr, edges, scores, rrank = R._score_request(predictor, h, adj, adj2, sources, batch_size, args, known, run_ahead, prefilter,
                                                  hops, targets if prefilter is not None else None)

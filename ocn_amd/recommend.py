@@ -598,6 +598,8 @@ def _emb_pass(stage: EmbeddingNeighbours, h: Optional[Tensor], adj: SparseTensor
     n = adj.size(0)
     if not isinstance(h, Tensor) or h.dim() != 2 or h.shape[0] != n:
         raise ValueError(f"h must be the [{n}, H] node embeddings of adj")
+    if stage.keys is None:
+        ops.refuse_half_table(h, "an EmbeddingNeighbours stage without keys= (the int8 index is quantised from fp32 rows)")
     index = stage.keys if isinstance(stage.keys, EmbeddingIndex) else \
         EmbeddingIndex((h if stage.keys is None else stage.keys).float(), stage.normalize)
     if index.n != n:
@@ -711,6 +713,21 @@ def _check_request(predictor, adj2: Optional[SparseTensor], k: int, prefilter, h
     return hops, prefilter
 
 
+def _check_table(predictor, h, prefilter) -> None:
+    """The refusals of a bf16 / f16 embedding table (``pipeline.embedding_table``) in a model request, before anything touches
+    the device (TypeError): cn6, and an ``EmbeddingNeighbours`` stage that would quantise its int8 index from ``h`` itself — pass
+    ``keys=EmbeddingIndex(h_fp32)``; the queries ``h[sources]`` are widened exactly.  Everything else passes the table on to the
+    scoring loop."""
+    from .model import CNLinkPredictor3hopCNs
+    if not ops.is_half_table(h):
+        return
+    if isinstance(predictor, CNLinkPredictor3hopCNs):
+        ops.refuse_half_table(h, "cn6 (cn_gather3)")
+    stages = prefilter.stages if isinstance(prefilter, ShortListUnion) else (prefilter,)
+    if any(isinstance(st, EmbeddingNeighbours) and st.keys is None for st in stages):
+        ops.refuse_half_table(h, "an EmbeddingNeighbours stage without keys= (the int8 index is quantised from fp32 rows)")
+
+
 def _score_request(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, batch_size: int,
                    args, known: Optional[SparseTensor], run_ahead: int, prefilter, hops: int,
                    targets: Optional[Tuple[Tensor, Tensor]] = None):
@@ -790,6 +807,7 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
         raise RuntimeError("recommend_links is the eval path; call predictor.eval() first")
     k = _check_k(k)
     hops, prefilter = _check_request(predictor, adj2, k, prefilter, hops)
+    _check_table(predictor, h, prefilter)
     ptr, edges, scores, _ = _score_request(predictor, h, adj, adj2, sources, batch_size, args, known, run_ahead, prefilter, hops)
     return _select(scores, ptr, edges, k)
 
