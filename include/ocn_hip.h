@@ -62,7 +62,8 @@ extern "C" {
  *    nodes, exact, on the integer matrix cores — a short list that is not bound to the graph neighbourhood);
  *    ocn_cn_flags_cover (the intersection pass with a certificate that T2 is the full A·A of a symmetric A: candidates that are
  *    stored entries of A read no T2; same bits); ocn_cn_gather_h16 (the pooling from a bf16 / f16 embedding table: half the
- *    bytes per row, fp32 sums, bit for bit ocn_cn_gather on the widened table). */
+ *    bytes per row, fp32 sums, bit for bit ocn_cn_gather on the widened table); ocn_walk_hash (the walk route's Bloom and slot
+ *    hashes on the host: tests build colliding node ids with the library's own arithmetic). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -224,12 +225,19 @@ int ocn_cn_flags_cover(const int64_t* rowptrA, const int32_t* colA,
  * entries of cn2 row e.  Work is cut into items of ocn_walk_chunk() neighbours of i (chunk_off from
  * ocn_chunk_offsets), so hub source nodes spread over many workgroups; cnt1 / cnt2 must be ZERO on
  * entry (a row's items add into them).  `status`: words [0] .. [2] ZERO on entry: [0] receives the
- * error bits as for ocn_cn_flags, [1] and [2] are the work-item ticket counters of the two sweeps, [3] the sticky word. */
+ * error bits as for ocn_cn_flags, [1] and [2] are the work-item ticket counters of the two sweeps, [3] the sticky word.
+ * Under OCN_ST_CAP (off[B] > flags_cap) a batch row is written whole or not at all: flags and wc of a row with
+ * off[e] + deg(src[e]) <= flags_cap are exact, the flags of every other row are left as they were, and so is its wc —
+ * except that with nds the whole of wc below the cap is cleared first (the reverse sweep adds into it).  cnt1, cnt2 and
+ * hist stay complete for the rows swept from the source's side (and for those of ocn_cn_walk_group), written or not.  A
+ * row that does not fit and that walk_reverse sends to the target's side (its counts live in wc) reports no cn2 entry:
+ * cnt1[e] and the n1 column of hist are complete, cnt2[e] is 0 and hist receives neither n2 nor walks from it (n_union
+ * counts its cn1 entries). */
 int32_t ocn_walk_chunk(void);
 int ocn_cn_walk_flags(const int64_t* rowptrA, const int32_t* colA, const int64_t* nds /* or NULL */,
                       const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
                       const int64_t* chunk_off, const int64_t* rev_off /* NULL iff nds is */, const int64_t* off,
-                      int64_t max_row_len /* longest row of A: sizes the LDS set; <= 0 = unknown */,
+                      int64_t max_row_len /* unused (kept for the ABI): the LDS copy of the probed row is fixed at 4096 entries */,
                       uint8_t* flags, int32_t* wc, int64_t flags_cap,
                       uint64_t* hist /* [N][2] */, int32_t* cnt1, int32_t* cnt2,
                       int32_t* status, void* stream);
@@ -247,7 +255,9 @@ int ocn_walk_rev_offsets(const int64_t* rowptrA, const int64_t* nds, const int64
                          void* stream);
 
 /* Small batches of the walk route (B <= ocn_walk_prep_max_batch(): the ppa / citation2 drivers use 2048) — everything in
- * front of the walk kernels in ONE single-workgroup launch: order[] = the batch rows sorted by (source, batch row); off =
+ * front of the walk kernels in ONE single-workgroup launch: order[] = a permutation of the batch rows in which the rows of
+ * one source are contiguous (the sources in the order of their slots in a hash table, a source's rows in whatever order the
+ * atomics gave them: neither is sorted, and no consumer needs more than the contiguity); off =
  * flag offsets (as ocn_edge_offsets); groups = runs of equal source cut into pieces of 64 (g_head[g] = first slot of
  * group g, g_head[n_groups] = B, meta[0] = n_groups); the members of a group whose target has at most 512 neighbours go
  * to the shared sweep ocn_cn_walk_group if their targets' rows sum to at most 4096 entries — if at least `min_share`
@@ -261,6 +271,11 @@ int ocn_walk_rev_offsets(const int64_t* rowptrA, const int64_t* nds, const int64
  * group's targets it neighbours).  Same outputs as ocn_cn_walk_flags, for the candidates of the shared groups; run it
  * after ocn_cn_walk_flags of the same batch (which handles the others and zeroes wc). */
 int32_t ocn_walk_prep_max_batch(void);
+/* The hashes of the walk route, computed on the host by the functions the kernels call.  which = 0: bit of `node` in the
+ * Bloom bitmap of the per-candidate sweeps (0 .. 2^17 - 1); 1: its bit in the shared sweep's bitmap (0 .. 2^17 - 1); 2: its
+ * home slot in the shared sweep's key table and in ocn_walk_prep's source table (0 .. 8191; both probe linearly and wrap).
+ * Another `which`: OCN_EINVAL.  For tests that must construct Bloom false positives and probe chains across the wrap. */
+int32_t ocn_walk_hash(int32_t which, int32_t node);
 int ocn_walk_prep(const int64_t* rowptrA, const int64_t* nds /* or NULL */, const int64_t* src, const int64_t* dst,
                   int64_t B, int32_t min_share, int64_t* order, int64_t* off, int64_t* chunk_off,
                   int64_t* rev_off /* NULL iff nds is */, int32_t* g_head /* [B+1] */, int64_t* g_item_off /* [B+1] */,

@@ -13,7 +13,7 @@
 // true hits (~1 % of the swept elements) plus the false positives — are queued in LDS and resolved in
 // bulk, one per thread, by binary search in the sorted CSR row; done inline that search would run with
 // a handful of live lanes on nearly every wave iteration.
-constexpr int WALK_BM_BITS = 17;
+// (WALK_BM_BITS and the hash walk_bit: common.h)
 #define WALK_BM_WORDS (1 << (WALK_BM_BITS - 5))
 constexpr int WALK_Q = 1024;      /* queue entries; flushed when half full, overflow resolves in place */
 // The probed row itself is kept in LDS beside its bitmap (it passes through the workgroup's hands anyway when the bitmap
@@ -23,7 +23,6 @@ constexpr int WALK_Q = 1024;      /* queue entries; flushed when half full, over
 // (128 Kbit: twice the false positives, each now one cheap LDS search).
 constexpr int WALK_SET = 4096;
 
-__device__ __forceinline__ unsigned walk_bit(int32_t v) { return ((unsigned)v * 2654435761u) >> (32 - WALK_BM_BITS); }
 __device__ __forceinline__ void walk_bm_add(unsigned* bm, int32_t v) {
   const unsigned b = walk_bit(v);
   atomicOr(&bm[b >> 5], 1u << (b & 31));

@@ -187,6 +187,10 @@ __device__ __forceinline__ i64 walk_group(const i64* __restrict__ nds, i64 i, i6
   return cg < 1 ? 1 : (cg > chunks ? chunks : cg);
 }
 
+// bit of a node in the per-candidate sweeps' Bloom bitmap (cn_walk.hip; walk_group.hip hands it to the host: ocn_walk_hash)
+constexpr int WALK_BM_BITS = 17;
+__host__ __device__ __forceinline__ unsigned walk_bit(int32_t v) { return ((unsigned)v * 2654435761u) >> (32 - WALK_BM_BITS); }
+
 // batch slot of a work item: last slot with item_off[slot] <= item (item_off[0] = 0 <= item <
 // item_off[B]).  Called by one whole wave: 64 probes per round instead of a dependent chain of
 // log2(B) single loads (2 rounds for B = 2048, 3 for 65 536).  (cn_walk.hip, cn3_flags.hip: the items of ocn_chunk_offsets)

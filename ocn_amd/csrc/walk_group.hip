@@ -9,7 +9,8 @@
 // keeps the common case (m neighbours none of the targets) at one LDS read.
 //
 // ocn_walk_prep replaces the launch chain in front of the walk kernels for small batches (B <= 4096: the drivers
-// use 2048): ONE single-workgroup launch sorts the candidates by source (LDS bitonic sort), scans the flag offsets,
+// use 2048): ONE single-workgroup launch groups the candidates by source (a hash table in LDS: the rows of a source end up
+// contiguous, neither the sources nor a source's rows sorted), scans the flag offsets,
 // forms the groups and decides per group whether it goes to the shared sweep (>= 2 members, target rows that fit
 // the table) or to the per-candidate two-sided kernels of cn_walk.hip, scans the three work-item lists and clears
 // the per-candidate counters.
@@ -25,6 +26,11 @@
 #define WG_BM_WORDS (1 << (WG_BM_BITS - 5))
 #define WG_SWEEP_THREADS 512
 #define WG_CPI_MAX 8                  /* chunks of WG_ROWS rows per work item (the table is built once per item): chosen per batch */
+
+// slot of a node in the 8192-slot open-addressing tables (the sweep's key table and the prep's source table), and its bit in
+// the sweep's Bloom bitmap; ocn_walk_hash hands both to the host
+__host__ __device__ __forceinline__ unsigned wg_hash(int32_t v) { return ((unsigned)v * 2654435761u) >> (32 - 13); }
+__host__ __device__ __forceinline__ unsigned wg_bit(int32_t v) { return ((unsigned)v * 2246822519u) >> (32 - WG_BM_BITS); }
 
 // ---------------------------------------------------------------------------------------------
 // block-wide helpers for the single-workgroup prep kernel (1024 threads)
@@ -99,7 +105,7 @@ __global__ __launch_bounds__(WG_THREADS) void walk_prep_kernel(
   // whatever the atomics decide — the order only fixes bit positions and locality, never a result)
   for (int e = t; e < B; e += WG_THREADS) {
     const int32_t v = (int32_t)src[e];
-    unsigned h = ((unsigned)v * 2654435761u) >> (32 - 13);
+    unsigned h = wg_hash(v);
     for (int probe = 0; probe < WG_TAB; ++probe) {
       const int32_t prev = atomicCAS(&s_tkey[h], -1, v);
       if (prev == -1 || prev == v) break;
@@ -223,9 +229,6 @@ __global__ __launch_bounds__(WG_THREADS) void walk_prep_kernel(
 // ---------------------------------------------------------------------------------------------
 // the shared sweep
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned wg_hash(int32_t v) { return ((unsigned)v * 2654435761u) >> (32 - 13); }
-__device__ __forceinline__ unsigned wg_bit(int32_t v) { return ((unsigned)v * 2246822519u) >> (32 - WG_BM_BITS); }
-
 // mask of the group's targets that neighbour m (0 if none)
 __device__ __forceinline__ u64 wg_lookup(const int32_t* keys, const u64* masks, int32_t m) {
   unsigned h = wg_hash(m);
@@ -443,6 +446,15 @@ static int wg_raise(const void* fn, int bytes) {
 extern "C" {
 
 int32_t ocn_walk_prep_max_batch(void) { return WG_MAX_B; }
+
+int32_t ocn_walk_hash(int32_t which, int32_t node) {
+  switch (which) {
+    case 0: return (int32_t)walk_bit(node);
+    case 1: return (int32_t)wg_bit(node);
+    case 2: return (int32_t)wg_hash(node);
+    default: return OCN_EINVAL;
+  }
+}
 
 int ocn_walk_prep(const int64_t* rowptrA, const int64_t* nds, const int64_t* src, const int64_t* dst, int64_t B,
                   int32_t min_share, int64_t* order, int64_t* off, int64_t* chunk_off, int64_t* rev_off, int32_t* g_head,
