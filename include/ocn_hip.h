@@ -63,7 +63,8 @@ extern "C" {
  *    ocn_cn_flags_cover (the intersection pass with a certificate that T2 is the full A·A of a symmetric A: candidates that are
  *    stored entries of A read no T2; same bits); ocn_cn_gather_h16 (the pooling from a bf16 / f16 embedding table: half the
  *    bytes per row, fp32 sums, bit for bit ocn_cn_gather on the widened table); ocn_walk_hash (the walk route's Bloom and slot
- *    hashes on the host: tests build colliding node ids with the library's own arithmetic). */
+ *    hashes on the host: tests build colliding node ids with the library's own arithmetic); OCN_REC_* / OCN_SCHED_* (names for
+ *    the slot record's fields and the schedule's limits: macros only, no entry added or changed). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -129,10 +130,11 @@ int ocn_batch_prep(const int64_t* rowptrA, const int64_t* src, int64_t B, int64_
 int ocn_order_by_node_finish(const int64_t* node, int64_t B, int64_t n_nodes, int64_t* order, void* workspace,
                              void* stream);
 /* ocn_order_by_node_finish for the pattern route's intersection pass: the scatter that gives a batch row its slot also
- * writes the slot's record (ocn_cn_flags `rec`): words 0 - 2 complete, word 3 = off[e] (`off` as ocn_batch_prep /
- * ocn_edge_offsets left it, on the same stream).  ocn_cn_flags_rec then starts every slot from that one 32-byte load. */
+ * starts the slot's record (laid out under ocn_cn_flags `rec`): words 0 - 2 complete, word 3 = off[e] with no bit above it
+ * (`off` as ocn_batch_prep / ocn_edge_offsets left it, on the same stream).  ocn_cn_flags_rec then starts every slot from
+ * that one 32-byte load. */
 int ocn_order_by_node_finish_rec(const int64_t* node /* src */, const int64_t* dst, const int64_t* rowptrA,
-                                 const int64_t* off, int64_t B, int64_t n_nodes, int64_t* order, uint64_t* rec /* [B][4] */,
+                                 const int64_t* off, int64_t B, int64_t n_nodes, int64_t* order, uint64_t* rec /* [B][OCN_REC_WORDS] */,
                                  void* workspace, void* stream);
 
 /* Forward work-item offsets of the walk route: out[slot] = number of items of the earlier processing
@@ -157,6 +159,20 @@ int ocn_class_order(const int32_t* cnt1, const int32_t* cnt2 /* or NULL */, cons
                     int64_t B, int64_t* order_out, int64_t* inv_out, int64_t* ranges, int64_t* prefix,
                     void* workspace, void* stream);
 
+/* What the intersection pass hands to the pooling.  The slot record (laid out under ocn_cn_flags `rec`; the kernels pack
+ * and unpack it in ocn_amd/csrc/slot_rec.h and nowhere else): */
+#define OCN_REC_WORDS      4    /* 64-bit words per slot */
+#define OCN_REC_LEN_SHIFT 40    /* word 2: row start below, row length from this bit */
+#define OCN_REC_FULL2_BIT 61    /* word 3: flag offset below; cnt2 == row length > 0 */
+#define OCN_REC_HAS1_BIT  62    /* word 3: cnt1 > 0 */
+#define OCN_REC_HAS2_BIT  63    /* word 3: cnt2 > 0 */
+/* ... and the schedule (ocn_cn_flags `gcost`, ocn_gather_schedule): a group is OCN_SCHED_GROUP consecutive slots — a
+ * workgroup of the intersection pass and of the H = 256 pooling; a schedule exists where every one of the OCN_SCHED_EIGHTHS
+ * XCDs gets the same number of whole groups, at most OCN_SCHED_MAX_EIGHTH of them (16-bit ranks of the counting sort). */
+#define OCN_SCHED_GROUP      4
+#define OCN_SCHED_EIGHTHS    8
+#define OCN_SCHED_MAX_EIGHTH 65535
+
 /* Exclusive scan of int32 counts into int64 offsets (out[n] = total). */
 int ocn_scan_i32(const int32_t* in, int64_t n, int64_t* out, void* workspace, void* stream);
 
@@ -169,11 +185,17 @@ int ocn_scan_i32(const int32_t* in, int64_t n, int64_t* out, void* workspace, vo
  * here; must be zero on entry; B < 2^21.  T2 may be NULL (single adjoverlap call).
  * bitmapT2: optional dense bit rows of T2 (row j at bitmapT2 + j*bm_stride_words, bit k = column k;
  * written by ocn_spgemm_pattern_count): membership in the long A² row becomes one probe.
- * rec (or NULL): per processing SLOT a 32-byte record {batch row, src | dst << 32, start of N(src) | length << 40,
- * off | (cnt1 > 0) << 62 | (cnt2 > 0) << 63}: ocn_cn_gather given the same `rec` reads it instead of walking
- * order -> src / dst / off / counts -> rowptr (one dependent load in front of its first gather instead of three).
- * gcost (or NULL): int32[ceil(B / 4)]: per group of four consecutive processing slots the number of cn1 + cn2 entries
- * its candidates have — what the group will cost the pooling; see ocn_gather_schedule.
+ * rec (or NULL): THE SLOT RECORD — per processing SLOT OCN_REC_WORDS 64-bit words (32 bytes, 16-byte aligned):
+ *   word 0: the batch row e = order[slot]
+ *   word 1: src[e] | dst[e] << 32                                  (node ids < 2^31)
+ *   word 2: start of N(src) in colA | its length << OCN_REC_LEN_SHIFT      (nnz < 2^40)
+ *   word 3: off[e] | (cnt2 == length > 0) << OCN_REC_FULL2_BIT | (cnt1 > 0) << OCN_REC_HAS1_BIT | (cnt2 > 0) << OCN_REC_HAS2_BIT
+ * (bit OCN_REC_FULL2_BIT: every position of the source row is a cn2 entry — ocn_cn_gather's `rowsum` shortcut reads it.)
+ * ocn_cn_gather given the same `rec` reads it instead of walking order -> src / dst / off / counts -> rowptr (one
+ * dependent load in front of its first gather instead of three).  ocn_order_by_node_finish_rec starts a record (words
+ * 0 - 2, word 3 = the bare off[e]); this pass finishes it.
+ * gcost (or NULL): int32[ceil(B / OCN_SCHED_GROUP)]: per group of OCN_SCHED_GROUP consecutive processing slots the largest
+ * number of cn1 + cn2 entries one of its candidates has — what the group will cost the pooling; see ocn_gather_schedule.
  * bitmapT1: the same for T1 (ocn_bitrows_from_csr; small dense graphs); rowptrT1 / colT1 may then be NULL.
  * status: device int32[4] (above): OCN_ST_CAP if off[B] > flags_cap (nothing is written past the cap), OCN_ST_SCAN if
  * off[B] is OCN_SCAN_POISON; both also ORed into the sticky word status[3].
@@ -188,9 +210,9 @@ int ocn_cn_flags(const int64_t* rowptrA, const int32_t* colA,
                  const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
                  int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
                  uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
-                 int32_t* status, uint64_t* rec /* [B][4] or NULL */, int32_t* gcost /* [ceil(B/4)] or NULL */, void* stream);
-/* The same pass behind ocn_order_by_node_finish_rec: `order` and `rec` are required, the records arrive with words 0 - 2
- * and the offset written and leave as ocn_cn_flags leaves them; src / dst / rowptrA are then not read per slot.  Every
+                 int32_t* status, uint64_t* rec /* [B][OCN_REC_WORDS] or NULL */, int32_t* gcost /* [ceil(B/OCN_SCHED_GROUP)] or NULL */, void* stream);
+/* The same pass behind ocn_order_by_node_finish_rec: `order` and `rec` are required, the records (ocn_cn_flags `rec`) arrive
+ * started — words 0 - 2 and the bare offset — and leave as ocn_cn_flags leaves them; src / dst / rowptrA are then not read per slot.  Every
  * output is identical to ocn_cn_flags' on the same arguments. */
 int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA,
                      const int64_t* rowptrT1, const int32_t* colT1,
@@ -200,7 +222,7 @@ int ocn_cn_flags_rec(const int64_t* rowptrA, const int32_t* colA,
                      const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
                      int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
                      uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
-                     int32_t* status, uint64_t* rec /* [B][4] */, int32_t* gcost /* [ceil(B/4)] or NULL */, void* stream);
+                     int32_t* status, uint64_t* rec /* [B][OCN_REC_WORDS] */, int32_t* gcost /* [ceil(B/OCN_SCHED_GROUP)] or NULL */, void* stream);
 /* Either of the two (rec_in != 0: ocn_cn_flags_rec) with a certificate on T2.  t2_cover != 0 is the caller's word that T2 —
  * bit rows and CSR alike — is the FULL pattern of A·A and that A (rowptrA / colA, rows sorted) equals its transpose.  Then a
  * candidate (i, j) that is a stored entry of A has every neighbour k of i in T2 row j (the wedge j - i - k), and its cn2
@@ -215,7 +237,7 @@ int ocn_cn_flags_cover(const int64_t* rowptrA, const int32_t* colA,
                        const int64_t* src, const int64_t* dst, const int64_t* order, int64_t B,
                        int64_t n_cols, const int64_t* off, uint8_t* flags, int64_t flags_cap,
                        uint64_t* hist /* [n_cols][2] */, int32_t* cnt1, int32_t* cnt2,
-                       int32_t* status, uint64_t* rec /* [B][4] or NULL */, int32_t* gcost /* [ceil(B/4)] or NULL */,
+                       int32_t* status, uint64_t* rec /* [B][OCN_REC_WORDS] or NULL */, int32_t* gcost /* [ceil(B/OCN_SCHED_GROUP)] or NULL */,
                        int32_t rec_in, int32_t t2_cover, void* stream);
 
 /* The pygho route get_cn1_cn2 (NeighborOverlap_large_ppa.py:147-173, NeighborOverlapCitation2.py:
@@ -343,6 +365,8 @@ int ocn_cn_colsum_exact(const int64_t* rowptrA, const int32_t* colA, const int64
  * cnt1 / cnt2 (or NULL): the per-row CN counts of the intersection pass; a row with neither kind of
  * entry is not walked at all, and with out_row the xcn1 / xcn2 rows the class-major heads never read
  * (no cn1 entry; no entry at all) are not written.
+ * rec (or NULL): the finished slot records of the intersection pass (laid out under ocn_cn_flags `rec`); order, src, dst,
+ * off and the counts are then not read per slot.  perm (or NULL): ocn_gather_schedule's visiting order of the groups.
  * rowsum (or NULL; pattern route with the cn7 weights only — the caller's promise that every cn2 entry has weight
  * exactly 1 and no cn1 correction): [N][H] rows (A h)[i] = sum_{k in N(i)} h[k] in ascending column order
  * (ocn_spmm_csr, mode sum).  A candidate whose WHOLE source row is cn2 (cnt2[e] = row length: the target's A^2 row
@@ -364,7 +388,7 @@ int ocn_cn_gather(const int64_t* rowptrA, const int32_t* colA,
  * and so are the skip rules (cnt1 / cnt2 / rec / out_row).  Hence xcn1, xcn2 and xij are bit for bit what ocn_cn_gather
  * leaves for the same table widened to fp32.  There is no `rowsum`: the shortcut wants an fp32 A h, and it adds the same
  * numbers in the same order, so leaving it out changes no bit.  max_row_len is accepted and not used (one form).  rec / perm
- * change the processing order only.  No allocation, no global state, no host synchronisation: the launch can be captured.
+ * (the slot records laid out under ocn_cn_flags `rec`, ocn_gather_schedule's order) change the processing order only.  No allocation, no global state, no host synchronisation: the launch can be captured.
  * H in {16, 32, 64, 128, 256, 512}; h16 must be 16-byte aligned.  NULL required pointers (rowptrA, src, dst, off, weights, h16,
  * the outputs), B < 0, another H, fmt outside {0, 1}: OCN_EINVAL before any HIP call.  B == 0 returns 0. */
 int ocn_cn_gather_h16(const int64_t* rowptrA, const int32_t* colA, const int64_t* src, const int64_t* dst,
@@ -746,10 +770,11 @@ int ocn_mips_topm_i8(const int8_t* query /* [Q][H] */, const int8_t* keys /* [N]
                      int32_t m, int32_t n_split /* 0 = auto */, float* top_val /* [Q][m] */, int64_t* top_node /* [Q][m] */,
                      void* workspace, void* stream);
 
-/* The pooling's visiting order at H = 256 (a workgroup = four candidates = one group of ocn_cn_flags' gcost): candidates
+/* The pooling's visiting order at H = 256 (a workgroup = OCN_SCHED_GROUP candidates = one group of ocn_cn_flags' gcost): candidates
  * differ 100x in cost and the few with hundreds of rows, met late, end the kernel as stragglers (0.206 -> 0.17 ms at the
  * collab shape).  perm[] = inside each XCD's contiguous eighth of the groups, the groups stable-sorted by descending cost:
- * groups of one source keep one cost and stay neighbours (L2).  n_groups = B / 4, a multiple of 8, at most 8 * 65535.
+ * groups of one source keep one cost and stay neighbours (L2).  n_groups = B / OCN_SCHED_GROUP, a multiple of OCN_SCHED_EIGHTHS, at most
+ * OCN_SCHED_EIGHTHS * OCN_SCHED_MAX_EIGHTH (else OCN_EINVAL).
  * segment > 0 (dividing an eighth): the sort runs inside consecutive segments of that many groups instead of over the whole
  * eighth — the sources in flight on an XCD then stay within a narrow range of the source order (what their rows' L2
  * residency depends on) while every segment still starts with its longest jobs; 0 = whole eighths. */

@@ -1,9 +1,9 @@
 // The common-neighbour stage, K1 (pattern route): the intersection pass.  It leaves the flag bytes, the column histogram, the
-// per-candidate counts and — for the pooling (cn_pool.hip) — the slot records and group costs whose layout common.h fixes.
+// per-candidate counts and — for the pooling (cn_pool.hip) — the slot records (slot_rec.h) and the group costs (common.h).
 // See include/ocn_hip.h for the reference call sites.
-#include "common.h"
+#include "slot_rec.h"
 
-// (sorted_has, wave_lds_sync and the slot record / schedule constants: common.h)
+// (sorted_has, wave_lds_sync and the schedule constants: common.h)
 
 // Two-level search of a long row: `samp` (LDS) holds the row's elements at positions (s*n)>>6,
 // s = 0..63; six LDS probes pick the segment, the remaining log2(n/64) probes go to memory.
@@ -38,11 +38,7 @@ __device__ __forceinline__ bool sampled_has(const int32_t* samp, const int32_t* 
 // (ocn_order_by_node_finish_rec): the slot is ONE 32-byte load away instead of order -> src / dst -> rowptr / off.
 #define LH_MAX_COLS 8192
 
-// a value every lane of the wave holds alike, moved to scalar registers (the loads it addresses become scalar too)
-__device__ __forceinline__ i64 wave_uniform(i64 v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(u64)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((u64)v >> 32));
-  return (i64)(((u64)hi << 32) | lo);
-}
+// (wave_uniform: common.h)
 // membership of key in a sorted row of at most 64 entries held one per lane (t = INT_MAX beyond its end): lower bound in
 // six cross-lane reads and one more for the element itself.  Every lane of the wave must call it.
 __device__ __forceinline__ bool lanes_have(int32_t t, int32_t key) {
@@ -109,29 +105,21 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
       e[s] = i[s] = j[s] = a0[s] = da[s] = b0[s] = db[s] = c0[s] = dc[s] = base[s] = 0;
       bm_row[s] = bm1_row[s] = nullptr;
     }
-    // NS > 1: the slots' records are consecutive, so lane l loads word l of them — ONE load for all slots, in two registers
-    // (a 32-byte load per slot would hold sixteen) — and a field is read from its lane
+    // NS > 1: the slots' records are consecutive: one lane-spread load for all of them, a field is read from its lane
     u64 recw = 0;
-    if (RECIN && NS > 1 && gl < 4 * NS && slot[0] + gl / 4 < B) recw = rec[4 * slot[0] + gl];
+    if (RECIN && NS > 1) recw = rec_load_spread<NS>(rec, slot[0], B, gl);
 #pragma unroll
     for (int s = 0; s < NS; ++s)
       if (act[s]) {
         if (RECIN) {
-          u64 w[4];
-          if (NS == 1) {
-            const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(rec + 4 * slot[s]);
-            const ulonglong2 ra = rp[0], rb = rp[1];
-            w[0] = ra.x; w[1] = ra.y; w[2] = rb.x; w[3] = rb.y;
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              w[q] = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)recw, 4 * s + q) |
-                     ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(recw >> 32), 4 * s + q) << 32);
-          }
-          e[s] = wave_uniform((i64)w[0]);
-          i[s] = wave_uniform((i64)(w[1] & 0xffffffffull)); j[s] = wave_uniform((i64)(w[1] >> 32));
-          a0[s] = wave_uniform((i64)(w[2] & ((1ull << REC_LEN_SHIFT) - 1))); da[s] = wave_uniform((i64)(w[2] >> REC_LEN_SHIFT));
-          base[s] = wave_uniform((i64)w[3]);
+          u64 w[OCN_REC_WORDS];
+          if (NS == 1) rec_load(rec, slot[s], w); else rec_spread_words(recw, s, w);
+          // (field by field into scalar registers: unpacked into a struct first, the NS = 2 instances keep their instruction
+          // count but not their schedule)
+          e[s] = wave_uniform(rec_row(w));
+          i[s] = wave_uniform(rec_src(w)); j[s] = wave_uniform(rec_dst(w));
+          a0[s] = wave_uniform(rec_start(w)); da[s] = wave_uniform(rec_len(w));
+          base[s] = wave_uniform(rec_base_started(w));
         } else {                              // (no records: small batches and training — a slot's chain runs on its own)
           e[s] = order ? order[slot[s]] : slot[s];
           i[s] = src[e[s]]; j[s] = dst[e[s]];
@@ -273,13 +261,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_flags_kernel(
         cnt1[e[s]] = c1[s];
         if (cnt2) cnt2[e[s]] = c2[s];
         if (rec) {                              // what the pooling needs to know about this slot, in ONE 32-byte record
-          u64* r = rec + 4 * slot[s];
-          if (!RECIN) {
-            r[0] = (u64)e[s];
-            r[1] = (u64)i[s] | ((u64)j[s] << 32);
-          }
-          if (!RECIN || void_batch) r[2] = (u64)a0[s] | ((u64)da[s] << REC_LEN_SHIFT);
-          r[3] = (u64)base[s] | ((u64)(da[s] > 0 && (i64)c2[s] == da[s]) << REC_FULL2_BIT) | ((u64)(c1[s] > 0) << 62) | ((u64)(c2[s] > 0) << 63);
+          u64* r = rec_at(rec, slot[s]);
+          if (!RECIN) rec_pack_head(r, e[s], i[s], j[s], a0[s], da[s]);
+          else if (void_batch) r[2] = rec_word2(a0[s], da[s]);      // (a started record's length is the real one)
+          r[3] = rec_word3(base[s], da[s] > 0 && (i64)c2[s] == da[s], c1[s] > 0, c2[s] > 0);
         }
       }
     if (gcost) {

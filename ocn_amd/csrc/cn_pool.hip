@@ -1,7 +1,8 @@
 // The common-neighbour stage, K3 forward: the pooling of cn5 / cn7 (packed, wave, long-row and generic forms) and the
 // three-vector pooling of cn6.  The slot records it reads are the intersection pass's (cn_flags.hip), the visiting order
-// cn_sched.hip's; common.h fixes their layout.  See include/ocn_hip.h for the reference call sites.
+// cn_sched.hip's; slot_rec.h and common.h (sched_followed) fix them.  See include/ocn_hip.h for the reference call sites.
 #include "lane_group.h"
+#include "slot_rec.h"
 
 // ---------------------------------------------------------------------------------------------
 // K3: pooling — gather embedding rows over the flagged neighbours
@@ -137,12 +138,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_kernel(
   i64 e, i, j, a0, da, base;
   bool has1, has2, full2;
   if (rec) {
-    const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(rec + 4 * slot);
-    const ulonglong2 ra = rp[0], rb = rp[1];
-    e = (i64)ra.x; i = (i64)(ra.y & 0xffffffffull); j = (i64)(ra.y >> 32);
-    a0 = (i64)(rb.x & ((1ull << REC_LEN_SHIFT) - 1)); da = (i64)(rb.x >> REC_LEN_SHIFT);
-    base = (i64)(rb.y & ((1ull << REC_FULL2_BIT) - 1)); has1 = (rb.y >> 62) & 1ull; has2 = rb.y >> 63;
-    full2 = rowsum && ((rb.y >> REC_FULL2_BIT) & 1ull);
+    const slot_rec r = rec_read_finished(rec, slot);
+    e = r.e; i = r.i; j = r.j; a0 = r.a0; da = r.da;
+    base = r.base; has1 = r.has1; has2 = r.has2;
+    full2 = rowsum && r.full2;
   } else {
     e = order ? order[slot] : slot;
     i = src[e]; j = dst[e];
@@ -303,26 +302,25 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_pair_kernel(
   if (perm) grp = perm[grp];                 // (the launch passes a schedule only where an eighth is whole pairs of groups)
   const i64 slot0 = grp * SCHED_GROUP + 2 * (w & 1);
   if (slot0 >= B) return;                    // whole wave leaves together
-  // both records in one load: lane l holds word l of the eight
+  // both records in one load: lane l holds word l of the eight.  (slot_rec.h's rec_load_spread<NS>, then per slot
+  // rec_unpack_finished, restated: through the former this kernel comes out 2 instructions longer, through the latter — or
+  // through the per-field functions — 28, and is no longer the measured one.  Every constant is slot_rec.h's.)
   u64 recw = 0;
-  if (lane < 4 * NS && slot0 + (lane >> 2) < B) recw = rec[4 * slot0 + lane];
+  if (lane < OCN_REC_WORDS * NS && slot0 + (lane >> 2) < B) recw = rec[OCN_REC_WORDS * slot0 + lane];
   // A slot that takes no part (past the batch's end, or a row of cn_gather_long_kernel's, which writes all three output
   // rows) keeps zeros: the endpoint rows loaded for it below are row 0's and are never stored.
   i64 e[NS], i[NS], j[NS], a0[NS], base[NS], n[NS];
   bool live[NS], has1[NS], has2[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    u64 q[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      q[t] = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)recw, 4 * s + t) |
-             ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(recw >> 32), 4 * s + t) << 32);
-    const i64 da = (i64)(q[2] >> REC_LEN_SHIFT);
+    u64 q[OCN_REC_WORDS];
+    rec_spread_words(recw, s, q);
+    const i64 da = (i64)(q[2] >> OCN_REC_LEN_SHIFT);
     live[s] = slot0 + s < B && da <= LONG_ROW;
     e[s] = live[s] ? (i64)q[0] : 0;
     i[s] = live[s] ? (i64)(q[1] & 0xffffffffull) : 0; j[s] = live[s] ? (i64)(q[1] >> 32) : 0;
-    a0[s] = (i64)(q[2] & ((1ull << REC_LEN_SHIFT) - 1));
-    base[s] = (i64)(q[3] & ((1ull << REC_FULL2_BIT) - 1)); has1[s] = (q[3] >> 62) & 1ull; has2[s] = q[3] >> 63;
+    a0[s] = (i64)(q[2] & REC_LEN_MASK);
+    base[s] = (i64)(q[3] & REC_BASE_MASK); has1[s] = (q[3] >> OCN_REC_HAS1_BIT) & 1ull; has2[s] = q[3] >> OCN_REC_HAS2_BIT;
     n[s] = live[s] && (has1[s] | has2[s]) ? da : 0;       // positions to walk: none for a candidate without CN entries
   }
   const bool same = live[0] && live[1] && i[0] == i[1];   // one source: one row of A (its start and length agree)
@@ -877,9 +875,7 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
                           const int32_t* wc, const float* weights, const float* h, int32_t H, int64_t max_row_len,
                           float* xcn1, float* xcn2, float* xij, const int64_t* out_row, const int32_t* cnt1,
                           const int32_t* cnt2, const uint64_t* rec, const int32_t* perm, const float* rowsum, hipStream_t st) {
-  const i64 epb = lane_group_epb(LPE);
-  // the schedule's groups are the workgroups of the intersection pass: usable where the pooling's workgroups are the same
-  const bool sched = perm && rec && epb == SCHED_GROUP && ((B + epb - 1) / epb) % 8 == 0;
+  const int32_t* sched = sched_followed(perm, rec, B, LPE);      // the schedule to follow, or nullptr (common.h)
   bool packed = true;
   if constexpr (LPE <= 16) {
     if (B * LPE < 262144) {                  // the packed form would not fill the SIMDs
@@ -898,17 +894,17 @@ static void launch_gather(const int64_t* rowptrA, const int32_t* colA, const int
     // two slots per wave (cn_gather_pair_kernel): record-fed pattern batches without the row-sum shortcut, from the bound on.
     // A workgroup is two schedule groups, so a schedule is followed only where an XCD's eighth is whole pairs of groups — an odd
     // eighth keeps the one-slot form; without a schedule the pairs are consecutive groups of the source order.
-    const i64 n_groups = (B + epb - 1) / epb;
-    if (rec && !wc && !rowsum && B >= g_gather_pair_min_batch && (!sched || (n_groups >> 3) % 2 == 0)) {
+    static_assert(lane_group_epb(LPE) == SCHED_GROUP, "the pair form's workgroup: two schedule groups");
+    const i64 n_groups = sched_groups(B);
+    if (rec && !wc && !rowsum && B >= g_gather_pair_min_batch && (!sched || (n_groups / SCHED_EIGHTHS) % 2 == 0)) {
       hipLaunchKernelGGL(cn_gather_pair_kernel, dim3((unsigned)((n_groups + 1) / 2)), dim3(OCN_BLOCK), 0, st, colA, (i64)B, flags,
-                         (const float4*)weights, h, xcn1, xcn2, xij, (const i64*)out_row, (const u64*)rec,
-                         sched ? perm : (const int32_t*)nullptr);
+                         (const float4*)weights, h, xcn1, xcn2, xij, (const i64*)out_row, (const u64*)rec, sched);
       packed = false;
     }
   }
   if (packed)
     hipLaunchKernelGGL((cn_gather_kernel<LPE, NV>), dim3(lane_group_blocks(B, LPE)), dim3(OCN_BLOCK), 0, st,
-                       PACKED_ARGS, sched ? perm : (const int32_t*)nullptr, rowsum);
+                       PACKED_ARGS, sched, rowsum);
 #undef PACKED_ARGS
 #define LONG_ARGS (const i64*)rowptrA, colA, (const i64*)src, (const i64*)dst, (i64)B, (const i64*)off, flags, wc, \
                   (const float4*)weights, h, (int)H, xcn1, xcn2, xij, (const i64*)out_row, cnt2, rowsum

@@ -10,6 +10,7 @@
 // LDS slab or workgroup-per-row pass exists here.  (The fp32 pooling's hub forms buy memory parallelism for such rows; what they
 // would buy a half table has not been measured: DESIGN.md section 4, half-precision tables.)
 #include "lane_group.h"
+#include "slot_rec.h"
 
 constexpr int H16_UNR = 4;                   // embedding rows in flight per lane group (eight where a wave has one candidate)
 
@@ -52,12 +53,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_h16_kernel(
   if (slot >= B) return;                     // whole group leaves together
   i64 e, i, j, a0, da, base;
   bool has1, has2;
-  if (rec) {                                 // the intersection pass's 32-byte slot record (common.h)
-    const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(rec + 4 * slot);
-    const ulonglong2 ra = rp[0], rb = rp[1];
-    e = (i64)ra.x; i = (i64)(ra.y & 0xffffffffull); j = (i64)(ra.y >> 32);
-    a0 = (i64)(rb.x & ((1ull << REC_LEN_SHIFT) - 1)); da = (i64)(rb.x >> REC_LEN_SHIFT);
-    base = (i64)(rb.y & ((1ull << REC_FULL2_BIT) - 1)); has1 = (rb.y >> 62) & 1ull; has2 = rb.y >> 63;
+  if (rec) {                                 // the intersection pass's 32-byte slot record (slot_rec.h)
+    const slot_rec r = rec_read_finished(rec, slot);
+    e = r.e; i = r.i; j = r.j; a0 = r.a0; da = r.da;
+    base = r.base; has1 = r.has1; has2 = r.has2;
   } else {
     e = order ? order[slot] : slot;
     i = src[e]; j = dst[e];
@@ -160,8 +159,7 @@ int ocn_cn_gather_h16(const int64_t* rowptrA, const int32_t* colA, const int64_t
 #define LAUNCH_H16(LPE, NV)                                                                              \
   {                                                                                                      \
     const unsigned blocks = lane_group_blocks(B, LPE);                                                   \
-    /* the schedule's groups are the intersection pass's workgroups: followed where the pooling's are the same */ \
-    const int32_t* sched = perm && rec && lane_group_epb(LPE) == SCHED_GROUP && blocks % 8 == 0 ? perm : nullptr; \
+    const int32_t* sched = sched_followed(perm, rec, B, LPE);      /* the schedule to follow, or nullptr (common.h) */ \
     if (fmt == 0) LAUNCH_H16_FMT(LPE, NV, 0); else LAUNCH_H16_FMT(LPE, NV, 1);                           \
   }
   OCN_SWITCH_WIDTH(H, LAUNCH_H16)

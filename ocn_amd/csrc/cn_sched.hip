@@ -9,6 +9,7 @@ extern "C" {
 // buckets of its contiguous share, the bucket-major table of counts is scanned, and the second pass writes every group
 // to its rank.  Stable: groups of one source (one cost) stay neighbours.
 #define SCHED_BUCKETS 64
+static_assert(SCHED_MAX_EIGHTH <= 0xffff, "gather_schedule_kernel: ranks inside an eighth are unsigned short");
 // `per`: groups per sorted range — an XCD's whole eighth, or a SEGMENT of it (ocn_gather_schedule `segment`): longest first inside
 // segments keeps the sources in flight on an XCD within a narrow id range (their rows then meet in its L2) and still starts
 // every segment with its long jobs.
@@ -50,10 +51,10 @@ __global__ __launch_bounds__(OCN_BLOCK) void gather_schedule_kernel(const int32_
 }
 
 int ocn_gather_schedule(const int32_t* gcost, int64_t n_groups, int64_t segment, int32_t* perm, void* stream) {
-  if (n_groups < 0 || (n_groups & 7) || (n_groups >> 3) > 65535 || segment < 0) return OCN_EINVAL;      // eighths; ranks are 16-bit
+  if (n_groups < 0 || n_groups % SCHED_EIGHTHS || n_groups / SCHED_EIGHTHS > SCHED_MAX_EIGHTH || segment < 0) return OCN_EINVAL;      // (common.h)
   if (n_groups == 0) return 0;
   if (!gcost || !perm) return OCN_EINVAL;
-  i64 per = n_groups >> 3;
+  i64 per = n_groups / SCHED_EIGHTHS;
   if (segment > 0 && segment < per && per % segment == 0) per = segment;      // (a segment that does not divide the eighth: whole eighths)
   hipLaunchKernelGGL(gather_schedule_kernel, dim3((unsigned)(n_groups / per)), dim3(OCN_BLOCK), 0, (hipStream_t)stream, gcost, per, perm);
   return launch_status();

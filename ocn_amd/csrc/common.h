@@ -20,18 +20,18 @@ __device__ __forceinline__ int hf_n2(u64 w) { return (int)((w >> HF_BITS) & HF_M
 __device__ __forceinline__ int hf_nu(u64 w) { return (int)((w >> (2 * HF_BITS)) & HF_MASK); }
 
 // ---------------------------------------------------------------------------------------------
-// the contract between the intersection pass (cn_flags.hip; scan.hip writes the record's first half) and the pooling
-// (cn_pool.hip): the slot record layout and the schedule's cost unit
+// the contract between the intersection pass (cn_flags.hip; scan.hip starts the records) and the pooling (cn_pool.hip,
+// cn_pool_h16.hip): the slot record — slot_rec.h, all of it — and the schedule: its cost unit, its groups, and when a
+// visiting order exists and is followed (sched_followed, below lane_group_epb)
 // ---------------------------------------------------------------------------------------------
-#define REC_LEN_SHIFT 40                     /* slot record word 2 (ocn_hip.h: ocn_cn_flags `rec`): row start (nnz < 2^40) | row length << 40 */
-#define REC_FULL2_BIT 61     /* record word 3: every position of the source row is a cn2 entry (cnt2 == row length) */
 // a group's cost: the largest entry count among its four candidates (a wave walks one candidate), in buckets of 32 —
 // measured at the collab shape (pooling): sum / max and 4 .. 256-entry buckets all land within
 // 0.184 - 0.200 ms against 0.206 unscheduled; coarse buckets keep more of the source order's L2 locality
 #define SCHED_COST(t, c) ((t) > (c) ? (t) : (c))
 constexpr int SCHED_SHIFT = 5;
 constexpr int POOL_LPE = 64;    /* lanes per candidate of the H = 256 pooling (64: one candidate per wave) */
-#define SCHED_GROUP OCN_WPB    /* slots per scheduling group: a workgroup of the intersection pass == one of the H = 256 pooling */
+#define SCHED_GROUP OCN_SCHED_GROUP    /* slots per scheduling group: a workgroup of the intersection pass == one of the H = 256 pooling */
+static_assert(SCHED_GROUP == OCN_WPB, "a schedule group is a workgroup's waves, one slot each");
 
 // cn5 / cn6: nip = innerprod / scale from the column statistics word (cn5_column_stats: 0 = no union entry,
 // -1 = union entries but no column with n1 >= 2, else min{n1 >= 2} - INT_MAX - 1); model.py:2370-2376
@@ -75,6 +75,15 @@ static inline bool lane_group_width(int H) { return H == 16 || H == 32 || H == 6
 // candidates per workgroup, and the workgroups of a batch of B
 constexpr i64 lane_group_epb(int lpe) { return (i64)OCN_WPB * (OCN_WAVE / lpe); }
 static inline unsigned lane_group_blocks(i64 B, int lpe) { return (unsigned)((B + lane_group_epb(lpe) - 1) / lane_group_epb(lpe)); }
+// The schedule's rule.  A batch of B slots is sched_groups(B) groups; ocn_gather_schedule orders them where every XCD's
+// eighth is the same whole number of groups, at most SCHED_MAX_EIGHTH (the counting sort's ranks are 16-bit) ...
+constexpr i64 SCHED_EIGHTHS = OCN_SCHED_EIGHTHS, SCHED_MAX_EIGHTH = OCN_SCHED_MAX_EIGHTH;
+static inline i64 sched_groups(i64 B) { return (B + SCHED_GROUP - 1) / SCHED_GROUP; }
+// ... and a pooling launch with `lpe` lanes per candidate follows `perm` where it reads the slot records and its workgroups
+// are those groups (the intersection pass's workgroups); else nullptr.  (The kernels test gridDim.x & 7 themselves.)
+static inline const int32_t* sched_followed(const int32_t* perm, const void* rec, i64 B, int lpe) {
+  return perm && rec && lane_group_epb(lpe) == SCHED_GROUP && sched_groups(B) % SCHED_EIGHTHS == 0 ? perm : nullptr;
+}
 // a T1 / T2 operand: bit rows that cover n_cols columns, or both CSR arrays
 static inline bool set_operand_ok(const void* bitmap, i64 stride_words, const void* rowptr, const void* col, i64 n_cols) {
   return bitmap ? stride_words * 32 >= n_cols : (rowptr && col);
@@ -106,6 +115,12 @@ __device__ __forceinline__ T wave_readlane64(T v, int l) {
   static_assert(sizeof(T) == 8, "wave_readlane64: a 64-bit integer");
   const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), l);
   return (T)(((u64)hi << 32) | lo);
+}
+
+// a value every lane of the wave holds alike, moved to scalar registers (the loads it addresses become scalar too)
+__device__ __forceinline__ i64 wave_uniform(i64 v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(u64)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((u64)v >> 32));
+  return (i64)(((u64)hi << 32) | lo);
 }
 
 // exclusive scan of one value per thread over a 256-thread block; returns the thread's prefix and

@@ -1,5 +1,5 @@
 // Exclusive scans: batch-row offsets (deg of src per edge) and int32 counts -> int64 offsets.
-#include "common.h"
+#include "slot_rec.h"
 
 // ---------------------------------------------------------------------------------------------
 // scans (edge offsets, row offsets)
@@ -299,9 +299,7 @@ __global__ __launch_bounds__(OCN_BLOCK) void order_scatter_rec(const i64* __rest
     const i64 slot = poisoned ? e : (i64)atomicAdd(cursor + v, 1ull);
     order[slot] = e;
     counts[v] = 0;
-    ulonglong2* r = reinterpret_cast<ulonglong2*>(rec + 4 * slot);
-    r[0] = make_ulonglong2((u64)e, (u64)v | ((u64)j << 32));
-    r[1] = make_ulonglong2((u64)a0 | ((u64)da << REC_LEN_SHIFT), (u64)base);
+    rec_pack_started(rec_at(rec, slot), e, v, j, a0, da, base);
   }
 }
 

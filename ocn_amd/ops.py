@@ -127,6 +127,20 @@ def refuse_half_table(t, what: str) -> None:
 
 
 ST_CAP, ST_SCAN = 1, 2           # include/ocn_hip.h: OCN_ST_CAP, OCN_ST_SCAN (bits of status[0] and of the sticky status[3])
+REC_WORDS = 4                    # include/ocn_hip.h: OCN_REC_WORDS (int64 words of a slot record)
+SCHED_GROUP, SCHED_EIGHTHS, SCHED_MAX_EIGHTH = 4, 8, 65535     # include/ocn_hip.h: OCN_SCHED_* (the pooling's schedule)
+SCHED_H = 256                    # the width whose pooling workgroups are the schedule's groups
+
+
+def sched_words(B: int) -> int:
+    """int32 words of a batch's ``sched`` buffer: the group costs of the intersection pass, then room for the visiting order."""
+    return 2 * ((B + SCHED_GROUP - 1) // SCHED_GROUP)
+
+
+def sched_groups(B: int, H: int) -> int:
+    """Schedule groups of ``B`` candidates pooled at width ``H`` where a visiting order exists and is followed, else 0."""
+    n, rest = divmod(B, SCHED_GROUP * SCHED_EIGHTHS)      # whole groups, the same number in every XCD's eighth
+    return n * SCHED_EIGHTHS if (H == SCHED_H and rest == 0 and 0 < n <= SCHED_MAX_EIGHTH) else 0
 
 
 def _total(t: Tensor) -> int:
@@ -354,7 +368,7 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     """Intersection pass.  ``walk=False``: flags of N(src) against the rows of dst in t1 (and t2).
     ``walk=True``: the pygho route on A itself (t1/t2 ignored): cn1 flags + walk counts; with ``nds``
     (``neighbor_degree_sum`` of A) every batch row is swept from its cheaper endpoint.
-    ``rec`` (int64 [B, 4], pattern route): receives the per-slot records ``cn_gather`` reads instead of walking
+    ``rec`` (int64 [B, REC_WORDS], pattern route): receives the per-slot records ``cn_gather`` reads instead of walking
     order -> src / dst / off / counts -> rowptr.
     ``t2_certified``: t2 is the complete pattern of A·A and A equals its transpose (``SparseTensor.covers``: the caller's
     word, not checked here) — with ``ops.t2_cover`` on, candidates that are stored entries of A then read no T2; same outputs.
@@ -391,8 +405,8 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     # the flag offsets, the counting phase of the order and the batch's resets: ONE launch (ocn_batch_prep)
     zs = [t for t in [hist, status[:3], scal] + ([cnt1, cnt2] if walk else []) if t is not None and t.numel()]     # (status[3]: sticky)
     if sched is not None:             # group costs for the pooling's schedule (ocn_hip.h: ocn_cn_flags `gcost`): first half of `sched`
-        if rec is None or walk or _req(sched, torch.int32, "sched", 1).numel() < 2 * ((B + 3) // 4):
-            raise ValueError("sched: int32[2 * ceil(B / 4)] beside the slot records of the pattern route")
+        if rec is None or walk or _req(sched, torch.int32, "sched", 1).numel() < sched_words(B):
+            raise ValueError("sched: int32[sched_words(B)] beside the slot records of the pattern route")
     zp = (ctypes.c_void_p * len(zs))(*[t.data_ptr() for t in zs])
     zb = (ctypes.c_int64 * len(zs))(*[t.numel() * t.element_size() for t in zs])
     check(_lib.lib().ocn_batch_prep(ptr(rowptrA), ptr(src), B, ptr(off), ptr(sws), n_src, ptr(ows), zp, zb, len(zs),
@@ -400,8 +414,8 @@ def cn_flags(rowptrA: Tensor, colA: Tensor, t1: Optional[Tuple[Tensor, Tensor]],
     rec_in = want_order and rec is not None and not walk      # the scatter that orders the batch starts the slot records too
     if rec_in:
         _req(dst, torch.int64, "dst", 1)
-        if _req(rec, torch.int64, "rec").numel() < 4 * B:
-            raise ValueError("rec: int64 [B, 4]")
+        if _req(rec, torch.int64, "rec").numel() < REC_WORDS * B:
+            raise ValueError("rec: int64 [B, REC_WORDS]")
         check(_lib.lib().ocn_order_by_node_finish_rec(ptr(src), ptr(dst), ptr(rowptrA), ptr(off), B, n_src, ptr(order), ptr(rec),
                                                       ptr(ows), stream_ptr()), "ocn_order_by_node_finish_rec")
     elif want_order:
@@ -636,9 +650,9 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
     if rowsum is not None and (wc is not None or cnt2 is None or _req(rowsum, torch.float32, "rowsum", 2).shape != h.shape):
         raise ValueError("rowsum: [N, H] row sums of h, pattern route with per-row counts only")
     perm = None
-    if sched is not None and rec is not None and H == 256 and B % 32 == 0 and B // 32 <= 65535:
-        n_groups = B // 4             # the intersection pass left the groups' costs in sched[:n_groups]; their visiting order follows
-        perm = sched[n_groups:]
+    n_groups = sched_groups(B, H) if (sched is not None and rec is not None) else 0
+    if n_groups:
+        perm = sched[n_groups:]       # the intersection pass left the groups' costs in sched[:n_groups]; their visiting order follows
         if not sched_ready:           # (a scoring loop's phase A has run gather_schedule already)
             check(_lib.lib().ocn_gather_schedule(ptr(sched), n_groups, int(sched_segment), ptr(perm), stream_ptr()), "ocn_gather_schedule")
     _mark("cn_pre")                   # (stage timers: what sits between the intersection pass and the pooling on this stream)
@@ -1434,11 +1448,11 @@ R_CN1, R_BOTH, R_CN2_ONLY, R_ANY, R_NONE, R_CN1_ONLY, R_ALL = range(CLASS_RANGES
 
 @_on_device
 def gather_schedule(sched: Tensor, B: int) -> bool:
-    """The pooling's longest-first visiting order from the group costs the intersection pass left in ``sched[:B // 4]``
-    (ocn_gather_schedule) into ``sched[B // 4:]``; False where the schedule does not apply (cn_gather's own conditions)."""
-    if sched is None or B % 32 != 0 or B // 32 > 65535 or B == 0:
+    """The pooling's longest-first visiting order from the group costs the intersection pass left in ``sched[:n_groups]``
+    (ocn_gather_schedule) into ``sched[n_groups:]``; False where the schedule does not apply (``sched_groups``)."""
+    n_groups = sched_groups(B, SCHED_H) if sched is not None else 0
+    if not n_groups:
         return False
-    n_groups = B // 4
     check(_lib.lib().ocn_gather_schedule(ptr(sched), n_groups, int(sched_segment), ptr(sched[n_groups:]), stream_ptr()), "ocn_gather_schedule")
     _mark("cn_sched")
     return True

@@ -127,9 +127,9 @@ class CNState(_BatchState):
         self.N = adj.size(1)
         ops.check_edges(self.src, self.dst, adj.size(0), adj.size(0) if walk else t1.size(0))
         # per-slot records the intersection pass leaves for the pooling (pattern route)
-        self.rec = None if (walk or self.B == 0) else ops.buf(ws, "rec", (self.B, 4), torch.int64, self.src.device)
-        # ... and what each group of four slots will cost the pooling, for its longest-first schedule (+ room for the schedule)
-        self.sched = (ops.buf(ws, "sched", 2 * ((self.B + 3) // 4), torch.int32, self.src.device)
+        self.rec = None if (walk or self.B == 0) else ops.buf(ws, "rec", (self.B, ops.REC_WORDS), torch.int64, self.src.device)
+        # ... and what each group of ops.SCHED_GROUP slots will cost the pooling, for its longest-first schedule (+ room for the schedule)
+        self.sched = (ops.buf(ws, "sched", ops.sched_words(self.B), torch.int32, self.src.device)
                       if (self.rec is not None and ops.heavy_first and self.B >= ops.sort_edges_min_batch) else None)
         # T2: the bit rows this batch may probe, the row pointers it has (rows on demand: none), the column ids unless deferred
         csr2 = bm2 = None
@@ -269,7 +269,7 @@ class CNState(_BatchState):
 
     def prepare_schedule(self, H: int) -> None:
         """Phase A of a scoring loop: the pooling's visiting order needs the intersection pass only."""
-        if H == 256 and self.sched is not None and self.rec is not None:
+        if self.sched is not None and self.rec is not None and ops.sched_groups(self.B, H):
             self._sched_ready = ops.gather_schedule(self.sched, self.B)
 
     def gather_backward(self, weights: Tensor, h: Tensor, g1: Tensor, g2: Tensor, g3: Tensor) -> Tensor:

@@ -30,6 +30,33 @@ def batch(oadj, B, seed):
     return sample_edges(oadj.row, oadj.col, oadj.n_rows, B, seed=seed)
 
 
+def header_defines():
+    """name -> int of every ``#define OCN_* <integer>`` of include/ocn_hip.h."""
+    import os
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ocn_hip.h")).read()
+    return {k: int(v, 0) for k, v in re.findall(r"^#define\s+(OCN_\w+)\s+\(?(-?(?:0x[0-9a-fA-F]+|\d+))u?\)?\s*(?:/\*.*)?$", txt, re.M)}
+
+
+_REC = header_defines()
+_LEN, _FULL2, _HAS1, _HAS2 = (_REC[k] for k in ("OCN_REC_LEN_SHIFT", "OCN_REC_FULL2_BIT", "OCN_REC_HAS1_BIT", "OCN_REC_HAS2_BIT"))
+
+
+def slot_record(e, i, j, a0, da, base, has1, has2, full2):
+    """The OCN_REC_WORDS int64 words of a slot record (include/ocn_hip.h, ocn_cn_flags ``rec``), as Python ints: the unsigned
+    words of the layout, reinterpreted as int64."""
+    words = [e, i | j << 32, a0 | da << _LEN, base | int(bool(full2)) << _FULL2 | int(bool(has1)) << _HAS1 | int(bool(has2)) << _HAS2]
+    assert len(words) == _REC["OCN_REC_WORDS"] and all(0 <= w < 1 << 64 for w in words)
+    return [w - (1 << 64) if w >> 63 else w for w in words]
+
+
+def slot_record_fields(words):
+    """The inverse of ``slot_record``: (e, i, j, a0, da, base, has1, has2, full2)."""
+    w = [int(x) & ((1 << 64) - 1) for x in words]
+    return (w[0], w[1] & 0xffffffff, w[1] >> 32, w[2] & ((1 << _LEN) - 1), w[2] >> _LEN, w[3] & ((1 << _FULL2) - 1),
+            bool(w[3] >> _HAS1 & 1), bool(w[3] >> _HAS2 & 1), bool(w[3] >> _FULL2 & 1))
+
+
 def spm_equal(prod, spm):
     """product SparseTensor (device) vs oracle SpM: identical pattern."""
     r, c, _ = prod.coo()

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import slot_record
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 HF = 21
@@ -74,10 +76,8 @@ def _expect(A, T1, T2, src, dst, off, order, n_cols, void):
         hist.index_add_(0, row.long(), f1.long() | (f2.long() << HF) | ((f1 | f2).long() << (2 * HF)))
         c1, c2 = int(f1.sum()), int(f2.sum())
         cnt1[e], cnt2[e] = c1, c2
-        w3 = base | (int(row.numel() > 0 and c2 == row.numel()) << 61) | (int(c1 > 0) << 62)
-        if c2 > 0:
-            w3 -= 1 << 63                                           # bit 63 of the unsigned word, as int64
-        rec[slot] = torch.tensor([e, i | (j << 32), int(A[0][i]) | (row.numel() << 40), w3])
+        rec[slot] = torch.tensor(slot_record(e, i, j, int(A[0][i]), row.numel(), base, c1 > 0, c2 > 0,
+                                             row.numel() > 0 and c2 == row.numel()))
         cost[slot] = c1 + c2
     return flags, hist, cnt1, cnt2, rec, cost.view(-1, 4).max(1)[0]
 

@@ -9,12 +9,11 @@ the real intersection pass on a 3 000-node graph with three hubs (two of them lo
 batch sizes where the launch takes another path."""
 from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import ocn_oracle as O
-from tests.helpers import batch, product_adj2, to_product
+from tests.helpers import batch, product_adj2, slot_record, to_product
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -84,11 +83,11 @@ def _hand_built(copies, seed):
             e = len(src)
             j = 10 + e
             has1, has2 = int((f & 1).any()), int((f & 2).any())
-            rec.append([e, i | (j << 32), int(rowptr[i]) | (d << 40), off[-1] | (has1 << 62) | (has2 << 63)])
+            rec.append(slot_record(e, i, j, int(rowptr[i]), d, off[-1], has1, has2, False))
             src.append(i); dst.append(j); flags.append(f); off.append(off[-1] + d)
             cost.append(int((f & 1).sum() + ((f >> 1) & 1).sum()))
     B = len(src)
-    rec = torch.from_numpy(np.array(rec, dtype=np.uint64).view(np.int64))
+    rec = torch.tensor(rec, dtype=torch.int64)
     gcost = torch.tensor(cost + [0] * (-B % 4)).view(-1, 4).max(1)[0].to(torch.int32)
     w = torch.rand(N_HAND, 4, generator=g)
     w[:, 1] *= (torch.rand(N_HAND, generator=g) < 0.5)                 # t: zero for half the columns
