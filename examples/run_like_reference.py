@@ -10,6 +10,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
         --gnnedp 0.07 --res --maskinput --batch_size 384
     python examples/run_like_reference.py --dataset cora --epochs 5 --table-dtype bf16    # test() and --recommend pool from a bf16 table of h
+    python examples/run_like_reference.py --dataset cora --epochs 5 --cn-cap 8:1          # ... pooling at most 8 sampled common neighbours per candidate (seed 1)
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-walk   # top-5 of the model without forming A²
@@ -469,7 +470,18 @@ def main(argv=None):
     ap.add_argument("--table-dtype", choices=("fp32", "bf16", "f16"), default="fp32",
                     help="the embedding table the predictor pools from in test() and under --recommend (pipeline.embedding_table): "
                          "bf16 / f16 rows are half the bytes, widened exactly and summed in fp32; training is always fp32")
+    ap.add_argument("--cn-cap", default=None, metavar="D[:SEED]",
+                    help="test() and --recommend pool at most D embedding rows per candidate (predictor.set_cn_cap): a stratified, "
+                         "reweighted sample of its common neighbours, fixed by SEED (default 0); training always pools exactly")
     args = ap.parse_args(argv)
+    if args.cn_cap is not None:
+        parts = args.cn_cap.split(":")
+        if not (1 <= len(parts) <= 2 and all(p.isdigit() for p in parts) and int(parts[0]) >= 1):
+            ap.error("--cn-cap D[:SEED]: D >= 1 rows per candidate, SEED a non-negative integer")
+        if (args.heuristic or args.predictor == "cn6" or args.table_dtype != "fp32" or args.recommend_explain
+                or args.recommend_explain_edges):
+            ap.error("--cn-cap: needs a cn5, cn7 or cn8 model and an fp32 table; the explanations explain the exact pooling")
+        args.cn_cap = (int(parts[0]), int(parts[1]) if len(parts) == 2 else 0)
     if args.table_dtype != "fp32" and (args.predictor == "cn6" or args.recommend_explain or args.recommend_explain_edges
                                        or args.recommend_emb):
         ap.error("--table-dtype bf16 / f16: cn6, --recommend-explain, --recommend-explain-edges and --recommend-emb read fp32 rows")
@@ -573,7 +585,10 @@ def main(argv=None):
         loss = train(model, predictor, data, split_edge, optimizer, args.batch_size, args.maskinput, args, epoch)
         t2 = time.time()
         run_test = test_mrr if evaluator.eval_metric == "mrr" else test
+        if args.cn_cap is not None:                      # --cn-cap: the evaluation pools a capped sample, the next epoch trains exactly
+            predictor.set_cn_cap(*args.cn_cap)
         results, _ = run_test(model, predictor, data, split_edge, evaluator, args.testbs, args.use_valedges_as_input, args)
+        predictor.set_cn_cap(None)
         torch.cuda.synchronize()
         t3 = time.time()
         line = (f"epoch {epoch:3d} loss {loss:.4f} train {t2 - t1:.2f}s test {t3 - t2:.2f}s  " +
@@ -582,6 +597,8 @@ def main(argv=None):
         print(line, flush=True)
         out.append((loss, results))
     if args.recommend:
+        if args.cn_cap is not None:
+            predictor.set_cn_cap(*args.cn_cap)
         recommend(args.recommend, data, split_edge, args, model, predictor)
     return out
 

@@ -64,7 +64,9 @@ extern "C" {
  *    stored entries of A read no T2; same bits); ocn_cn_gather_h16 (the pooling from a bf16 / f16 embedding table: half the
  *    bytes per row, fp32 sums, bit for bit ocn_cn_gather on the widened table); ocn_walk_hash (the walk route's Bloom and slot
  *    hashes on the host: tests build colliding node ids with the library's own arithmetic); OCN_REC_* / OCN_SCHED_* (names for
- *    the slot record's fields and the schedule's limits: macros only, no entry added or changed). */
+ *    the slot record's fields and the schedule's limits: macros only, no entry added or changed); ocn_cn_gather_cap (the
+ *    pooling with at most `cap` sampled, reweighted rows per candidate: an unbiased estimate at a bounded cost; candidates
+ *    within the cap bit for bit ocn_cn_gather's). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -397,6 +399,37 @@ int ocn_cn_gather_h16(const int64_t* rowptrA, const int32_t* colA, const int64_t
                       int32_t fmt /* 0 = bf16, 1 = f16 */, int32_t H, int64_t max_row_len, float* xcn1, float* xcn2,
                       float* xij, const int64_t* out_row, const int32_t* cnt1, const int32_t* cnt2,
                       const uint64_t* rec /* or NULL */, const int32_t* perm /* or NULL */, void* stream);
+/* The CAPPED pooling: ocn_cn_gather with at most `cap` embedding rows per candidate, chosen by a deterministic stratified
+ * sample of the candidate's common-neighbour entries and reweighted so that xcn1 / xcn2 are unbiased estimates of
+ * ocn_cn_gather's.  Every argument up to `perm` means what it means for ocn_cn_gather (fp32 table; there is no `rowsum`).
+ * For candidate e = (i, j), q = off[e] + p over the positions p of row N(i): the MEMBERS are the positions with
+ * flags[q] != 0, ranked r = 0 .. u - 1 in ascending p; d = cap.
+ *   u <= d: every member is selected with multiplier s = 1.
+ *   u >  d: stratum t = 0 .. d - 1 holds the ranks [lo_t, lo_{t+1}), lo_t = ceil(t u / d) (so t(r) = floor(r d / u), and
+ *           the size s_t = lo_{t+1} - lo_t is floor(u / d) or ceil(u / d)); its one selected rank is
+ *           lo_t + floor(W_t s_t / 2^64), W_t = x | y << 32 of Philox4x32-10 at the counter (i, j, t, 7) under the key
+ *           (seed & 0xffffffff, seed >> 32); the selected member carries the multiplier s_t.  The multipliers sum to u and a
+ *           member is selected with probability 1 / s_t (up to the 2^-64 s_t bias of the multiply-high).
+ * A selected entry has (wa, wb) = the entry weights of ocn_cn_gather, then wa' = wa * (float)s and wb' = wb * (float)s, each
+ * rounded once; h[k] is fetched exactly when wa' != 0 or wb' != 0 and then added to both sums, one rounded multiply and one
+ * add per feature, in ascending position: ocn_cn_gather's order, arithmetic and fetch rule.  x * 1.0f is exact, so every
+ * candidate with u <= cap gets, bit for bit, ocn_cn_gather's three rows.  The sample is fixed by (seed, i, j, the
+ * candidate's flags): not by the batch, its order, `rec`, `perm` or the launch geometry.  xij, the skip and the store rules
+ * (cnt1 / cnt2 / rec has-bits / out_row) are ocn_cn_gather_h16's, with the counts of the FULL set: a candidate whose sample
+ * holds no cn1 entry gets a zero xcn1 row where one is stored at all.  With `perm`, the group costs are upper bounds.
+ * mult (or NULL): int32, one word per flag position.  Every position of [off[e], off[e] + len N(src[e])) of every batch
+ * row is written, unwalked candidates included: s for a selected member, 0 for any other position; nothing else — nothing
+ * at or beyond flags_cap where the flag buffer holds the batch (the positions written are the flag positions read).
+ * One form for every row length (a candidate whose source row is longer than `cap` is counted first: one pass over its
+ * flag bytes); max_row_len is accepted and not used.  No atomics, no workspace, no LDS, no host synchronisation.
+ * H in {16, 32, 64, 128, 256, 512}.  cap < 1, B < 0, another H, a NULL required pointer (rowptrA, colA, src, dst, off, flags,
+ * weights, h, the outputs): OCN_EINVAL before any HIP call.  B == 0 returns 0. */
+int ocn_cn_gather_cap(const int64_t* rowptrA, const int32_t* colA, const int64_t* src, const int64_t* dst,
+                      const int64_t* order, int64_t B, const int64_t* off, const uint8_t* flags, const int32_t* wc,
+                      const float* weights /* [N][4] */, const float* h, int32_t H, int64_t max_row_len, float* xcn1,
+                      float* xcn2, float* xij, const int64_t* out_row, const int32_t* cnt1, const int32_t* cnt2,
+                      const uint64_t* rec /* or NULL */, const int32_t* perm /* or NULL */, int32_t cap, uint64_t seed,
+                      int32_t* mult /* [flags_cap] or NULL */, void* stream);
 /* cn8 (CNLinkPredictorbaselearnablation, model.py:3233-3449; pattern route): intersection and pooling in ONE pass.  cn8
  * pools without column weights, so a candidate's vectors depend on nothing but the candidate:
  *   xcn1[e] = sum_{k in N(i) ∩ T1(j)} h[k]   xcn2[e] = sum_{k in N(i) ∩ T2(j)} h[k]   xij[e] = h[i] (.) h[j]

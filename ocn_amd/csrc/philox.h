@@ -1,5 +1,5 @@
 // Philox4x32-10 and the counter streams of everything random in the library: the structured negative samplers
-// (neg_sample.hip) and the random-walk retrieval (rw_retrieve.hip).  One generator, one key rule, one stream word per use.
+// (neg_sample.hip), the random-walk retrieval (rw_retrieve.hip) and the capped pooling's strata (cn_pool_cap.hip).  One generator, one key rule, one stream word per use.
 #pragma once
 #include "common.h"
 
@@ -11,6 +11,7 @@ constexpr unsigned PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 constexpr unsigned SAMPLE_STREAM_PAIRS = 1u, SAMPLE_STREAM_ROWS = 2u;      // counter word 3: the samplers never share a word
 constexpr unsigned SAMPLE_STREAM_TWO_HOP = 3u, SAMPLE_STREAM_TWO_HOP_ID = 4u;
 constexpr unsigned SAMPLE_STREAM_RW_A = 5u, SAMPLE_STREAM_RW_B = 6u;       // random-walk retrieval: steps 1 | 2 of a walk, step 3
+constexpr unsigned SAMPLE_STREAM_CN_CAP = 7u;                              // capped pooling: the pick of stratum t of candidate (i, j)
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
 #pragma unroll

@@ -89,6 +89,8 @@ def _check_request(predictor, h, edges, m, rank, args, what: str = "explain_link
         raise RuntimeError(f"{what} explains eval-mode scores; call predictor.eval() first")
     if predictor._sharded:
         raise RuntimeError("an edge-sharded predictor scores one rank's slice of a batch: explain on an unsharded one")
+    if getattr(predictor, "_cn_cap", None) is not None:
+        raise RuntimeError(f"{what} explains the exact pooling, this predictor pools a capped sample: set_cn_cap(None) first")
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= ops.segment_topk_max_k():
         raise ValueError(f"{count} must be an int in 1..{ops.segment_topk_max_k()}, got {m!r}")
     if rank not in RANKS:

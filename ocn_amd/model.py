@@ -733,6 +733,7 @@ class _CNPredictorBase(nn.Module):
         self._rowsum_cache = None              # cn7: A·h of the live embeddings (_rowsum)
         self._skip_state = None                # per-run state of the zero-row skipping, from the first probe on
         self._frozen = None                    # a FrozenColumns in place of every batch's own column weights (set_frozen_columns)
+        self._cn_cap = None                    # (rows, seed): pool a capped sample of every candidate's entries (set_cn_cap)
 
     def set_frozen_columns(self, fc, args=None):
         """Install the column weights of a reference batch (``ocn_amd.frozen.freeze_columns``) in place of every batch's own, or
@@ -763,6 +764,37 @@ class _CNPredictorBase(nn.Module):
                 raise ValueError(f"the table was frozen with {k} = {getattr(fc, k)}, the predictor has {v}")
         self._frozen = fc
         return before
+
+    def set_cn_cap(self, cap, seed: int = 0):
+        """Pool at most ``cap`` embedding rows per candidate (``ops.cn_gather_cap``), or None to pool exactly again; returns what
+        was set before ((cap, seed) or None).  An opt-in serving mode of cn5 / cn7 / cn8 in eval mode under ``torch.no_grad()``:
+        the rows are a stratified sample of the candidate's common-neighbour entries, fixed by (``seed``, src, dst, the
+        candidate's flags) and reweighted so that the pooled vectors are unbiased estimates of the exact ones; a candidate with at
+        most ``cap`` entries is pooled exactly, bit for bit.  The column statistics and weights stay those of the full
+        intersection pass — the batch's own or a frozen table.  What a candidate costs the pooling is then bounded whatever its
+        degree.  Not part of the ``state_dict``.  With a cap set the one-pass forms (``OCN_CN8_FUSED``, ``OCN_FROZEN_FUSED``) fall
+        to the chain and cn7's row-sum shortcut is dropped; training mode, autograd and an edge-sharded predictor raise
+        RuntimeError, a bf16 / f16 table TypeError, before the batch's first launch."""
+        before = self._cn_cap
+        if cap is None:
+            self._cn_cap = None
+            return before
+        if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap < (1 << 31):
+            raise ValueError(f"cap must be an int >= 1 (rows per candidate) or None, got {cap!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an int in 0 .. 2^64 - 1, got {seed!r}")
+        self._cn_cap = (cap, ops._seed(seed))
+        return before
+
+    def _check_cap(self, x) -> None:
+        """The refusals of a capped predictor, before the batch's first launch."""
+        if self._cn_cap is None:
+            return
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("a capped pooling is the eval path: call .eval() under torch.no_grad(), or set_cn_cap(None) first")
+        if self._sharded:
+            raise RuntimeError("a capped pooling on an edge-sharded predictor is not built")
+        ops.refuse_half_table(x, "a capped pooling (set_cn_cap)")
 
     def _frozen_weights(self, st):
         """The installed table as the weights of batch state ``st`` (the chain's, or the one pass's), checked against it."""
@@ -802,13 +834,14 @@ class _CNPredictorBase(nn.Module):
         """The batch state of (cn1, cn2); a state that pools in its own pass arrives with ``pooled`` set (cn8; cn5 / cn7 with
         frozen column weights on pattern handles, under ``ops.frozen_fused_eval``)."""
         fc = self._frozen
+        self._check_cap(x)
         if fc is not None:
             if self.training or torch.is_grad_enabled():
                 raise RuntimeError("frozen column weights are the eval path: call .eval() under torch.no_grad(), or "
                                    "set_frozen_columns(None) first")
             if self._sharded:
                 raise RuntimeError("frozen column weights on an edge-sharded predictor are not built")
-            if (ops.frozen_fused_eval and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.float32
+            if (ops.frozen_fused_eval and self._cn_cap is None and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.float32
                     and x.shape[1] in ops.LN_WIDTHS):
                 from .utils import fuse8
                 st = fuse8(cn1, cn2, tar_ei, ws, weights=fc.weights)
@@ -941,6 +974,8 @@ class _CNPredictorBase(nn.Module):
             return _PoolFn.apply(x, st, w)
         if not st._cls_decided:
             self._class_order(st, x)
+        if self._cn_cap is not None:           # (no row-sum shortcut: a capped candidate's xcn2 is its sample's)
+            return st.gather(w, x, out_row=None if st.cls is None else st.cls[1], cap=self._cn_cap)
         rs = self._rowsum(st, x)
         if st.cls is not None:
             # (the pooling keeps its own source-sorted, XCD-balanced processing order and only WRITES to the
@@ -1333,8 +1368,9 @@ class CNLinkPredictorbaselearnablation(_CNPredictorBase):
     def _batch_state(self, x, cn1, cn2, tar_ei, ws, adj):
         """The one-pass state, pooled, where it applies (eval, no grad, pattern handles, a width the kernel has); else the
         flag form of cn5 / cn7."""
-        if (ops.cn8_fused_eval and not self.training and not torch.is_grad_enabled() and torch.is_tensor(x) and x.dim() == 2
-                and x.dtype == torch.float32 and x.shape[1] in ops.LN_WIDTHS):
+        self._check_cap(x)
+        if (ops.cn8_fused_eval and self._cn_cap is None and not self.training and not torch.is_grad_enabled()
+                and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] in ops.LN_WIDTHS):
             from .utils import fuse8
             st = fuse8(cn1, cn2, tar_ei, ws)
             if st is not None:
@@ -1373,6 +1409,11 @@ class CNLinkPredictor3hopCNs(_CNPredictorBase):
         self.xcn3lin = nn.Sequential(nn.Linear(in_channels, H), nn.Dropout(p, inplace=True), nn.ReLU(inplace=True),
                                      nn.Linear(H, H), norm, nn.Dropout(p, inplace=True), nn.ReLU(inplace=True),
                                      nn.Linear(H, H))
+
+    def set_cn_cap(self, cap, seed: int = 0):
+        if cap is None:
+            return None
+        raise NotImplementedError("cn6 pools three vectors with three column tables (cn_gather3): a capped pooling of it is not built")
 
     def multidomainforward(self, x, adj, cn1, cn2, cn3, tar_ei, args=None, cndropprobs: Iterable[float] = []):
         from .utils import fuse3

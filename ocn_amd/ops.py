@@ -671,6 +671,47 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
     return out[0], out[1], out[2]
 
 
+@_on_device
+def cn_gather_cap(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights: Tensor, h: Tensor, cap: int, seed: int = 0,
+                  order: Optional[Tensor] = None, max_row_len: int = 0, wsd=None, out_row: Optional[Tensor] = None,
+                  cnt1: Optional[Tensor] = None, cnt2: Optional[Tensor] = None, rec: Optional[Tensor] = None,
+                  sched: Optional[Tensor] = None, sched_ready: bool = False, mult: Optional[Tensor] = None):
+    """The capped pooling (ocn_hip.h: ocn_cn_gather_cap): ``cn_gather`` with at most ``cap`` embedding rows per candidate — a
+    stratified sample of its common-neighbour entries, fixed by (``seed``, src, dst, the candidate's flags) and reweighted so
+    that the pooled vectors are unbiased estimates of the exact ones.  A candidate with at most ``cap`` entries gets the bits
+    of ``cn_gather``.  The same output buffer, schedule and slot records as ``cn_gather``; no ``rowsum``; fp32 tables of the
+    widths ``LN_WIDTHS`` only.  ``mult`` (optional, int32, one word per flag position): receives every position's multiplier
+    — the stratum size of a selected entry, 1 where the candidate is within the cap, 0 for every other position."""
+    refuse_half_table(h, "the capped pooling (cn_gather_cap)")
+    _req(weights, torch.float32, "weights", 2)
+    _req(h, torch.float32, "h", 2)
+    if weights.shape[0] != h.shape[0] or weights.shape[1] != 4:
+        raise ValueError("weights must be [N,4] with N = h.shape[0]")
+    cap = int(cap)
+    if not 1 <= cap < (1 << 31):
+        raise ValueError("cap: at least one row per candidate (an int32)")
+    seed = _seed(seed)
+    B, H = src.numel(), h.shape[1]
+    if H not in LN_WIDTHS:
+        raise NotImplementedError(f"the capped pooling supports hidden widths {LN_WIDTHS}, got {H}")
+    if mult is not None and (_req(mult, torch.int32, "mult", 1).numel() < flags.numel()):
+        raise ValueError("mult: one int32 word per flag position")
+    out = buf(wsd, "pooled", (3, B, H), torch.float32, h.device)
+    perm = None
+    n_groups = sched_groups(B, H) if (sched is not None and rec is not None) else 0
+    if n_groups:
+        perm = sched[n_groups:]       # (the groups' costs are those of the full sets: upper bounds here, which is fine for an order)
+        if not sched_ready:
+            check(_lib.lib().ocn_gather_schedule(ptr(sched), n_groups, int(sched_segment), ptr(perm), stream_ptr()), "ocn_gather_schedule")
+    _mark("cn_pre")
+    check(_lib.lib().ocn_cn_gather_cap(ptr(rowptrA), ptr(colA), ptr(src), ptr(dst), ptr(order), B, ptr(off), ptr(flags),
+                                       ptr(wc), ptr(weights), ptr(h), H, int(max_row_len), ptr(out[0]), ptr(out[1]),
+                                       ptr(out[2]), ptr(out_row), ptr(cnt1), ptr(cnt2), ptr(rec), ptr(perm), cap, seed, ptr(mult),
+                                       stream_ptr()), "ocn_cn_gather_cap")
+    _mark("cn_gather")
+    return out[0], out[1], out[2]
+
+
 _unit_w: dict = {}
 
 

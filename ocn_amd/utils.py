@@ -256,10 +256,17 @@ class CNState(_BatchState):
         return ops.cn_weights_cn7(self.hist, sum_fill, diag1, diag2)
 
     def gather(self, weights: Tensor, h: Tensor, order: Optional[Tensor] = None, out_row: Optional[Tensor] = None,
-               rowsum: Optional[Tensor] = None):
+               rowsum: Optional[Tensor] = None, cap=None, mult: Optional[Tensor] = None):
         """(xcn1, xcn2, x_i * x_j); ``order`` overrides the processing order, ``out_row`` sends batch row e
         to output row out_row[e] (class-major rows for the heads, ops.class_order); ``rowsum`` = A·h for the cn7 weights
-        (ocn_hip.h, ocn_cn_gather: candidates whose whole source row is cn2 copy their xcn2 row)."""
+        (ocn_hip.h, ocn_cn_gather: candidates whose whole source row is cn2 copy their xcn2 row).  ``cap`` = (rows, seed): the
+        capped pooling in its place (``ops.cn_gather_cap``; ``rowsum`` is dropped, ``mult`` receives the multipliers)."""
+        if cap is not None:
+            return ops.cn_gather_cap(self.adj._rowptr, self.adj._col, self.src, self.dst, self.off, self.flags, self.wc, weights, h,
+                                     cap[0], cap[1], order=self.order if order is None else order,
+                                     max_row_len=self.adj.max_rowcount(), wsd=self.ws, out_row=out_row, cnt1=self.cnt1,
+                                     cnt2=self.cnt2, rec=self.rec if order is None else None,
+                                     sched=self.sched if order is None else None, sched_ready=self._sched_ready, mult=mult)
         return ops.cn_gather(self.adj._rowptr, self.adj._col, self.src, self.dst, self.off,
                              self.flags, self.wc, weights, h, order=self.order if order is None else order,
                              max_row_len=self.adj.max_rowcount(), wsd=self.ws, out_row=out_row,
@@ -525,7 +532,8 @@ def adjoverlap(adj1: SparseTensor, adj2: SparseTensor, tarei: Tensor, filled1: b
     """utils.py:248-285.  ``calresadj`` / sampling belong to the cn2-cn4 predictors, which no
     reference driver can call."""
     if calresadj or cnsampledeg > 0 or ressampledeg > 0:
-        raise NotImplementedError("calresadj / neighbour sampling are outside the cn5/cn7 path")
+        raise NotImplementedError("calresadj / neighbour sampling are outside the cn5/cn7 path (a bounded pooling cost with "
+                                  "other semantics than the reference's cnsampledeg: predictor.set_cn_cap)")
     return CNBatch(adj1, adj2, tarei)
 
 
