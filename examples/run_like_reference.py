@@ -10,6 +10,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset citeseer --model puremean --mplayers 3 --nnlayers 1 --hiddim 64 \
         --gnnedp 0.07 --res --maskinput --batch_size 384
     python examples/run_like_reference.py --dataset cora --epochs 5 --table-dtype bf16    # test() and --recommend pool from a bf16 table of h
+    python examples/run_like_reference.py --dataset cora --epochs 5 --table-dtype int8 --cn-cap 32    # ... from int8 rows, capped
     python examples/run_like_reference.py --dataset cora --epochs 5 --cn-cap 8:1          # ... pooling at most 8 sampled common neighbours per candidate (seed 1)
     python examples/run_like_reference.py --dataset cora --heuristic ra        # no training: a classical baseline's metric
     python examples/run_like_reference.py --dataset cora --heuristic ra --recommend 5     # ... and its top-5 targets per source
@@ -45,7 +46,7 @@ from ocn_amd.explain import explain_link_edges, explain_links                   
 from ocn_amd.frozen import freeze_columns                                           # noqa: E402
 from ocn_amd.heuristics import KINDS, TWO_HOP, score_edges_heuristic                # noqa: E402
 from ocn_amd.model import GCN, predictor_dict                                       # noqa: E402
-from ocn_amd.pipeline import embedding_table, score_mrr_split                       # noqa: E402
+from ocn_amd.pipeline import embedding_table, embedding_table_int8, score_mrr_split  # noqa: E402
 from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
 from ocn_amd.recommend import (EmbeddingNeighbours, RandomWalks, ShortListUnion, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
                                three_hop_candidates, two_hop_candidates)
@@ -111,6 +112,11 @@ def train(model, predictor, data, split_edge, optimizer, batch_size, maskinput, 
     return float(torch.stack(total_loss).mean())
 
 
+def _table(h, dtype):
+    """--table-dtype: ``h`` as the table the predictor pools from (pipeline.embedding_table; "int8": embedding_table_int8)."""
+    return embedding_table_int8(h) if dtype == "int8" else embedding_table(h, dtype)
+
+
 @torch.no_grad()
 def test(model, predictor, data, split_edge, evaluator, batch_size, use_valedges_as_input, args):
     model.eval(); predictor.eval()
@@ -121,7 +127,7 @@ def test(model, predictor, data, split_edge, evaluator, batch_size, use_valedges
     adj = data.adj_t
     h = model(data.x, adj)
     adj2 = build_adj2(adj, args)
-    table = lambda h: embedding_table(h, args.table_dtype)        # --table-dtype: cast once per embedding matrix, never per batch
+    table = lambda h: _table(h, args.table_dtype)        # --table-dtype: cast once per embedding matrix, never per batch
 
     def score(e, h, adj):
         return torch.cat([predictor(h, adj, adjoverlap(adj, adj, e[perm].t()), adjoverlap(adj, adj2, e[perm].t()),
@@ -163,7 +169,7 @@ def test_mrr(model, predictor, data, split_edge, evaluator, batch_size, use_vale
             neg = two_hop_negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
         elif args.structured_negatives:
             neg = negative_targets(data.full_adj_t, source, neg.shape[1], seed=seed)
-        out.append(score_mrr_split(predictor, embedding_table(model(data.x, adj), args.table_dtype), adj, source, target, neg, batch_size, args, evaluator))
+        out.append(score_mrr_split(predictor, _table(model(data.x, adj), args.table_dtype), adj, source, target, neg, batch_size, args, evaluator))
     return {'MRR': tuple(out)}, None
 
 
@@ -233,7 +239,7 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
 
     def table(adj):
         # --table-dtype: the embeddings the model requests pool from, cast once per request (pipeline.embedding_table)
-        return embedding_table(state.h if state is not None else model(data.x, adj), args.table_dtype)
+        return _table(state.h if state is not None else model(data.x, adj), args.table_dtype)
 
     def refreshed(adj, edges, tag):
         rows = state.refresh(adj, edges)                  # only the rows the update can reach are recomputed
@@ -467,9 +473,10 @@ def main(argv=None):
     ap.add_argument("--recommend-check-refresh", action="store_true",
                     help="with --recommend-accept and a model: assert that the refreshed node embeddings (ocn_amd.update.EncoderState) "
                          "equal a full encoder pass bit for bit after the insert, and after the undo")
-    ap.add_argument("--table-dtype", choices=("fp32", "bf16", "f16"), default="fp32",
+    ap.add_argument("--table-dtype", choices=("fp32", "bf16", "f16", "int8"), default="fp32",
                     help="the embedding table the predictor pools from in test() and under --recommend (pipeline.embedding_table): "
-                         "bf16 / f16 rows are half the bytes, widened exactly and summed in fp32; training is always fp32")
+                         "bf16 / f16 rows are half the bytes, widened exactly and summed in fp32; int8 rows with a scale per row are "
+                         "a quarter, the image --recommend-emb retrieves from, and may be capped (--cn-cap); training is always fp32")
     ap.add_argument("--cn-cap", default=None, metavar="D[:SEED]",
                     help="test() and --recommend pool at most D embedding rows per candidate (predictor.set_cn_cap): a stratified, "
                          "reweighted sample of its common neighbours, fixed by SEED (default 0); training always pools exactly")
@@ -478,13 +485,14 @@ def main(argv=None):
         parts = args.cn_cap.split(":")
         if not (1 <= len(parts) <= 2 and all(p.isdigit() for p in parts) and int(parts[0]) >= 1):
             ap.error("--cn-cap D[:SEED]: D >= 1 rows per candidate, SEED a non-negative integer")
-        if (args.heuristic or args.predictor == "cn6" or args.table_dtype != "fp32" or args.recommend_explain
+        if (args.heuristic or args.predictor == "cn6" or args.table_dtype not in ("fp32", "int8") or args.recommend_explain
                 or args.recommend_explain_edges):
-            ap.error("--cn-cap: needs a cn5, cn7 or cn8 model and an fp32 table; the explanations explain the exact pooling")
+            ap.error("--cn-cap: needs a cn5, cn7 or cn8 model and an fp32 or int8 table; the explanations explain the exact pooling")
         args.cn_cap = (int(parts[0]), int(parts[1]) if len(parts) == 2 else 0)
     if args.table_dtype != "fp32" and (args.predictor == "cn6" or args.recommend_explain or args.recommend_explain_edges
-                                       or args.recommend_emb):
-        ap.error("--table-dtype bf16 / f16: cn6, --recommend-explain, --recommend-explain-edges and --recommend-emb read fp32 rows")
+                                       or (args.recommend_emb and (args.table_dtype != "int8" or args.recommend_emb.endswith(":cos")))):
+        ap.error("--table-dtype bf16 / f16 / int8: cn6, --recommend-explain, --recommend-explain-edges and --recommend-emb read fp32 "
+                 "rows (int8: --recommend-emb M retrieves from the table itself, M:cos needs the fp32 rows)")
     if not 0.0 <= args.hard_negatives <= 1.0:
         ap.error("--hard-negatives SHARE: a share in [0, 1]")
     if args.recommend_check_refresh and (args.heuristic or not (args.recommend and args.recommend_accept > 0)):

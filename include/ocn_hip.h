@@ -66,7 +66,9 @@ extern "C" {
  *    hashes on the host: tests build colliding node ids with the library's own arithmetic); OCN_REC_* / OCN_SCHED_* (names for
  *    the slot record's fields and the schedule's limits: macros only, no entry added or changed); ocn_cn_gather_cap (the
  *    pooling with at most `cap` sampled, reweighted rows per candidate: an unbiased estimate at a bounded cost; candidates
- *    within the cap bit for bit ocn_cn_gather's). */
+ *    within the cap bit for bit ocn_cn_gather's); ocn_cn_gather_q8 (the pooling, exact or capped, from the int8 rows and row
+ *    scales a retrieval index keeps: one resident image for retrieval and scoring, a quarter of the bytes per row, bit for bit
+ *    ocn_cn_gather / ocn_cn_gather_cap on the dequantised table). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -430,6 +432,31 @@ int ocn_cn_gather_cap(const int64_t* rowptrA, const int32_t* colA, const int64_t
                       float* xcn2, float* xij, const int64_t* out_row, const int32_t* cnt1, const int32_t* cnt2,
                       const uint64_t* rec /* or NULL */, const int32_t* perm /* or NULL */, int32_t cap, uint64_t seed,
                       int32_t* mult /* [flags_cap] or NULL */, void* stream);
+/* The pooling from an INT8 embedding table, exact or capped.  q8 holds N rows of `row_stride` bytes, the first H of each the
+ * row's int8 elements (what follows is padding and is never read); scale is fp32 [N], one per row — the image of
+ * ocn_mips_topm_i8's keys, so one resident table can serve retrieval and scoring.  Every other argument up to `perm` means
+ * what it means for ocn_cn_gather_h16, and (cap, seed, mult) what they mean for ocn_cn_gather_cap.  Arithmetic: element c of
+ * row k is v = fl32((float)q8[k][c] * scale[k]) — the conversion is exact, the product is ONE IEEE fp32 multiply, rounded to
+ * nearest even, a subnormal result kept — and from there the term is ocn_cn_gather's: one separately rounded multiply by the
+ * entry weight and one add, in ascending position, strictly sequential for every row length; xij = v_i (.) v_j.  The scale
+ * is never folded into an entry weight (that would move a rounding).  Hence, with D[k][c] = fl32((float)q8[k][c] * scale[k])
+ * as an fp32 [N][H] table:
+ *   cap == 0: xcn1, xcn2 and xij are bit for bit what ocn_cn_gather leaves for D (mult must be NULL);
+ *   cap >= 1: the sample is ocn_cn_gather_cap's, unchanged — strata, Philox counter (i, j, t, 7) and key, multipliers — and
+ *             xcn1, xcn2, xij and mult (every position written, unwalked candidates included) are bit for bit what
+ *             ocn_cn_gather_cap leaves for D.
+ * The skip and store rules (cnt1 / cnt2 / rec has-bits / out_row) are ocn_cn_gather_h16's; there is no `rowsum`.  One form
+ * for every row length; max_row_len is accepted and not used.  No atomics, no workspace, no LDS, no host synchronisation: the
+ * launch can be captured.  H in {16, 32, 64, 128, 256, 512}; row_stride >= H and a multiple of 16; q8 16-byte aligned.
+ * B < 0, cap < 0, cap == 0 with a mult, another H, a bad row_stride: OCN_EINVAL; B == 0 then returns 0; a NULL required pointer
+ * (rowptrA, colA, src, dst, off, flags, weights, q8, scale, the outputs): OCN_EINVAL — all before any HIP call. */
+int ocn_cn_gather_q8(const int64_t* rowptrA, const int32_t* colA, const int64_t* src, const int64_t* dst,
+                     const int64_t* order, int64_t B, const int64_t* off, const uint8_t* flags, const int32_t* wc,
+                     const float* weights /* [N][4] */, const int8_t* q8 /* [N] rows of row_stride bytes */,
+                     int64_t row_stride, const float* scale /* [N] */, int32_t H, int64_t max_row_len, float* xcn1,
+                     float* xcn2, float* xij, const int64_t* out_row, const int32_t* cnt1, const int32_t* cnt2,
+                     const uint64_t* rec /* or NULL */, const int32_t* perm /* or NULL */, int32_t cap /* 0 = uncapped */,
+                     uint64_t seed, int32_t* mult /* [flags_cap] or NULL */, void* stream);
 /* cn8 (CNLinkPredictorbaselearnablation, model.py:3233-3449; pattern route): intersection and pooling in ONE pass.  cn8
  * pools without column weights, so a candidate's vectors depend on nothing but the candidate:
  *   xcn1[e] = sum_{k in N(i) ∩ T1(j)} h[k]   xcn2[e] = sum_{k in N(i) ∩ T2(j)} h[k]   xij[e] = h[i] (.) h[j]

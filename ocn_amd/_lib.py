@@ -62,6 +62,8 @@ SIGNATURES = {
                                     _P, _P, _P, _P]),
     "ocn_cn_gather_cap": (c_int32, [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int64, _P, _P, _P, _P, _P, _P, _P,
                                     _P, c_int32, ctypes.c_uint64, _P, _P]),
+    "ocn_cn_gather_q8": (c_int32, [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int64, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, c_int32, ctypes.c_uint64, _P, _P]),
     "ocn_cn8_pool": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int32, _P, _P,
                                _P, _P, _P, _P]),
     "ocn_cn_pool_frozen": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, c_int32, _P,

@@ -20,17 +20,6 @@
 
 constexpr int CAP_UNR = 4;                   // embedding rows in flight per lane group (eight where a wave has one candidate)
 
-// The multiplier of the member of rank r among u > d members: its stratum's size where it is the stratum's pick, else 0.
-// T: an unsigned type that holds u * d.
-template <typename T>
-__device__ __forceinline__ int32_t cap_multiplier(T r, T u, T d, unsigned i, unsigned j, u64 seed) {
-  const T t = r * d / u;                                   // the stratum of rank r
-  const T lo = (t * u + d - 1) / d, hi = ((t + 1) * u + d - 1) / d;
-  const T s = hi - lo;                                     // floor(u / d) or ceil(u / d), never 0
-  const u64 pick = (u64)lo + sample_rank(make_uint4(i, j, (unsigned)t, SAMPLE_STREAM_CN_CAP), seed, (u64)s);
-  return (u64)r == pick ? (int32_t)s : 0;
-}
-
 // The arguments are ocn_cn_gather's (cn_gather_kernel, cn_pool.hip) without `rowsum`, then the sample's.
 template <int LPE, int NV, int UNR = (LPE >= 64 ? 2 * CAP_UNR : CAP_UNR)>
 __global__ __launch_bounds__(OCN_BLOCK) void cn_gather_cap_kernel(

@@ -30,3 +30,15 @@ __device__ __forceinline__ u64 sample_rank(uint4 ctr, u64 seed, u64 m) {
   const uint4 w = philox4x32_10(ctr, (unsigned)seed, (unsigned)(seed >> 32));
   return __umul64hi((u64)w.x | ((u64)w.y << 32), m);
 }
+
+// The capped pooling's sample (cn_pool_cap.hip, cn_pool_q8.hip; include/ocn_hip.h states it).  The multiplier of the member
+// of rank r among u > d members: its stratum's size where it is the stratum's pick, else 0.  T: an unsigned type that holds
+// u * d.
+template <typename T>
+__device__ __forceinline__ int32_t cap_multiplier(T r, T u, T d, unsigned i, unsigned j, u64 seed) {
+  const T t = r * d / u;                                   // the stratum of rank r
+  const T lo = (t * u + d - 1) / d, hi = ((t + 1) * u + d - 1) / d;
+  const T s = hi - lo;                                     // floor(u / d) or ceil(u / d), never 0
+  const u64 pick = (u64)lo + sample_rank(make_uint4(i, j, (unsigned)t, SAMPLE_STREAM_CN_CAP), seed, (u64)s);
+  return (u64)r == pick ? (int32_t)s : 0;
+}

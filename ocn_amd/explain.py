@@ -100,7 +100,7 @@ def _check_request(predictor, h, edges, m, rank, args, what: str = "explain_link
     if not 1 <= int(edges.shape[0]) <= ops.MAX_BATCH:
         raise ValueError(f"edges is ONE batch of 1 .. {ops.MAX_BATCH} candidates (the histogram field width), got {int(edges.shape[0])}")
     if h is not _NO_H:
-        ops.refuse_half_table(h, f"{what} (gradients through the pooled rows)")
+        ops.refuse_compact_table(h, f"{what} (gradients through the pooled rows)")
     if h is not _NO_H and (not isinstance(h, Tensor) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[1] not in ops.LN_WIDTHS):
         raise ValueError(f"h must be float32 [N, H] with H in {ops.LN_WIDTHS}")
     if predictor._weights_need_args and predictor._frozen is None and args is None:
@@ -271,7 +271,7 @@ def explain_link_edges(model, predictor, x: Tensor, adj, adj2, edges: Tensor, wh
     from .model import message_masks
     from .utils import adjoverlap, fuse, get_cn1_cn2
     L = _check_edge_request(model, predictor, edges, which, top, rank, args)
-    ops.refuse_half_table(x, "explain_link_edges (gradients through the encoder and the pooled rows)")
+    ops.refuse_compact_table(x, "explain_link_edges (gradients through the encoder and the pooled rows)")
     e = edges.t().contiguous()
     adj.warm(walk=adj2 is None)
     if adj2 is not None:
@@ -286,7 +286,7 @@ def explain_link_edges(model, predictor, x: Tensor, adj, adj2, edges: Tensor, wh
         with message_masks(adj, masks):
             h = model(xl, adj)
     hc = h.detach().contiguous()
-    ops.refuse_half_table(hc, "explain_link_edges (gradients through the encoder and the pooled rows)")
+    ops.refuse_compact_table(hc, "explain_link_edges (gradients through the encoder and the pooled rows)")
     if hc.dim() != 2 or hc.dtype != torch.float32 or hc.shape[1] not in ops.LN_WIDTHS:
         raise ValueError(f"the encoder's output must be float32 [N, H] with H in {ops.LN_WIDTHS}")
     with torch.no_grad():

@@ -852,19 +852,20 @@ class _CNPredictorBase(nn.Module):
         return fuse(cn1, cn2, tar_ei, ws, adj=adj)
 
     def _check_table(self, x) -> None:
-        """A bf16 / f16 embedding table (``pipeline.embedding_table``) is pooled by the eval path alone: TypeError under
+        """A bf16 / f16 or int8 embedding table (``pipeline.embedding_table``) is pooled by the eval path alone: TypeError under
         autograd, in training mode and on an edge-sharded predictor, before the batch's first launch.  The pooling widens its
         rows exactly and sums in fp32 (ocn_hip.h: ocn_cn_gather_h16), so the heads receive the bits they would receive for
         ``x.float()``.  The one-pass forms (``OCN_CN8_FUSED``, ``OCN_FROZEN_FUSED``) read fp32 rows: with a half table the chain
-        runs in their place — bit-equal by their own contracts."""
-        if not ops.is_half_table(x):
+        runs in their place — bit-equal by their own contracts.  An ``ops.Int8Table`` is dequantised with one multiply per
+        element (ocn_cn_gather_q8): the bits of ``x.float()`` again, with or without ``set_cn_cap``."""
+        if not ops.is_compact_table(x):
             return
         if self.training:
-            ops.refuse_half_table(x, "training mode")
+            ops.refuse_compact_table(x, "training mode")
         if torch.is_grad_enabled() or x.requires_grad:
-            ops.refuse_half_table(x, "autograd (the pooling's backward)")
+            ops.refuse_compact_table(x, "autograd (the pooling's backward)")
         if self._sharded:
-            ops.refuse_half_table(x, "an edge-sharded predictor")
+            ops.refuse_compact_table(x, "an edge-sharded predictor")
 
     def _score(self, x, adj, cn1, cn2, tar_ei, args=None):
         """The one-call batch path: state, exchange, weights, pooling, heads."""
@@ -1327,7 +1328,7 @@ class CNLinkPredictorbaselearn(_CNPredictorBase):
         summing ~500 embedding rows again for each of the source's candidates (ocn_hip.h, ocn_cn_gather `rowsum`).  Only
         where it can pay: pattern route, A² at least half full."""
         adj, t2 = st.adj, st.t2
-        if ops.is_half_table(x):
+        if ops.is_compact_table(x):
             return None                        # (the shortcut wants an fp32 A·h; summed entry by entry the bits are the same)
         if not ops.share_full_rows or st.walk or t2 is None or not x.is_cuda or x.dim() != 2 or int(self.polysecond) != 0:
             return None                        # (a non-trivial basis weights the cn2 entries: the row sum is not their pool)
@@ -1417,7 +1418,7 @@ class CNLinkPredictor3hopCNs(_CNPredictorBase):
 
     def multidomainforward(self, x, adj, cn1, cn2, cn3, tar_ei, args=None, cndropprobs: Iterable[float] = []):
         from .utils import fuse3
-        ops.refuse_half_table(x, "cn6 (cn_gather3)")
+        ops.refuse_compact_table(x, "cn6 (cn_gather3)")
         if self.training:
             raise NotImplementedError("cn6 in training mode updates the one `innerprod` buffer three times per call with three "
                                       "different quantities (model.py:2527-2533, 2636, 2817, 2842) and is reached by no driver: "

@@ -126,6 +126,81 @@ def refuse_half_table(t, what: str) -> None:
                         "eval-mode, no-grad pooling of cn5 / cn7 / cn8 only — pass table.float()")
 
 
+class Int8Table:
+    """An int8 embedding table (``pipeline.embedding_table(h, "int8")``): ``rows`` int8 [N, Hp], ``scale`` float32 [N] and
+    ``width`` = H <= Hp — what ``quantize_rows_i8(h)`` returns, the image a ``recommend.EmbeddingIndex`` keeps, so one resident
+    copy serves retrieval and scoring (``from_index`` / ``EmbeddingIndex.from_table`` share storage).  The table it stands for
+    is ``float()`` = ``rows[:, :H].float() * scale[:, None]``, one fp32 multiply per element; the eval pooling of cn5 / cn7 / cn8
+    (``cn_gather``, ``cn_gather_cap``: ocn_cn_gather_q8) gives bit for bit what the fp32 entries give for that matrix.  A plain
+    object with as much of a tensor's surface as a scoring loop reads: ``torch.save`` stores it, ``to(device)`` moves it."""
+    requires_grad = False
+
+    def __init__(self, rows: Tensor, scale: Tensor, width: int):
+        if not isinstance(rows, Tensor) or rows.dtype != torch.int8 or rows.dim() != 2 or not rows.is_contiguous():
+            raise ValueError("rows must be a contiguous int8 [N, Hp] matrix")
+        if not isinstance(scale, Tensor) or scale.dtype != torch.float32 or scale.dim() != 1 or not scale.is_contiguous() \
+                or scale.numel() != rows.shape[0]:
+            raise ValueError(f"scale must be a contiguous float32 [{rows.shape[0]}] vector: one scale per row")
+        if scale.device != rows.device:
+            raise ValueError(f"rows live on {rows.device}, scale on {scale.device}")
+        if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= rows.shape[1]:
+            raise ValueError(f"width must be an int in 1..{rows.shape[1]} (the columns of rows), got {width!r}")
+        self.rows, self.scale, self.width = rows, scale, width
+
+    @classmethod
+    def from_index(cls, index) -> "Int8Table":
+        """The table an ``EmbeddingIndex`` holds, on the same storage.  A ``normalize=True`` index holds the image of the
+        normalised rows, which is not the table: ValueError."""
+        if index.normalize:
+            raise ValueError("an index made with normalize=True holds the unit-norm rows, not the embedding table")
+        return cls(index.keys_q, index.kscale, index.width)
+
+    shape = property(lambda self: torch.Size((self.rows.shape[0], self.width)))
+    device = property(lambda self: self.rows.device)
+    dtype = property(lambda self: torch.int8)
+    is_cuda = property(lambda self: self.rows.is_cuda)
+
+    def dim(self) -> int:
+        return 2
+
+    def contiguous(self) -> "Int8Table":
+        return self
+
+    def detach(self) -> "Int8Table":
+        return self
+
+    def new_zeros(self, *size, dtype=torch.float32) -> Tensor:
+        return self.scale.new_zeros(*size, dtype=dtype)
+
+    def float(self) -> Tensor:
+        """The fp32 [N, H] matrix this table stands for."""
+        return self.rows[:, :self.width].float() * self.scale[:, None]
+
+    def float_rows(self, ids: Tensor) -> Tensor:
+        """``float()[ids]`` without forming the whole matrix."""
+        return self.rows[ids, :self.width].float() * self.scale[ids][:, None]
+
+    def to(self, device) -> "Int8Table":
+        return Int8Table(self.rows.to(device), self.scale.to(device), self.width)
+
+
+if hasattr(torch.serialization, "add_safe_globals"):        # (torch.load's weights_only unpickler names the classes it builds)
+    torch.serialization.add_safe_globals([Int8Table])
+
+
+def is_compact_table(t) -> bool:
+    """A table the eval pooling of cn5 / cn7 / cn8 alone reads: bf16 / f16 rows, or an ``Int8Table``."""
+    return is_half_table(t) or isinstance(t, Int8Table)
+
+
+def refuse_compact_table(t, what: str) -> None:
+    """``refuse_half_table``, and the same refusal of an ``Int8Table``.  Reads the type alone."""
+    refuse_half_table(t, what)
+    if isinstance(t, Int8Table):
+        raise TypeError(f"{what} needs an fp32 (torch.float32) embedding table, got an int8 table (Int8Table): an int8 table "
+                        "serves the eval-mode, no-grad pooling of cn5 / cn7 / cn8 only — pass table.float()")
+
+
 ST_CAP, ST_SCAN = 1, 2           # include/ocn_hip.h: OCN_ST_CAP, OCN_ST_SCAN (bits of status[0] and of the sticky status[3])
 REC_WORDS = 4                    # include/ocn_hip.h: OCN_REC_WORDS (int64 words of a slot record)
 SCHED_GROUP, SCHED_EIGHTHS, SCHED_MAX_EIGHTH = 4, 8, 65535     # include/ocn_hip.h: OCN_SCHED_* (the pooling's schedule)
@@ -633,7 +708,10 @@ def cn_gather(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], weights
     """The pooling (ocn_hip.h: ocn_cn_gather).  ``h``: the fp32 embedding table — or a bf16 / f16 one (``pipeline.embedding_table``),
     which goes to ocn_cn_gather_h16: the same fp32 output buffer, the same schedule and slot records, no ``rowsum`` (it is
     dropped: the shortcut adds the same numbers in the same order), widths ``LN_WIDTHS`` only.  The three outputs are bit for
-    bit those of the fp32 entry on ``h.float()``."""
+    bit those of the fp32 entry on ``h.float()``.  An ``Int8Table`` goes to ocn_cn_gather_q8 on the same terms."""
+    if isinstance(h, Int8Table):
+        return _cn_gather_q8(rowptrA, colA, src, dst, off, flags, wc, weights, h, 0, 0, order, max_row_len, wsd, out_row, cnt1,
+                             cnt2, rec, sched, sched_ready, None)
     _req(weights, torch.float32, "weights", 2)
     half = is_half_table(h)
     _req(h, h.dtype if half else torch.float32, "h", 2)
@@ -681,8 +759,15 @@ def cn_gather_cap(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], wei
     that the pooled vectors are unbiased estimates of the exact ones.  A candidate with at most ``cap`` entries gets the bits
     of ``cn_gather``.  The same output buffer, schedule and slot records as ``cn_gather``; no ``rowsum``; fp32 tables of the
     widths ``LN_WIDTHS`` only.  ``mult`` (optional, int32, one word per flag position): receives every position's multiplier
-    — the stratum size of a selected entry, 1 where the candidate is within the cap, 0 for every other position."""
+    — the stratum size of a selected entry, 1 where the candidate is within the cap, 0 for every other position.  An
+    ``Int8Table`` in place of ``h`` goes to ocn_cn_gather_q8: the same sample, bit for bit this call on ``h.float()``."""
     refuse_half_table(h, "the capped pooling (cn_gather_cap)")
+    if isinstance(h, Int8Table):
+        cap = int(cap)
+        if not 1 <= cap < (1 << 31):
+            raise ValueError("cap: at least one row per candidate (an int32)")
+        return _cn_gather_q8(rowptrA, colA, src, dst, off, flags, wc, weights, h, cap, _seed(seed), order, max_row_len, wsd,
+                             out_row, cnt1, cnt2, rec, sched, sched_ready, mult)
     _req(weights, torch.float32, "weights", 2)
     _req(h, torch.float32, "h", 2)
     if weights.shape[0] != h.shape[0] or weights.shape[1] != 4:
@@ -708,6 +793,38 @@ def cn_gather_cap(rowptrA, colA, src, dst, off, flags, wc: Optional[Tensor], wei
                                        ptr(wc), ptr(weights), ptr(h), H, int(max_row_len), ptr(out[0]), ptr(out[1]),
                                        ptr(out[2]), ptr(out_row), ptr(cnt1), ptr(cnt2), ptr(rec), ptr(perm), cap, seed, ptr(mult),
                                        stream_ptr()), "ocn_cn_gather_cap")
+    _mark("cn_gather")
+    return out[0], out[1], out[2]
+
+
+def _cn_gather_q8(rowptrA, colA, src, dst, off, flags, wc, weights, table: Int8Table, cap: int, seed: int, order, max_row_len, wsd,
+                  out_row, cnt1, cnt2, rec, sched, sched_ready, mult):
+    """``cn_gather`` (``cap`` = 0) and ``cn_gather_cap`` (``cap`` >= 1) of an ``Int8Table``: ocn_cn_gather_q8."""
+    _req(weights, torch.float32, "weights", 2)
+    q, scale = _req(table.rows, torch.int8, "table.rows", 2), _req(table.scale, torch.float32, "table.scale", 1)
+    N, H = table.shape
+    if weights.shape[0] != N or weights.shape[1] != 4:
+        raise ValueError("weights must be [N,4] with N = h.shape[0]")
+    if H not in LN_WIDTHS:
+        raise NotImplementedError(f"the pooling of an int8 table supports hidden widths {LN_WIDTHS}, got {H}")
+    stride = q.shape[1]
+    if stride % 16 or q.data_ptr() % 16:
+        raise ValueError("an int8 table's rows must be 16-byte aligned and a multiple of 16 bytes long (quantize_rows_i8 pads)")
+    B = src.numel()
+    if mult is not None and (_req(mult, torch.int32, "mult", 1).numel() < flags.numel()):
+        raise ValueError("mult: one int32 word per flag position")
+    out = buf(wsd, "pooled", (3, B, H), torch.float32, q.device)
+    perm = None
+    n_groups = sched_groups(B, H) if (sched is not None and rec is not None) else 0
+    if n_groups:
+        perm = sched[n_groups:]
+        if not sched_ready:
+            check(_lib.lib().ocn_gather_schedule(ptr(sched), n_groups, int(sched_segment), ptr(perm), stream_ptr()), "ocn_gather_schedule")
+    _mark("cn_pre")
+    check(_lib.lib().ocn_cn_gather_q8(ptr(rowptrA), ptr(colA), ptr(src), ptr(dst), ptr(order), B, ptr(off), ptr(flags), ptr(wc),
+                                      ptr(weights), ptr(q), stride, ptr(scale), H, int(max_row_len), ptr(out[0]), ptr(out[1]),
+                                      ptr(out[2]), ptr(out_row), ptr(cnt1), ptr(cnt2), ptr(rec), ptr(perm), cap, seed, ptr(mult),
+                                      stream_ptr()), "ocn_cn_gather_q8")
     _mark("cn_gather")
     return out[0], out[1], out[2]
 
@@ -1545,7 +1662,7 @@ def cn_weights_cn6(histA: Tensor, histB: Tensor, innerprod: Tensor, exact=None, 
 def cn_gather3(rowptrA, colA, src, dst, off, flagsA, flagsB, wA: Tensor, wB: Tensor, nip: Tensor, h: Tensor,
                order: Optional[Tensor] = None):
     """(xcn1, xcn2, xcn3, x_i * x_j) of the 3-hop predictor.  fp32 rows only: a bf16 / f16 table raises TypeError."""
-    refuse_half_table(h, "cn6 (cn_gather3)")
+    refuse_compact_table(h, "cn6 (cn_gather3)")
     _req(wA, torch.float32, "weightsA", 2); _req(wB, torch.float32, "weightsB", 2)
     _req(h, torch.float32, "h", 2)
     if wA.shape != (h.shape[0], 4) or wB.shape != (h.shape[0], 4):

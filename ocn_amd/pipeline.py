@@ -20,8 +20,8 @@ import torch
 from torch import Tensor
 
 from . import ops
+from .ops import Int8Table                   # (re-exported: the table type of embedding_table_int8)
 from .utils import PermIterator, scratch_set_count
-
 
 TABLE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 
@@ -45,6 +45,19 @@ def embedding_table(h: Tensor, dtype: str) -> Tensor:
         raise ValueError(f"h holds finite values that round to infinity in {dtype}" +
                          (" (|x| above 65504): use \"bf16\", or scale h" if dtype == "f16" else ""))
     return t
+
+
+def embedding_table_int8(h: Tensor) -> Int8Table:
+    """The node embeddings ``h`` [N, H] as an int8 table: an ``ops.Int8Table`` of ``ops.quantize_rows_i8(h)`` — int8 rows and one
+    fp32 scale per row, a quarter of fp32's bytes per row and the image an ``EmbeddingIndex`` keeps (``EmbeddingIndex.from_table``
+    shares it: one resident copy for retrieval and scoring).  The consumers of a half table (``embedding_table``) take it in
+    place of ``h``, and ``set_cn_cap`` as well; the scores are bit for bit those of ``table.float()`` and differ from those of
+    ``h`` by the quantisation: ``|h - table.float()| <= scale * (0.5 + 2**-14)`` per element, ``scale`` = the row's largest
+    magnitude / 127 (1 for an all-zero row).  ValueError where ``h`` holds a value that is not finite.  (A function of its
+    own: ``embedding_table`` returns tensors and keeps refusing every name that is not a torch dtype of ``TABLE_DTYPES``.)"""
+    if not isinstance(h, Tensor) or h.dim() != 2 or h.dtype != torch.float32:
+        raise ValueError("h must be a float32 [N, H] matrix of node embeddings")
+    return Int8Table(*ops.quantize_rows_i8(h.detach(), False), int(h.shape[1]))
 
 
 def _graphed(predictor, h, adj, make_handles, batch_size, args, n_batches):
@@ -161,7 +174,7 @@ def _score_3hop(predictor, h: Tensor, adj, adj2, edges: Tensor, batch_size: int,
     ``adj`` and the bit rows of ``adj2``, no A³ — so the scores are exactly those of per-batch ``forward`` calls at this batch
     size.  No side streams, no graph replay; the batches' status words are ORed on the device and read once at the end."""
     from .utils import adjoverlap, adjoverlap_3hop
-    ops.refuse_half_table(h, "cn6 (cn_gather3)")
+    ops.refuse_compact_table(h, "cn6 (cn_gather3)")
     if group is not None:
         raise ValueError("cn6 is scored on one GPU: score_edges deals batches over a group for the two-handle predictors only")
     if adj2 is None:

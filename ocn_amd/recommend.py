@@ -434,6 +434,19 @@ class EmbeddingIndex:
         self.n, self.width, self.normalize = int(keys.shape[0]), int(keys.shape[1]), normalize
         self.keys_q, self.kscale = ops.quantize_rows_i8(keys.detach(), normalize)
 
+    @classmethod
+    def from_table(cls, table) -> "EmbeddingIndex":
+        """The index an ``ops.Int8Table`` already is (``pipeline.embedding_table(h, "int8")``), on the same storage: what
+        ``EmbeddingIndex(h)`` makes, without a second image of the embeddings.  ``normalize`` is False."""
+        if not isinstance(table, ops.Int8Table):
+            raise ValueError(f"table must be an ops.Int8Table, got {type(table).__name__}")
+        if table.shape[0] < 1 or table.width > ops.MIPS_H_MAX:
+            raise ValueError(f"the table must have at least one row and 1..{ops.MIPS_H_MAX} columns, got {tuple(table.shape)}")
+        other = object.__new__(EmbeddingIndex)
+        other.n, other.width, other.normalize = int(table.shape[0]), int(table.width), False
+        other.keys_q, other.kscale = table.rows, table.scale
+        return other
+
     def to(self, device) -> "EmbeddingIndex":
         other = object.__new__(EmbeddingIndex)
         other.n, other.width, other.normalize = self.n, self.width, self.normalize
@@ -587,6 +600,15 @@ def _prefilter_m(prefilter) -> Optional[int]:
     return None if prefilter is None or isinstance(prefilter, ShortListUnion) else _stage_m(prefilter)
 
 
+def _refuse_cosine_of_int8(h, stage: EmbeddingNeighbours) -> None:
+    """An ``ops.Int8Table`` serves a ``normalize=False`` stage as its own index; a cosine index is quantised from the unit-norm
+    fp32 rows, which the table does not hold (TypeError; reads the types alone)."""
+    if isinstance(h, ops.Int8Table) and stage.normalize:
+        raise TypeError("an EmbeddingNeighbours stage with normalize=True and without keys= needs an fp32 (torch.float32) "
+                        "embedding table, got an int8 table (Int8Table): its cosine index is quantised from the unit-norm fp32 "
+                        "rows — pass keys=EmbeddingIndex(h_fp32, normalize=True)")
+
+
 def _emb_pass(stage: EmbeddingNeighbours, h: Optional[Tensor], adj: SparseTensor, sources: Tensor, known: Optional[SparseTensor],
               targets: Optional[Tuple[Tensor, Tensor]] = None):
     """``_path_index_pass`` for an embedding stage: (``short``, ``rank``, ``count``) — the ``m`` nearest per source, the place of
@@ -596,16 +618,22 @@ def _emb_pass(stage: EmbeddingNeighbours, h: Optional[Tensor], adj: SparseTensor
     known = adj if known is None else known
     sources = _check_sources(adj, sources, known)
     n = adj.size(0)
-    if not isinstance(h, Tensor) or h.dim() != 2 or h.shape[0] != n:
+    q8 = isinstance(h, ops.Int8Table)
+    if not (q8 or isinstance(h, Tensor)) or h.dim() != 2 or h.shape[0] != n:
         raise ValueError(f"h must be the [{n}, H] node embeddings of adj")
     if stage.keys is None:
         ops.refuse_half_table(h, "an EmbeddingNeighbours stage without keys= (the int8 index is quantised from fp32 rows)")
-    index = stage.keys if isinstance(stage.keys, EmbeddingIndex) else \
-        EmbeddingIndex((h if stage.keys is None else stage.keys).float(), stage.normalize)
+        _refuse_cosine_of_int8(h, stage)
+    if isinstance(stage.keys, EmbeddingIndex):
+        index = stage.keys
+    elif q8 and stage.keys is None:
+        index = EmbeddingIndex.from_table(h)                 # (an int8 table IS the index of its rows: no second image)
+    else:
+        index = EmbeddingIndex((h if stage.keys is None else stage.keys).float(), stage.normalize)
     if index.n != n:
         raise ValueError(f"the stage's keys hold {index.n} nodes, adj {n}")
     ops.check_edges(sources, sources, n, n)                  # (before h is indexed)
-    queries = h.detach()[sources].float()
+    queries = h.float_rows(sources) if q8 else h.detach()[sources].float()
     ptr, edges, _ = embedding_candidates(index, queries, sources, stage.m, known)
     rank = embedding_retrieval_rank(index, queries, sources, known, *targets) if targets is not None else None
     return (ptr, edges), rank, ptr[1:] - ptr[:-1]
@@ -716,16 +744,20 @@ def _check_request(predictor, adj2: Optional[SparseTensor], k: int, prefilter, h
 def _check_table(predictor, h, prefilter) -> None:
     """The refusals of a bf16 / f16 embedding table (``pipeline.embedding_table``) in a model request, before anything touches
     the device (TypeError): cn6, and an ``EmbeddingNeighbours`` stage that would quantise its int8 index from ``h`` itself — pass
-    ``keys=EmbeddingIndex(h_fp32)``; the queries ``h[sources]`` are widened exactly.  Everything else passes the table on to the
+    ``keys=EmbeddingIndex(h_fp32)``; the queries ``h[sources]`` are widened exactly.  An ``ops.Int8Table`` is refused by cn6
+    alike; a ``normalize=False`` stage without ``keys=`` takes the table itself as its index (``EmbeddingIndex.from_table``,
+    queries ``table.float_rows(sources)``), a ``normalize=True`` one is refused.  Everything else passes the table on to the
     scoring loop."""
     from .model import CNLinkPredictor3hopCNs
-    if not ops.is_half_table(h):
+    if not ops.is_compact_table(h):
         return
     if isinstance(predictor, CNLinkPredictor3hopCNs):
-        ops.refuse_half_table(h, "cn6 (cn_gather3)")
+        ops.refuse_compact_table(h, "cn6 (cn_gather3)")
     stages = prefilter.stages if isinstance(prefilter, ShortListUnion) else (prefilter,)
-    if any(isinstance(st, EmbeddingNeighbours) and st.keys is None for st in stages):
-        ops.refuse_half_table(h, "an EmbeddingNeighbours stage without keys= (the int8 index is quantised from fp32 rows)")
+    for st in stages:
+        if isinstance(st, EmbeddingNeighbours) and st.keys is None:
+            ops.refuse_half_table(h, "an EmbeddingNeighbours stage without keys= (the int8 index is quantised from fp32 rows)")
+            _refuse_cosine_of_int8(h, st)
 
 
 def _score_request(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor, batch_size: int,
