@@ -5,22 +5,14 @@ import torch
 
 from ocn_amd import ops
 from ocn_amd.sparse import SparseTensor
+from tests.graph_build_mirror import csr_of_coo
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _ref_csr(row, col, n_rows, n_cols, symmetrize, dedupe):
-    """torch restatement on the CPU: sort by (row, col), optionally with the transposed entries and without duplicates."""
-    row, col = row.cpu(), col.cpu()
-    if symmetrize:
-        row, col = torch.cat([row, col]), torch.cat([col, row])
-    key = row * n_cols + col
-    key = torch.unique(key) if dedupe else torch.sort(key).values
-    r, c = torch.div(key, n_cols, rounding_mode="floor"), key % n_cols
-    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64)
-    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=n_rows), 0)
-    return rowptr, c.to(torch.int32)
+# torch restatement on the CPU: sort by (row, col), optionally with the transposed entries and without duplicates
+_ref_csr = csr_of_coo
 
 
 def _coo_case(name):
