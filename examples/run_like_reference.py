@@ -19,6 +19,7 @@ argument parser is the reference's call sequence with the three import lines swa
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32   # ... ranking a short list only
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-hops 3 --recommend-frozen --recommend-prefilter ra:32:0.5   # ... over 3 hops
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-prefilter ra:32 --recommend-eval 200   # ... and where the test links rank
+    python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-frozen --recommend-long ra:300 --recommend-eval 200   # ... a short list beyond 128
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-rw 32:256:2 --recommend-eval 200   # ... a short list from random walks instead
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-emb 32 --recommend-eval 200        # ... the nearest embeddings over ALL nodes instead
     python examples/run_like_reference.py --dataset cora --recommend 5 --recommend-prefilter ra:32 --recommend-emb 32:cos --recommend-union --recommend-eval 200   # ... or the union of the two
@@ -49,7 +50,7 @@ from ocn_amd.model import GCN, predictor_dict                                   
 from ocn_amd.pipeline import embedding_table, embedding_table_int8, score_mrr_split  # noqa: E402
 from ocn_amd.ranking import rank_links, rank_links_heuristic, ranking_metrics       # noqa: E402
 from ocn_amd.recommend import (EmbeddingNeighbours, RandomWalks, ShortListUnion, random_walk_short_list, prefilter_candidates, recommend_links, recommend_links_heuristic,  # noqa: E402
-                               three_hop_candidates, two_hop_candidates)
+                               three_hop_candidates, two_hop_candidates, PathSums, prefilter_candidates_long)
 from ocn_amd.update import EncoderState, insert_edges, remove_edges                 # noqa: E402
 from ocn_amd.sampling import (negative_edges, negative_targets, two_hop_negative_edges,  # noqa: E402
                               two_hop_negative_targets)
@@ -198,6 +199,8 @@ def prefilter_name(pf):
         return f"embedding {pf.m}" + (":cos" if pf.normalize else "")
     if isinstance(pf, ShortListUnion):
         return "union of " + " + ".join(prefilter_name(st) for st in pf.stages)
+    if isinstance(pf, PathSums):
+        return f"long {pf.kind}:{pf.m}" + (f":{pf.decay:g}" if pf.decay is not None else "")
     return ":".join(f"{p:g}" if isinstance(p, float) else str(p) for p in pf)
 
 
@@ -212,6 +215,8 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
     with --recommend-frozen the number of unfiltered top-K links that the short list kept is printed.
     --recommend-hops 3: the candidates within three hops (every target with a non-empty cn1 or cn2), expanded from the adjacency;
     the prefilter is then KIND:M:DECAY and ranks them by the local path index P2 + DECAY * P3.
+    --recommend-long KIND:M[:DECAY]: the same short list for ANY M >= K (ocn_amd.recommend.PathSums: the M best taken as a set by
+    ocn_segment_keep_best, no limit of 128); --recommend-prefilter keeps its limit and its route.
     --recommend-rw M:W:L[:DECAY]: the short list comes from W random walks of L steps per source instead (the M most visited nodes,
     ranked by c2 + DECAY * c3; ocn_amd.recommend.RandomWalks): a sample of the candidates at a cost that no hub source raises.
     --recommend-emb M[:cos]: the short list is the M nodes nearest to the source's embedding by int8 inner product (cosine with
@@ -288,6 +293,10 @@ def recommend(k, data, split_edge, args, model=None, predictor=None, n_sources=5
                 n_all = int((three_hop_candidates(adj, sources) if args.recommend_hops == 3 else two_hop_candidates(adj, adj2, sources))[0][-1])
                 n_short = int(random_walk_short_list(adj, sources, args.recommend_prefilter)[0][-1])
                 name = rw_name(args.recommend_prefilter)
+            elif isinstance(args.recommend_prefilter, PathSums):
+                n_all = int((three_hop_candidates(adj, sources) if args.recommend_hops == 3 else two_hop_candidates(adj, adj2, sources))[0][-1])
+                n_short = int(prefilter_candidates_long(adj, sources, args.recommend_prefilter, hops=args.recommend_hops)[0][-1])
+                name = prefilter_name(args.recommend_prefilter) + (" over 3 hops" if args.recommend_hops == 3 else "")
             elif args.recommend_hops == 3:
                 kind, m, decay = args.recommend_prefilter
                 n_all = int(three_hop_candidates(adj, sources)[0][-1])
@@ -444,6 +453,9 @@ def main(argv=None):
     ap.add_argument("--recommend-prefilter", default=None, metavar="KIND:M[:DECAY]",
                     help="with --recommend and a model: short-list the M best candidates per source by the heuristic KIND (cn, aa or "
                          "ra; K <= M <= 128) and let the model rank only those (recommend_links(prefilter=...))")
+    ap.add_argument("--recommend-long", default=None, metavar="KIND:M[:DECAY]",
+                    help="with --recommend and a model, instead of --recommend-prefilter: the same short list for any M >= K "
+                         "(ocn_amd.recommend.PathSums: the M best as a set through ocn_segment_keep_best; no limit of 128)")
     ap.add_argument("--recommend-rw", default=None, metavar="M:W:L[:DECAY]",
                     help="with --recommend and a model, instead of --recommend-prefilter: short-list the M most visited nodes of W "
                          "random walks of L = --recommend-hops steps per source (ocn_amd.recommend.RandomWalks; DECAY with L = 3) and "
@@ -529,9 +541,24 @@ def main(argv=None):
             if not (math.isfinite(d) and d >= 0):
                 ap.error("--recommend-prefilter KIND:M:DECAY: DECAY is a finite number >= 0")
             args.recommend_prefilter += (d,)
+    if args.recommend_long:
+        if args.recommend_prefilter:
+            ap.error("--recommend-long and --recommend-prefilter are two short lists: give one")
+        if args.heuristic or not args.recommend:
+            ap.error("--recommend-long KIND:M[:DECAY]: needs a model and --recommend K")
+        parts = args.recommend_long.split(":")
+        try:
+            if len(parts) != args.recommend_hops:
+                raise ValueError("KIND:M with --recommend-hops 2, KIND:M:DECAY with --recommend-hops 3")
+            stage = PathSums(parts[0], int(parts[1]), float(parts[2]) if len(parts) == 3 else None)
+            if args.recommend > stage.m:
+                raise ValueError(f"M = {stage.m} is fewer than K = {args.recommend}")
+        except ValueError as e:
+            ap.error(f"--recommend-long KIND:M[:DECAY]: {e}")
+        args.recommend_prefilter = stage         # (one short list per request: the calls below pass it as prefilter=)
     if args.recommend_rw:
         if args.recommend_prefilter:
-            ap.error("--recommend-rw and --recommend-prefilter are two short lists: give one")
+            ap.error("--recommend-rw and --recommend-prefilter / --recommend-long are two short lists: give one")
         if args.heuristic or not args.recommend:
             ap.error("--recommend-rw M:W:L[:DECAY]: needs a model and --recommend K")
         parts = args.recommend_rw.split(":")
@@ -559,7 +586,7 @@ def main(argv=None):
                 raise ValueError("M, or M:cos")
             emb = EmbeddingNeighbours(int(parts[0]), normalize=len(parts) == 2)
             if args.recommend > max(emb.m, 0 if not args.recommend_union else
-                                    (args.recommend_prefilter.m if isinstance(args.recommend_prefilter, RandomWalks) else args.recommend_prefilter[1])):
+                                    (args.recommend_prefilter.m if isinstance(args.recommend_prefilter, (RandomWalks, PathSums)) else args.recommend_prefilter[1])):
                 raise ValueError(f"M = {emb.m} is fewer than K = {args.recommend}")
         except ValueError as e:
             ap.error(f"--recommend-emb M[:cos]: {e}")

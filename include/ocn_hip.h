@@ -68,7 +68,8 @@ extern "C" {
  *    pooling with at most `cap` sampled, reweighted rows per candidate: an unbiased estimate at a bounded cost; candidates
  *    within the cap bit for bit ocn_cn_gather's); ocn_cn_gather_q8 (the pooling, exact or capped, from the int8 rows and row
  *    scales a retrieval index keeps: one resident image for retrieval and scoring, a quarter of the bytes per row, bit for bit
- *    ocn_cn_gather / ocn_cn_gather_cap on the dequantised table). */
+ *    ocn_cn_gather / ocn_cn_gather_cap on the dequantised table); ocn_segment_keep_best (the m best entries of every segment
+ *    as a set, in position order, for any m: short lists beyond ocn_segment_topk_max_k()). */
 #define OCN_ABI_VERSION 9
 #define OCN_EINVAL (-1)   /* null pointer / negative size / unsupported combination */
 #define OCN_ECAP   (-2)   /* reported through the device status word: flags capacity too small */
@@ -685,6 +686,23 @@ int ocn_segment_topk(const float* scores, const int64_t* ptr, int64_t Q, int32_t
 int ocn_segment_rank(const float* scores, const int64_t* ptr, const int64_t* edges /* [ptr[Q]][2] */, int64_t Q,
                      const int64_t* tptr /* [Q + 1] */, const int64_t* tnode /* [P] */, int64_t P,
                      int64_t* rank /* [P] */, int64_t* pos /* [P] */, void* stream);
+/* The m best entries of every segment in that order, as a SET: what a short list needs, for any 1 <= m <= 2^31 - 1 (no
+ * limit of ocn_segment_topk applies).  ptr_m [Q + 1] is formed by the caller as the scan of min(ptr[q + 1] - ptr[q], m); the
+ * positions in the FLAT vector of the min(len, m) entries of segment q that come first in the total order of
+ * ocn_segment_topk are written to keep_pos[ptr_m[q] .. ptr_m[q + 1]), ASCENDING — within a segment of a candidate list that
+ * is ascending node id.  Keys are distinct, so exactly min(len, m) entries are kept and they are ocn_segment_topk's where
+ * m is within its limit.  cut (may be NULL) [Q]: the key of the worst kept entry of segment q — high word the score's
+ * monotone image (-0.0 folded onto +0.0, NaN = 0), low word ~(position in the segment) — 0 for an empty segment.
+ * A workgroup owns a segment.  len <= m: copied through.  Else the m-th best image is found by an MSB-first radix select,
+ * four passes of 8 bits over a 256-bin histogram in LDS (integer LDS atomics: the counts do not depend on their order), and
+ * one ordered compaction pass keeps what lies above the cut image U and the first r entries that equal it.  No float
+ * atomics, no global atomics, no workspace; the result is fixed by the segment alone.  The segment is read five times (the
+ * later passes from L2 at the sizes a 2-hop or 3-hop list has), and the longest segment sets the launch's tail, as it does
+ * for ocn_segment_topk and ocn_segment_rank.  Whatever scores holds, nothing is written outside [ptr_m[q], ptr_m[q + 1]).
+ * A segment must have fewer than 2^32 - 1 entries.
+ * NULL pointers (cut excepted), Q < 0, m < 1 or m > 2^31 - 1: OCN_EINVAL before any HIP call.  Q == 0 returns 0. */
+int ocn_segment_keep_best(const float* scores, const int64_t* ptr, int64_t Q, int64_t m, const int64_t* ptr_m /* [Q + 1] */,
+                          int64_t* keep_pos /* [ptr_m[Q]] */, uint64_t* cut /* [Q] or NULL */, void* stream);
 
 /* Structured negative sampling (ocn_amd/sampling.py): pairs that are guaranteed not to be links of a square `known` matrix
  * (sorted, duplicate-free int32 columns, n_cols rows and columns, 1 <= n_cols < 2^31), drawn exactly uniformly, with

@@ -86,6 +86,7 @@ SIGNATURES = {
     "ocn_segment_topk_max_k": (c_int32, []),
     "ocn_segment_topk": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     "ocn_segment_rank": (c_int32, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P]),
+    "ocn_segment_keep_best": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, _P]),
     "ocn_philox4x32": (c_int32, [_P, ctypes.c_uint32, ctypes.c_uint32, c_int64, _P, _P]),
     "ocn_complement_count": (c_int32, [_P, _P, c_int64, _P, _P]),
     "ocn_sample_stage_cols": (c_int32, []),

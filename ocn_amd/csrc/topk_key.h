@@ -8,12 +8,16 @@ constexpr int TOPK_MAX = 2 * OCN_WAVE;                       // the longest sort
 // -0.0 is folded onto +0.0 first, every NaN goes to 0, below -inf (0x007fffff) — the low word is ~(position in the segment),
 // so that among equal scores (and among NaNs) the lower position wins.  A segment has fewer than 2^32 - 1 entries: no entry
 // has the key 0, which marks an empty slot.
-__device__ __forceinline__ u64 topk_key(float x, unsigned rel) {
+__device__ __forceinline__ unsigned topk_image(float x) {    // the high word alone (segment_keep.hip selects on it)
   unsigned b = __float_as_uint(x);
   if (b == 0x80000000u) b = 0u;
   unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
   if (x != x) u = 0u;
-  return ((u64)u << 32) | (u64)(0xffffffffu - rel);
+  return u;
+}
+
+__device__ __forceinline__ u64 topk_key(float x, unsigned rel) {
+  return ((u64)topk_image(x) << 32) | (u64)(0xffffffffu - rel);
 }
 
 __device__ __forceinline__ u64 topk_shfl_up1(u64 v) {

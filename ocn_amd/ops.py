@@ -1295,6 +1295,38 @@ def segment_rank(scores: Tensor, seg_ptr: Tensor, edges: Tensor, tptr: Tensor, t
     return rank, pos
 
 
+SEGMENT_KEEP_MAX_M = (1 << 31) - 1
+
+
+@_on_device
+def segment_keep_best(scores: Tensor, seg_ptr: Tensor, m: int, return_cut: bool = False):
+    """The ``m`` best entries of every segment in the order of ``segment_topk``, as a set (ocn_hip.h: ocn_segment_keep_best):
+    (``ptr_m`` int64 [Q + 1], ``keep_pos`` int64 [ptr_m[-1]][, ``cut`` int64 [Q]]).  ``keep_pos[ptr_m[q] : ptr_m[q + 1]]`` are the
+    positions in the flat vector of the ``min(len_q, m)`` entries of segment ``q`` that ``segment_topk`` would list first,
+    ASCENDING — no ranked order, no [Q, m] rectangle, and no limit of ``segment_topk_max_k()``: ``1 <= m <= 2^31 - 1``.
+    ``return_cut``: the key of the worst kept entry of every segment (the bits of the kernel's uint64 — high word the score's
+    monotone image, low word ~(position in the segment) — in an int64 tensor), 0 for an empty segment.  ``seg_ptr`` is trusted
+    as ``segment_topk`` trusts it.  One host sync: the size of the kept list."""
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= SEGMENT_KEEP_MAX_M:
+        raise ValueError(f"m must be an int in 1..{SEGMENT_KEEP_MAX_M}, got {m!r}")
+    _req(scores, torch.float32, "scores", 1); _req(seg_ptr, torch.int64, "ptr", 1)
+    if seg_ptr.numel() < 1:
+        raise ValueError("ptr: [Q + 1] offsets")
+    if scores.numel() >= (1 << 32) - 1:
+        raise ValueError("scores: segments of 2^32 - 1 entries or more are not supported")
+    Q = seg_ptr.numel() - 1
+    ptr_m = torch.zeros_like(seg_ptr)
+    torch.cumsum((seg_ptr[1:] - seg_ptr[:-1]).clamp(max=m), 0, out=ptr_m[1:])
+    total = int(ptr_m[-1].item()) if Q else 0
+    keep = torch.empty(total, dtype=torch.int64, device=scores.device)
+    cut = torch.zeros(Q, dtype=torch.int64, device=scores.device) if return_cut else None
+    if Q and total:                                                      # (nothing kept: every segment is empty, every cut 0)
+        check(_lib.lib().ocn_segment_keep_best(ptr(scores), ptr(seg_ptr), Q, m, ptr(ptr_m), ptr(keep), ptr(cut), stream_ptr()),
+              "ocn_segment_keep_best")
+        _mark("segment_keep_best")
+    return (ptr_m, keep, cut) if return_cut else (ptr_m, keep)
+
+
 @_on_device
 def philox4x32(ctr: Tensor, key0: int, key1: int) -> Tensor:
     """Philox4x32-10 of every counter row (ocn_hip.h: ocn_philox4x32): ``ctr`` int32 [n, 4] holds the bit patterns of the four

@@ -112,6 +112,9 @@ def rank_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[SparseTen
     ``prefilter``: the model ranks the short list only, and ``retrieval_rank`` tells where the heuristic put every target among
     all the candidates within ``hops`` — taken in the retrieval pass itself, chunk by chunk under ``hops=3``.
 
+    ``prefilter=recommend.PathSums(kind, m[, decay])``: the tuple's stage for any ``m`` — the same ``retrieval_rank``, and
+    ``rank > 0`` exactly when ``1 <= retrieval_rank <= m`` with that ``m``, which is the one reported.
+
     ``prefilter=recommend.RandomWalks(...)``: ``retrieval_rank`` is the place by the walks' ``val`` among all VISITED candidates
     of the source, before the cut to ``m`` — 0 means that no walk reached the target (or that it is no candidate at all).
 

@@ -35,7 +35,12 @@ made and return a flat score vector.  This module makes the pairs and picks from
   ``embedding_candidates`` takes, per source, the ``m`` nodes with the largest inner product over ALL nodes
   (``ops.mips_topm_i8``: an exact int8 GEMM on the matrix cores whose epilogue keeps ``m`` keys per query — no [Q, N] matrix),
   ``prefilter=EmbeddingNeighbours(m)`` lets the model rank those, and ``prefilter=ShortListUnion(...)`` the per-source union
-  of several stages' lists: graph evidence where there is some, embeddings for the cold sources.  Opt-in.
+  of several stages' lists: graph evidence where there is some, embeddings for the cold sources.  Opt-in;
+* short lists beyond 128: the tuple form keeps its ``m`` best through ``ops.segment_topk``, whose sorted list a wave holds in
+  two registers per lane — ``m <= 128``.  A short list needs the SET of the ``m`` best in ascending node id, not their ranked
+  order: ``prefilter=PathSums(kind, m[, decay])`` means what the tuple means and takes the set through
+  ``ops.segment_keep_best`` — a radix select of the cut and one ordered compaction — for any ``m``
+  (``prefilter_candidates_long``).  Opt-in.
 
 Everything runs on one GPU; dealing the sources over several is not built here.
 """
@@ -248,6 +253,13 @@ def _keep_m_best(ptr: Tensor, edges: Tensor, val: Tensor, m: int) -> Tuple[Tenso
     return ptr_m, edges[keep]
 
 
+def _keep_m_long(ptr: Tensor, edges: Tensor, val: Tensor, m: int) -> Tuple[Tensor, Tensor]:
+    """What ``_keep_m_best`` returns, for any ``m``: the kept positions come from ``ops.segment_keep_best`` already ascending —
+    no ranked [Q, m] rectangle, no sort."""
+    ptr_m, keep = ops.segment_keep_best(val, ptr.contiguous(), m)
+    return ptr_m, edges[keep]
+
+
 def _budget_chunks(count: Tensor, budget: int):
     """Consecutive runs [a, b) of sources whose candidate total stays at or below ``budget``; a source above it goes alone."""
     sizes = count.tolist()
@@ -262,10 +274,12 @@ def _budget_chunks(count: Tensor, budget: int):
 
 
 def _path_index_pass(adj: SparseTensor, sources: Tensor, kind: str, m: Optional[int], known: Optional[SparseTensor], hops: int,
-                     decay: Optional[float], budget: Optional[int], targets: Optional[Tuple[Tensor, Tensor]] = None):
+                     decay: Optional[float], budget: Optional[int], targets: Optional[Tuple[Tensor, Tensor]] = None,
+                     keep=_keep_m_best):
     """One pass over the path-scored candidates of every source, shared by ``prefilter_candidates`` and ``ocn_amd.ranking``:
     (``short``, ``rank``, ``count``).  ``short``: the (``ptr_m``, ``edges_m``) of ``prefilter_candidates`` where ``m`` is given,
-    else None.  ``rank``: with ``targets = (tptr int64 [Q + 1], tnode int64 [P])``, the place of every target among ALL the
+    else None; ``keep(ptr, edges, val, m)`` selects it — ``_keep_m_best`` (``m <= ops.segment_topk_max_k()``) or
+    ``_keep_m_long`` (any ``m``).  ``rank``: with ``targets = (tptr int64 [Q + 1], tnode int64 [P])``, the place of every target among ALL the
     candidates of its source by the path index (``ops.segment_rank``: 0 = no candidate), else None.  ``count`` int64 [Q]: the
     candidates of every source.  Under ``hops=3`` both are taken chunk by chunk — a chunk's targets are ranked against the
     chunk's ``val`` before it is reduced to its ``m`` best — so the full three-hop list never exists at once and neither result
@@ -286,7 +300,7 @@ def _path_index_pass(adj: SparseTensor, sources: Tensor, kind: str, m: Optional[
             if targets is not None:
                 ranks.append(ops.segment_rank(val, ptr, edges, targets[0][a:b + 1] - tp[a], targets[1][tp[a]:tp[b]])[0])
             if m is not None:
-                parts.append(_keep_m_best(ptr, edges, val, m))
+                parts.append(keep(ptr, edges, val, m))
         rank = None
         if targets is not None:
             rank = torch.cat(ranks) if ranks else torch.zeros_like(targets[1])
@@ -303,7 +317,7 @@ def _path_index_pass(adj: SparseTensor, sources: Tensor, kind: str, m: Optional[
         raise ValueError("decay and budget belong to hops=3")
     ptr, edges, val = two_hop_scored_candidates(adj, sources, kind, known)
     rank = ops.segment_rank(val, ptr, edges, *targets)[0] if targets is not None else None
-    return (_keep_m_best(ptr, edges, val, m) if m is not None else None), rank, ptr[1:] - ptr[:-1]
+    return (keep(ptr, edges, val, m) if m is not None else None), rank, ptr[1:] - ptr[:-1]
 
 
 def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, known: Optional[SparseTensor] = None,
@@ -321,6 +335,47 @@ def prefilter_candidates(adj: SparseTensor, sources: Tensor, kind: str, m: int, 
     a chunk is filled, ranked and reduced to its ``m`` best before the next.  The result does not depend on ``budget``."""
     _check_path_sum(kind)
     return _path_index_pass(adj, sources, kind, _check_m(m), known, hops, decay, budget)[0]
+
+
+@dataclass(frozen=True)
+class PathSums:
+    """A path-sum retrieval stage without the 128 limit, a ``prefilter`` of ``recommend_links`` / ``ranking.rank_links`` and a
+    stage of a ``ShortListUnion``: it means what the tuple ``(kind, m[, decay])`` means — the same candidates, the same path
+    index, the same total order, the same ascending short list — and takes its ``m`` best through ``ops.segment_keep_best``
+    for every ``m``.  Checked on construction: ``kind`` in ``PATH_SUMS``, ``m`` an int in 1 .. ``ops.SEGMENT_KEEP_MAX_M``,
+    ``decay`` None or finite and >= 0.  ``decay`` is required under ``hops=3`` and refused under ``hops=2``; that is checked
+    where ``hops`` is known (``_check_prefilter``)."""
+    kind: str
+    m: int
+    decay: Optional[float] = None
+
+    def __post_init__(self):
+        _check_path_sum(self.kind)
+        if isinstance(self.m, bool) or not isinstance(self.m, int) or not 1 <= self.m <= ops.SEGMENT_KEEP_MAX_M:
+            raise ValueError(f"m must be an int in 1..{ops.SEGMENT_KEEP_MAX_M}, got {self.m!r}")
+        if self.decay is not None:
+            _check_decay(self.decay)
+
+
+def _check_path_sums_hops(stage: PathSums, hops: int) -> PathSums:
+    if not isinstance(stage, PathSums):
+        raise ValueError(f"stage must be a PathSums, got {stage!r}")
+    if hops == 3 and stage.decay is None:
+        raise ValueError("a PathSums stage under hops=3 needs decay (the weight of a 3-walk beside a 2-path; it has no default)")
+    if hops == 2 and stage.decay is not None:
+        raise ValueError("decay belongs to hops=3")
+    return stage
+
+
+def prefilter_candidates_long(adj: SparseTensor, sources: Tensor, stage: PathSums, known: Optional[SparseTensor] = None,
+                              hops: int = 2, budget: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """``prefilter_candidates(adj, sources, stage.kind, stage.m, known, hops, stage.decay, budget)`` for any ``m``: the same
+    (``ptr_m`` int64 [Q + 1], ``edges_m`` int64 [T_m, 2]) — bit for bit where ``m <= ops.segment_topk_max_k()`` — with the ``m``
+    best of every source taken as a set (``ops.segment_keep_best``: the cut by a radix select, then one ordered compaction)
+    instead of a ranked top-``m`` that is sorted back.  Under ``hops=3`` every chunk is reduced that way before the next is
+    filled; the result does not depend on ``budget``."""
+    stage = _check_path_sums_hops(stage, _check_hops(hops))
+    return _path_index_pass(adj, sources, stage.kind, stage.m, known, hops, stage.decay, budget, keep=_keep_m_long)[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -573,8 +628,9 @@ class EmbeddingNeighbours:
 
 class ShortListUnion:
     """A ``prefilter`` whose short list is, per source, the union (ascending, duplicate-free) of the short lists of its
-    ``stages``: each a ``(kind, m[, decay])`` tuple (``prefilter_candidates``; the arity goes with ``hops``), a ``RandomWalks``
-    (its ``length`` must equal ``hops``) or an ``EmbeddingNeighbours``.  What a mixed request needs: graph evidence where there
+    ``stages``: each a ``(kind, m[, decay])`` tuple (``prefilter_candidates``; the arity goes with ``hops``), a ``PathSums`` (the
+    same stage for any ``m``; its ``decay`` goes with ``hops``), a ``RandomWalks`` (its ``length`` must equal ``hops``) or an
+    ``EmbeddingNeighbours``.  What a mixed request needs: graph evidence where there
     is some, embeddings for the cold sources.  A source's list holds at most the sum of the stages' ``m``; ``k`` may be at most
     the largest ``m``.  There is no single retrieval order: ``ranking.rank_links`` reports ``retrieval_rank`` and ``m`` as None,
     and membership in the union is what ``coverage`` reads."""
@@ -583,8 +639,8 @@ class ShortListUnion:
         if not stages:
             raise ValueError("ShortListUnion needs at least one stage")
         for st in stages:
-            if not isinstance(st, (tuple, list, RandomWalks, EmbeddingNeighbours)):
-                raise ValueError(f"a stage must be a (kind, m[, decay]) tuple, a RandomWalks or an EmbeddingNeighbours, got {st!r}")
+            if not isinstance(st, (tuple, list, PathSums, RandomWalks, EmbeddingNeighbours)):
+                raise ValueError(f"a stage must be a (kind, m[, decay]) tuple, a PathSums, a RandomWalks or an EmbeddingNeighbours, got {st!r}")
         self.stages = tuple(tuple(st) if isinstance(st, list) else st for st in stages)
 
     def __repr__(self):
@@ -592,7 +648,7 @@ class ShortListUnion:
 
 
 def _stage_m(stage) -> int:
-    return stage.m if isinstance(stage, (RandomWalks, EmbeddingNeighbours)) else stage[1]
+    return stage.m if isinstance(stage, (PathSums, RandomWalks, EmbeddingNeighbours)) else stage[1]
 
 
 def _prefilter_m(prefilter) -> Optional[int]:
@@ -648,6 +704,8 @@ def _union_pass(union: ShortListUnion, h: Optional[Tensor], adj: SparseTensor, s
             p, e = _rw_pass(adj, sources, st, known)[0]
         elif isinstance(st, EmbeddingNeighbours):
             p, e = _emb_pass(st, h, adj, sources, known)[0]
+        elif isinstance(st, PathSums):
+            p, e = _path_index_pass(adj, sources, st.kind, st.m, known, hops, st.decay, None, keep=_keep_m_long)[0]
         else:
             p, e = _path_index_pass(adj, sources, st[0], st[1], known, hops, None if hops == 2 else st[2], None)[0]
         c = e[:, 1].to(torch.int32).contiguous()
@@ -659,7 +717,13 @@ def _union_pass(union: ShortListUnion, h: Optional[Tensor], adj: SparseTensor, s
 def _check_prefilter(prefilter, k: int, hops: int = 2):
     """(kind, m) for ``hops=2``, (kind, m, decay) for ``hops=3``: the other arity is refused.  A ``RandomWalks`` (checked when
     it was made) passes as it is where it keeps at least ``k`` and walks ``hops`` steps, an ``EmbeddingNeighbours`` where it
-    keeps at least ``k``; the stages of a ``ShortListUnion`` are checked one by one and the largest ``m`` must reach ``k``."""
+    keeps at least ``k``; the stages of a ``ShortListUnion`` are checked one by one and the largest ``m`` must reach ``k``.  A
+    ``PathSums`` passes where it keeps at least ``k`` and carries ``decay`` exactly under ``hops=3``; no 128 limit applies."""
+    if isinstance(prefilter, PathSums):
+        _check_path_sums_hops(prefilter, hops)
+        if k > prefilter.m:
+            raise ValueError(f"prefilter keeps m = {prefilter.m} candidates per source, fewer than k = {k}")
+        return prefilter
     if isinstance(prefilter, EmbeddingNeighbours):
         if k > prefilter.m:
             raise ValueError(f"prefilter keeps m = {prefilter.m} candidates per source, fewer than k = {k}")
@@ -700,6 +764,10 @@ def _candidates(adj: SparseTensor, adj2: Optional[SparseTensor], sources: Tensor
         return (*_union_pass(prefilter, h, adj, sources, known, hops), None)
     if isinstance(prefilter, RandomWalks):
         short, rank, _ = _rw_pass(adj, sources, prefilter, known, targets)
+        return short[0], short[1], rank
+    if isinstance(prefilter, PathSums):
+        short, rank, _ = _path_index_pass(adj, sources, prefilter.kind, prefilter.m, known, hops, prefilter.decay, None, targets,
+                                          keep=_keep_m_long)
         return short[0], short[1], rank
     if prefilter is not None:
         short, rank, _ = _path_index_pass(adj, sources, prefilter[0], prefilter[1], known, hops,
@@ -818,6 +886,12 @@ def recommend_links(predictor, h: Tensor, adj: SparseTensor, adj2: Optional[Spar
     of times the 2-hop list, so the form to serve is ``hops=3`` with ``prefilter=(kind, m, decay)``: the short list is then
     taken over three hops by ``P₂ + decay · P₃`` (``prefilter_candidates(..., hops=3, decay=decay)``).  A 2-tuple with
     ``hops=3`` or a 3-tuple with ``hops=2`` is refused.  cn6 is served over these <= 3 hops; its own evidence reaches four.
+
+    ``prefilter=PathSums(kind, m[, decay])``: the tuple form without its limit — the short list is
+    ``prefilter_candidates_long(adj, sources, prefilter, known, hops)``, the tuple's list where ``m <=
+    ops.segment_topk_max_k()`` and the ``m`` best by the same order beyond it; ``decay`` is required under ``hops=3`` and refused
+    under ``hops=2``.  The contract is the same sentence.  ``k <= m``, and ``k`` itself stays within
+    ``ops.segment_topk_max_k()``: the short list grows, the ranked answer does not.
 
     ``prefilter=RandomWalks(m, walks, length[, decay, seed])``: the short list is ``random_walk_short_list(adj, sources,
     prefilter, known)`` — the ``m`` most visited nodes of ``walks`` random walks per source, at a cost that does not grow with
